@@ -19,6 +19,13 @@ the GPU (a process that has initialised the GPU is never re-exec'ed) and relays 
 (WORLD_SIZE set) --gpus must equal WORLD_SIZE, otherwise the run fails loudly.  On a box with fewer than N GPUs the run
 fails unless --rehearse is given (gloo ranks sharing cuda:0; never a performance number, flagged in the line).
 
+A plain run sets up, warms up, times --steps passes and prints the line.  --full adds what takes runs of its own: the
+in-run HBM traffic (rocprofv3 PMC passes), the roofline of the step kernel (a profiled pass), the bit-exactness check
+against the oracle (first 12 steps) and the CPU baseline.  --dump-outputs DIR writes what the last timed pass computed
+as DIR/<name>.npy (float64): the log-likelihood(s) and per-step log conditional likelihoods, and in replicas mode the
+log-mean-exp and rank 0's particles and normalised weights after the last step (16 MiB at N = 2^20).  The inputs are
+fixed (seeded), and the last timed pass always runs the base seed, so two builds can be compared output for output.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -179,6 +186,10 @@ def main():
     ap.add_argument("--rehearse", action="store_true", help="gloo ranks sharing cuda:0 when the box has fewer GPUs than --gpus")
     ap.add_argument("--driver", choices=["native", "python"], default="native",
                     help="sharded bootstrap filter: the C++ loop over RCCL (ssme_pf_shard_run_series) or the Python loop over torch.distributed")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure traffic and roofline, check against the oracle and time the CPU baseline (runs of their own)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed pass computed to DIR/<name>.npy")
     ap.add_argument("--particles", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--resampler", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--no-cpu-baseline", action="store_true", help=argparse.SUPPRESS)
@@ -208,8 +219,8 @@ def main():
 
     n = args.particles or (N_PARTICLES_LW if args.lw else N_PARTICLES)
     # --- in-run HBM traffic of the dominant kernel (rank 0 at N = 1 only), before this process initialises the GPU ---
-    traffic, traffic_note = None, "measured at --gpus 1, replicas mode, default N only"
-    if world == 1 and args.mode == "replicas" and n == N_PARTICLES and not args.no_traffic:
+    traffic, traffic_note = None, "measured with --full at --gpus 1, replicas mode, default N only"
+    if args.full and world == 1 and args.mode == "replicas" and n == N_PARTICLES and not args.no_traffic:
         traffic, traffic_note = measure_traffic()
 
     import torch
@@ -289,8 +300,18 @@ def main():
         lme = ll                                                  # one filter: identical on every rank
         psteps_per_pass = float(n) * T
 
+    outputs = None
+    if args.dump_outputs is not None:
+        # what the last timed pass computed, read back before anything else runs on the filter
+        if args.mode == "replicas":
+            px, pw = bank.weights(0)
+            outputs = {"loglik": np.asarray(lls, dtype=np.float64), "loglik_log_mean_exp": np.array([lme], dtype=np.float64),
+                       "per_step_loglik": bank.per_step()[0], "particles": px, "weights": pw}
+        else:
+            outputs = {"loglik": np.array([ll], dtype=np.float64), "per_step_loglik": np.asarray(filt.per_step(), dtype=np.float64)}
+
     short_ll = None
-    if args.mode == "sharded" and not args.lw:
+    if args.full and args.mode == "sharded" and not args.lw:
         short_ll = filt.run_series_native(y[:12]) if native else filt.run_series(y[:12])       # every rank takes part
     if rank == 0:
         value = psteps_per_pass * args.steps / dt
@@ -320,6 +341,7 @@ def main():
         }
         if args.mode == "replicas":
             out["device_ms_per_step"] = dev_ms / args.steps
+        if args.mode == "replicas" and args.full:
             # launch duration of the step kernel, live, HIP events on the handle's stream
             prof = bank.profile_series(y)
             k_us = prof["filter_step_us"]
@@ -337,7 +359,7 @@ def main():
             d, lg, lo = oracle_delta(bank, y, 12, n)
             out["loglik_delta_vs_oracle"] = {"abs_delta": d, "gpu": lg, "oracle": lo,
                                              "sample": "first 12 steps, full N, oracle Philox mode (bit-matched)"}
-        else:
+        elif args.mode == "sharded":
             # the step of a sharded filter includes its collectives: whole-step rate per rank, flagged as such
             bpp = BYTES_PER_PSTEP_LW if args.lw else BYTES_PER_PSTEP
             step_us = dt / args.steps / T * 1e6
@@ -355,16 +377,21 @@ def main():
                 else:
                     out["config"]["driver"] = "Python over torch.distributed"
                     out["roofline"]["tiles_received_last_pass_rank0"] = int(filt.exchanged_tiles)
-                # the sharded filter must reproduce the unsharded oracle bit for bit: first 12 steps at full N
-                from oracle import oracle as O
-                lo = O.Filter(O.MODEL_SVOL, n, THETA, SEED, rep=0, resampler=args.resampler, tile=2048).run_series(y[:12])[0]
-                out["loglik_delta_vs_oracle"] = {"abs_delta": abs(short_ll - lo), "gpu": short_ll, "oracle": lo,
-                                                 "sample": "first 12 steps, full N, oracle Philox mode (bit-matched), unsharded oracle"}
+                if args.full:
+                    # the sharded filter must reproduce the unsharded oracle bit for bit: first 12 steps at full N
+                    from oracle import oracle as O
+                    lo = O.Filter(O.MODEL_SVOL, n, THETA, SEED, rep=0, resampler=args.resampler, tile=2048).run_series(y[:12])[0]
+                    out["loglik_delta_vs_oracle"] = {"abs_delta": abs(short_ll - lo), "gpu": short_ll, "oracle": lo,
+                                                     "sample": "first 12 steps, full N, oracle Philox mode (bit-matched), unsharded oracle"}
             else:
                 out["config"]["driver"] = ("C++ over RCCL (ssme_lw_shard_run_series): " + getattr(filt, "native_path", "?")) if native else "Python over torch.distributed"
                 out["roofline"]["tiles_received_last_pass_rank0"] = int(filt.native_state()[2] if native else filt.exchanged_tiles)
-        if not args.no_cpu_baseline and world == 1 and args.mode == "replicas":
+        if args.full and not args.no_cpu_baseline and world == 1 and args.mode == "replicas":
             out["cpu_baseline"] = cpu_baseline(np.loadtxt(os.path.join(ROOT, "tests", "golden", "spy_returns.csv")), args.cpu_steps)
+        if outputs is not None:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, a in outputs.items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(out) + "\n").encode())
     (bank if args.mode == "replicas" else filt).close()

@@ -408,18 +408,28 @@ def test_liu_west_delta_one_freezes_parameters(oracle):
 # ---- oracle/_ref: the reference's own thread_pool.h (the one hot-path header that builds here) -----------------------
 def test_log_mean_exp_pinned_by_reference_thread_pool(oracle):
     """thread_pool<>::work (thread_pool.h:189-215,263-268) computes the replicate log-mean-exp; the oracle's and the
-    product host code's versions must agree with it.  Skipped only if oracle/_ref could not be built or shipped."""
-    if oracle.build_ref() is None:
-        pytest.skip("oracle/_ref not available (no /root/reference and no prebuilt library)")
+    product host code's versions must agree with it.  The reference's values are stored in
+    golden/ref_thread_pool_lme.npz (golden/make_golden_ref_lme.py); where oracle/_ref is built, the live reference
+    must reproduce them too."""
     from ssme_amd.parallel import log_mean_exp
-    assert abs(oracle.ref_log_mean_exp(np.full(10000, 3.0)) - 3.0) < 1e-3        # the reference's own KAT, test_thread_pool.cpp:39-46
+    g = np.load(os.path.join(os.path.dirname(__file__), "golden", "ref_thread_pool_lme.npz"))
+    live = oracle.build_ref() is not None
+    assert abs(g["kat_want"][0] - 3.0) < 1e-3                  # the reference's own KAT, test_thread_pool.cpp:39-46
+    if live:
+        assert oracle.ref_log_mean_exp(np.full(10000, 3.0)) == g["kat_want"][0]
     rng = np.random.default_rng(5)
-    for n in (1, 2, 7, 100, 1000):
-        for scale in (1e-3, 1.0, 50.0, 700.0):
-            v = -4700.0 + scale * rng.standard_normal(n)
-            want = oracle.ref_log_mean_exp(v)
-            assert abs(oracle.log_mean_exp(v) - want) <= 1e-12 * abs(want)
-            assert abs(log_mean_exp(v) - want) <= 1e-12 * abs(want)
+    cases = [(n, scale) for n in (1, 2, 7, 100, 1000) for scale in (1e-3, 1.0, 50.0, 700.0)]
+    assert [(int(n), float(s)) for n, s in zip(g["cases_n"], g["cases_scale"])] == cases
+    off = 0
+    for (n, scale), want in zip(cases, g["cases_want"]):
+        v = g["cases_v"][off:off + n]
+        off += n
+        np.testing.assert_array_equal(v, -4700.0 + scale * rng.standard_normal(n))
+        if live:
+            assert oracle.ref_log_mean_exp(v) == want
+        assert abs(oracle.log_mean_exp(v) - want) <= 1e-12 * abs(want)
+        assert abs(log_mean_exp(v) - want) <= 1e-12 * abs(want)
+    assert off == g["cases_v"].size
 
 
 @pytest.mark.parametrize("n", [300, 5000])

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Round-end measurement on the GPU box (run from the repo root through gpurun):
 #   bash tools/profile_round.sh r02
-# 1. bench.py (default flags, in-run PMC traffic)     -> profiles/<tag>_bench.json
+# 1. bench.py --full (in-run PMC traffic)             -> profiles/<tag>_bench.json
 # 2. rocprofv3 --kernel-trace --stats of the same cmd -> profiles/<tag>_bench_kernel_stats.csv
 # 3. SQ instruction counters of the step kernel       -> profiles/<tag>_valu_counters.txt
 # 4. Liu-West: kernel stats + FETCH/WRITE PMC         -> profiles/<tag>_liu_west_*.{csv,txt}
@@ -11,9 +11,9 @@ TAG=${1:-r02}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-python3 bench.py > $OUT/${TAG}_bench.json 2> $OUT/bench.err
+python3 bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/bench.err
 cat $OUT/${TAG}_bench.json | cut -c1-600
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -- python3 bench.py --no-cpu-baseline --no-traffic > $OUT/${TAG}_bench_under_rocprof.json 2> $OUT/prof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -- python3 bench.py --full --no-cpu-baseline --no-traffic > $OUT/${TAG}_bench_under_rocprof.json 2> $OUT/prof.err
 cp $(find $OUT/prof -name '*kernel_stats.csv' | head -1) $OUT/${TAG}_bench_kernel_stats.csv
 head -6 $OUT/${TAG}_bench_kernel_stats.csv
 # SQ counters (own passes, no tracing)
@@ -49,9 +49,9 @@ cp $(find $OUT/pc4 -name '*kernel_stats.csv' | head -1) $OUT/${TAG}_config4_kern
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/plw -- python3 tools/prof_run.py --lw --T 24 --passes 2 --n 16777216 > $OUT/plw.log 2>&1
 cp $(find $OUT/plw -name '*kernel_stats.csv' | head -1) $OUT/${TAG}_liu_west_2p24_kernel_stats.csv
 head -4 $OUT/${TAG}_n2p23_kernel_stats.csv | cut -c1-150; head -3 $OUT/${TAG}_config4_kernel_stats.csv | cut -c1-150; head -8 $OUT/${TAG}_liu_west_2p24_kernel_stats.csv | cut -c1-150
-python3 bench.py --mode sharded --steps 2 --no-cpu-baseline > $OUT/${TAG}_bench_sharded_world1_native.json 2> $OUT/sh1.err
-python3 bench.py --mode sharded --driver python --steps 2 --no-cpu-baseline > $OUT/${TAG}_bench_sharded_world1_python.json 2> $OUT/sh2.err
-python3 bench.py --mode sharded --lw --particles 2097152 --steps 2 --no-cpu-baseline > $OUT/${TAG}_bench_sharded_world1_lw_native.json 2> $OUT/sh3.err
+python3 bench.py --full --mode sharded --steps 2 --no-cpu-baseline > $OUT/${TAG}_bench_sharded_world1_native.json 2> $OUT/sh1.err
+python3 bench.py --full --mode sharded --driver python --steps 2 --no-cpu-baseline > $OUT/${TAG}_bench_sharded_world1_python.json 2> $OUT/sh2.err
+python3 bench.py --full --mode sharded --lw --particles 2097152 --steps 2 --no-cpu-baseline > $OUT/${TAG}_bench_sharded_world1_lw_native.json 2> $OUT/sh3.err
 cut -c1-300 $OUT/${TAG}_bench_sharded_world1_native.json; cut -c1-300 $OUT/${TAG}_bench_sharded_world1_python.json
 g++ -std=c++17 -O2 -Iinclude tools/step_latency.cpp -o tools/step_latency -Lssme_amd -l:libssme_pf.so -Wl,-rpath,$PWD/ssme_amd
 ./tools/step_latency tests/golden/spy_returns.csv > $OUT/${TAG}_step_api_latency.txt
