@@ -38,6 +38,9 @@ constexpr int kSplitLevel2Above = 1024;    // measured (profiles/r02_level2_spli
 constexpr int kL2Scratch = 64;             // doubles of l2_work per filter after the block-local scans: [0, 16) block totals, [16] m,
 constexpr int kL2Offsets = 32;             //   [kL2Offsets, + 17) exclusive offsets of the blocks and S' (l2_inkernel)
 constexpr int kMaxTilesSplit = 16384;      // split level-2 (k_level2_plan + k_filter_step<.., true>): N <= 2^25
+#ifndef SSME_SEARCH_WINDOW
+#define SSME_SEARCH_WINDOW 16              // staged_search: a pair's second target is counted in a window of this many elements (0: off)
+#endif
 constexpr int kStageTiles = 3;             // cdf tiles staged in LDS per output tile
 constexpr int kEShift = 35;                // exponential spacings: qE = rne(E * 2^35)
 constexpr int kTileShift = 41;             // tile-local fixed point: q = rne(exp(logw - m_tile) * 2^41), tile sums <= 2^52
@@ -535,13 +538,14 @@ __device__ __forceinline__ void prio_at(int mode, int idx) {
 template <int STEP, int NQ>
 struct lds_count_search {
     static __device__ __forceinline__ void run(uint32_t (&pa)[NQ], const double (&t)[NQ]) {
-        static_assert(NQ == 2 || NQ == 4 || NQ == 8, "one, two or four particle pairs per thread");
+        static_assert(NQ == 1 || NQ == 2 || NQ == 4 || NQ == 8, "one to eight searches per thread");
         double v[NQ];
 #pragma unroll
         for (int q = 0; q < NQ; ++q) asm volatile("ds_read_b64 %0, %1 offset:%2" : "=&v"(v[q]) : "v"(pa[q]), "n"((STEP - 1) * 8) : "memory");
         if constexpr (NQ == 8) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]));
         else if constexpr (NQ == 4) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]));
-        else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v[0]), "+v"(v[1]));
+        else if constexpr (NQ == 2) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v[0]), "+v"(v[1]));
+        else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v[0]));
 #pragma unroll
         for (int q = 0; q < NQ; ++q) pa[q] = (v[q] < t[q]) ? pa[q] + (uint32_t)(STEP * 8) : pa[q];
         lds_count_search<STEP / 2, NQ>::run(pa, t);
@@ -597,13 +601,50 @@ __device__ __forceinline__ void staged_search(const double (&tau)[NK][2], int sp
             }
         }
     }
-    uint32_t pa[2 * NK];
-    double tq[2 * NK];
+    // With one pair per thread the window is not used: its log2 W probes lengthen a chain that then runs alone (N = 2^16,
+    // 512-particle tiles: 6.73 -> 7.00 us per step, profiles/r04_search_philox_ab.txt); with two or more the chains of the pairs overlap.
+    if constexpr (SSME_SEARCH_WINDOW > 0 && NK >= 2) {
+        // The pair's first targets: a full descent, NK chains together.
+        constexpr int W = SSME_SEARCH_WINDOW > 0 ? SSME_SEARCH_WINDOW : 2;
+        static_assert(W >= 2 && (W & (W - 1)) == 0 && W <= TILE, "the window is a power of two inside the tile");
+        uint32_t pa0[NK], pa1[NK], top[NK];
+        double t0[NK], t1[NK];
 #pragma unroll
-    for (int k = 0; k < NK; ++k) { pa[2 * k] = pb[k][0]; pa[2 * k + 1] = pb[k][1]; tq[2 * k] = tloc[k][0]; tq[2 * k + 1] = tloc[k][1]; }
-    lds_count_search<TILE / 2, 2 * NK>::run(pa, tq);
+        for (int k = 0; k < NK; ++k) { pa0[k] = pb[k][0]; t0[k] = tloc[k][0]; t1[k] = tloc[k][1]; }
+        lds_count_search<TILE / 2, NK>::run(pa0, t0);
+        // The second target is not below the first (both resampling orders are sorted), so in the same tile every element below
+        // the first count is below it too and its count starts there; in a later tile it starts at that tile's first element.
+        // It is counted inside a window of W elements, moved down if it would leave the tile (an element below the start is
+        // below the target as well): log2 W probes.  A count that reaches the window's last element is not bracketed; then
+        // the wave repeats the full descent for its second targets (a uniform branch), so the result is the full search's
+        // for any weights.
 #pragma unroll
-    for (int k = 0; k < NK; ++k) { off[k][0] = (int)((pa[2 * k] - stage_a) >> 3); off[k][1] = (int)((pa[2 * k + 1] - stage_a) >> 3); }
+        for (int k = 0; k < NK; ++k) {
+            const uint32_t lo = pb[k][1], hi = pb[k][1] + (uint32_t)((TILE - W) * 8);
+            const uint32_t st = pa0[k] > lo ? pa0[k] : lo;
+            pa1[k] = st < hi ? st : hi;
+            top[k] = pa1[k] + (uint32_t)((W - 1) * 8);
+        }
+        lds_count_search<W / 2, NK>::run(pa1, t1);
+        bool open = false;
+#pragma unroll
+        for (int k = 0; k < NK; ++k) open = open || pa1[k] == top[k];
+        if (__builtin_amdgcn_ballot_w64(open)) {
+#pragma unroll
+            for (int k = 0; k < NK; ++k) pa1[k] = pb[k][1];
+            lds_count_search<TILE / 2, NK>::run(pa1, t1);
+        }
+#pragma unroll
+        for (int k = 0; k < NK; ++k) { off[k][0] = (int)((pa0[k] - stage_a) >> 3); off[k][1] = (int)((pa1[k] - stage_a) >> 3); }
+    } else {
+        uint32_t pa[2 * NK];
+        double tq[2 * NK];
+#pragma unroll
+        for (int k = 0; k < NK; ++k) { pa[2 * k] = pb[k][0]; pa[2 * k + 1] = pb[k][1]; tq[2 * k] = tloc[k][0]; tq[2 * k + 1] = tloc[k][1]; }
+        lds_count_search<TILE / 2, 2 * NK>::run(pa, tq);
+#pragma unroll
+        for (int k = 0; k < NK; ++k) { off[k][0] = (int)((pa[2 * k] - stage_a) >> 3); off[k][1] = (int)((pa[2 * k + 1] - stage_a) >> 3); }
+    }
 }
 
 // 16-byte store of a particle pair.  stream = 1: non-temporal, the lines leave the XCD's L2 as they are written.  A launch

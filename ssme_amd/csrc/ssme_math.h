@@ -50,14 +50,24 @@ SSME_HD double pow2i(int n) { return bits2d((uint64_t)(n + 1023) << 52); }
 // ---- Philox4x32-10 -------------------------------------------------------------------
 struct u32x4 { uint32_t v0, v1, v2, v3; };
 
+// a ^ b ^ c.  On gfx950 one v_bitop3_b32 (truth table 0x96, the key may sit in an SGPR); hipcc emits two v_xor_b32 for
+// the plain expression (kept for the host and, with -DSSME_PLAIN_XOR3, for timing comparisons).
+SSME_HD uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(SSME_PLAIN_XOR3)
+    return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
+#else
+    return a ^ b ^ c;
+#endif
+}
+
 SSME_HD u32x4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
 #pragma unroll
     for (int r = 0; r < 10; ++r) {
         if (r) { k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
         const uint64_t p0 = (uint64_t)0xD2511F53u * c0;     // one v_mad_u64_u32 each
         const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
-        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        const uint32_t n0 = xor3((uint32_t)(p1 >> 32), c1, k0);
+        const uint32_t n2 = xor3((uint32_t)(p0 >> 32), c3, k1);
         c1 = (uint32_t)p1; c3 = (uint32_t)p0; c0 = n0; c2 = n2;
     }
     return u32x4{c0, c1, c2, c3};
