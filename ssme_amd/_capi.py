@@ -187,12 +187,14 @@ def u64ptr(a):
     return None if a is None else a.ctypes.data_as(C.POINTER(C.c_uint64))
 
 
-def check(status, handle=None):
+def check(status, handle=None, last_error=None):
+    """Raise SsmeError unless status is OK.  For HIP, state and unsupported-configuration errors of a handle the message
+    ends with the handle's last error, read by last_error (ssme_pf_last_error, or ssme_lw_last_error for Liu-West handles)."""
     if status != OK:
         L = lib()
         msg = L.ssme_pf_strerror(status).decode()
-        if handle is not None and status == ERR_HIP:
-            msg += " (" + L.ssme_pf_last_error(handle).decode() + ")"
+        if handle is not None and status in (ERR_HIP, ERR_STATE, ERR_UNSUPPORTED):
+            msg += " (" + (last_error or L.ssme_pf_last_error)(handle).decode() + ")"
         raise SsmeError(status, msg)
 
 

@@ -1,0 +1,199 @@
+// handle_core.h -- host state and plumbing that the two filter handles of pf_api.hip share (the bootstrap handle ssme_pf_s and
+// the Liu-West handle ssme_lw_s both derive from HandleCore): tile layout, stream and events, device buffers owned by the
+// handle, error reporting, and the entry points that both C ABIs offer under their own names.
+#pragma once
+#include "../../include/ssme_pf.h"
+#include "pf_kernels.h"
+
+#include <string>
+#include <type_traits>
+#include <utility>
+#include <vector>
+
+namespace ssme {
+
+static int next_pow2(int n) { int p = 1; while (p < n) p <<= 1; return p; }
+static int ceil_log2(int n) { int k = 0; while ((1ll << k) < n) ++k; return k; }
+
+constexpr int kStepGammaChunk = 64;     // step APIs: Gamma-table rows drawn at a time
+
+struct Layout {
+    int N, R, B, Npad, Bs, Bpow2, rshift;
+    int tile;                      // particles per tile: 2048, 1024 or 512 (cfg.tile_particles or default_tile); sharded and Liu-West handles: 2048
+    int split_l2;                  // level-2 by the split kernels (filters of more than kSplitLevel2Above tiles, or forced by set_debug)
+    size_t lds_bytes, lds_bytes_big, lds_bytes_plan;
+    int shard_rank, shard_world;   // particle-sharded filter: this handle computes tiles [rank*Bl, rank*Bl + sh_Bown); world = 0: unsharded
+    int sh_Bl, sh_Bown;            // Bl = ceil(B / world) tiles per rank in every layout (gathers, halos); the last rank owns B - (world-1) Bl >= 1 of them
+};
+
+// n_filters filters of n_particles particles in tiles of `tile` particles, and rank `rank`'s share of them when world > 0.
+// Returns false if the last rank would own no tile.
+static bool set_layout(Layout* l, int n_particles, int n_filters, int tile, int rank, int world) {
+    const int B = (n_particles + tile - 1) / tile;
+    l->N = n_particles; l->R = n_filters; l->B = B; l->tile = tile; l->Npad = B * tile;
+    l->Bs = (B + 1) & ~1; l->Bpow2 = next_pow2(B);
+    l->rshift = 52 - ceil_log2(l->Npad);
+    l->split_l2 = B > kSplitLevel2Above ? 1 : 0;
+    // in-kernel level-2 keeps T' and A/A' of all tiles in LDS (possible up to 2048 tiles, whichever policy is the default)
+    l->lds_bytes = sizeof(double) * (2 * (size_t)(B > kMaxTilesPerFilter ? 2 : (l->Bpow2 < 2 ? 2 : l->Bpow2)) + (size_t)kStageTiles * tile);
+    l->lds_bytes_big = sizeof(double) * (4 + (size_t)kStageTiles * tile);
+    l->lds_bytes_plan = sizeof(double) * (size_t)(l->Bpow2 < 2 ? 2 : l->Bpow2);
+    l->shard_rank = rank; l->shard_world = world;
+    l->sh_Bl = l->sh_Bown = 0;
+    if (world > 0) {
+        // ceil(B / world) tiles per rank; the last rank takes what is left (fewer tiles, a ragged last tile)
+        l->sh_Bl = (B + world - 1) / world;
+        l->sh_Bown = B - rank * l->sh_Bl < l->sh_Bl ? B - rank * l->sh_Bl : l->sh_Bl;
+    }
+    return world < 1 || (world - 1) * l->sh_Bl < B;
+}
+
+struct HandleCore : Layout {
+    hipStream_t stream;            // where the handle's work is queued: own_stream, or the caller's (set_stream)
+    hipStream_t own_stream;        // the stream created with the handle
+    hipEvent_t ev0, ev1;           // around the last series
+    float last_ms;
+    std::string err;               // last_error
+    int t;                         // next time index
+    int32_t* plan_dev;             // [world][2] source-tile ranges (k_shard_plan)
+    double* pin;                   // pinned, device-mapped host staging; the step API's R results are written here by the device
+    double* pin_dev;               // the same memory as the device sees it
+    uint32_t* keybuf;              // [2] Philox key = seed (lo, hi)
+    double *ybuf, *zbuf, *per_step;     // observations (ycap time rows), per-step log-likelihood terms [R][tcap]
+    int ycap, tcap, gcap;          // time rows of ybuf / zbuf, per_step, the Gamma tables
+    int gamma_t0, gamma_rows;      // step API: the Gamma tables hold time indices gamma_t0 .. gamma_t0 + gamma_rows - 1
+    // native RCCL drivers (shard_driver.h)
+    int32_t* sh_flag;              // [0] a window left the halo ON THIS RANK, [1] / [2] widest reach left / right of the own tiles (in tiles),
+                                   // [3] max of [0] over all ranks (reduce_flags after the time loop): what the fallback decision reads
+    int32_t sh_stats[4];           // host copy of sh_flag after the last native series
+    int sh_margin, sh_rows;        // halo margin (tiles on each side) and rows [margin | Bl own | margin] of the halo buffers
+    int sh_check;                  // 1 while a driver launches a step on the fixed halo: the kernel verifies its source tiles
+    long sh_exchanged;             // tiles received from other ranks during the last native series
+    std::vector<std::pair<void*, bool>> owned;     // (buffer, pinned) from own_alloc: what release_core frees
+};
+
+static int fail(HandleCore* h, const char* what, hipError_t e) {
+    if (h) h->err = std::string(what) + ": " + hipGetErrorString(e);
+    return SSME_ERR_HIP;
+}
+#define HIPCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail(h, #call, e_); } while (0)
+
+// Every device buffer of a handle, and its pinned host memory, comes from here and is freed by release_core.  Whatever p
+// held is freed first (growth).
+enum class Mem { device, zeroed, pinned };   // pinned: host memory, device-mapped
+template <class T>
+static hipError_t own_alloc(HandleCore* h, T*& p, size_t bytes, Mem kind = Mem::device) {
+    if (p) {
+        for (size_t i = 0; i < h->owned.size(); ++i)
+            if (h->owned[i].first == p) {
+                if (h->owned[i].second) hipHostFree(p); else hipFree(p);
+                h->owned.erase(h->owned.begin() + i);
+                break;
+            }
+        p = nullptr;
+    }
+    void* q = nullptr;
+    hipError_t e = kind == Mem::pinned ? hipHostMalloc(&q, bytes, hipHostMallocMapped) : hipMalloc(&q, bytes);
+    if (e != hipSuccess) return e;
+    h->owned.emplace_back(q, kind == Mem::pinned);
+    p = static_cast<T*>(q);
+    return kind == Mem::zeroed ? hipMemset(q, 0, bytes) : hipSuccess;
+}
+
+static int create_stream(HandleCore* h) {
+    HIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    h->own_stream = h->stream;
+    HIPCHK(hipEventCreate(&h->ev0));
+    HIPCHK(hipEventCreate(&h->ev1));
+    return SSME_OK;
+}
+
+// what the two destroy functions share: wait for the handle's work, free its buffers, events and own stream
+static void release_core(HandleCore* h) {
+    if (h->stream) hipStreamSynchronize(h->stream);
+    for (auto& b : h->owned) { if (b.second) hipHostFree(b.first); else hipFree(b.first); }
+    h->owned.clear();
+    if (h->ev0) hipEventDestroy(h->ev0);
+    if (h->ev1) hipEventDestroy(h->ev1);
+    if (h->own_stream) hipStreamDestroy(h->own_stream);
+}
+
+// observations (dy values per time index, and z) and per-step terms for T time indices; *moved = true if a buffer moved
+static int ensure_series_buffers(HandleCore* h, int T, int dy, bool* moved) {
+    if (T > h->ycap) {
+        HIPCHK(own_alloc(h, h->ybuf, sizeof(double) * T * dy));
+        HIPCHK(own_alloc(h, h->zbuf, sizeof(double) * T, Mem::zeroed));
+        h->ycap = T; *moved = true;
+    }
+    if (T > h->tcap) {
+        HIPCHK(own_alloc(h, h->per_step, sizeof(double) * (size_t)T * h->R));
+        h->tcap = T; *moved = true;
+    }
+    return SSME_OK;
+}
+
+// ---- entry points that both ABIs repeat (H: ssme_pf_s or ssme_lw_s) -------------------------------------------------------
+template <class H>
+static int set_stream(H* h, void* hip_stream) {
+    if (!h) return SSME_ERR_INVALID_ARG;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->stream = hip_stream ? reinterpret_cast<hipStream_t>(hip_stream) : h->own_stream;
+    return SSME_OK;
+}
+
+// particles this rank owns: sh_Bown tiles, the last of them ragged on the last rank
+static size_t own_particles(const HandleCore* h) {
+    const size_t first = (size_t)h->shard_rank * h->sh_Bl * kTile, own = (size_t)h->sh_Bown * kTile;
+    return (size_t)h->N - first < own ? (size_t)h->N - first : own;
+}
+
+static int shard_layout(const HandleCore* h, int32_t* out4) {
+    if (!h || !out4) return SSME_ERR_INVALID_ARG;
+    if (h->shard_world < 1) return SSME_ERR_STATE;
+    out4[0] = h->B; out4[1] = h->sh_Bl; out4[2] = h->sh_Bown; out4[3] = (int32_t)own_particles(h);
+    return SSME_OK;
+}
+
+template <class H>
+static int read_per_step(H* h, double* out, int T) {
+    if (!h || !out || T < 1 || T > h->tcap) return SSME_ERR_INVALID_ARG;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    // device layout is [R][tcap]; return [R][T]
+    for (int r = 0; r < h->R; ++r)
+        HIPCHK(hipMemcpyAsync(out + (size_t)r * T, h->per_step + (size_t)r * h->tcap, sizeof(double) * T, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return SSME_OK;
+}
+
+// the R log-likelihoods from the device scalars (FilterScalars or LwScalars); synchronises, out may be null
+template <class H>
+static int read_loglik(H* h, double* out) {
+    using Scalars = std::remove_pointer_t<decltype(h->scal)>;
+    std::vector<Scalars> sc(h->R);
+    HIPCHK(hipMemcpyAsync(sc.data(), h->scal, sizeof(Scalars) * h->R, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (out) for (int r = 0; r < h->R; ++r) out[r] = sc[r].loglik;
+    return SSME_OK;
+}
+
+static int elapsed_ms(const HandleCore* h, float* ms) {
+    if (!h || !ms) return SSME_ERR_INVALID_ARG;
+    *ms = h->last_ms;
+    return SSME_OK;
+}
+
+static const char* last_error(const HandleCore* h) { return h ? h->err.c_str() : ""; }
+
+// step APIs: the Gamma-table row of time index h->t.  The tables are drawn kStepGammaChunk time steps at a time (data
+// independent), so that the table launches are paid once per chunk and not once per call.
+template <class H>
+static int step_gamma_row(H* h, void (*draw)(H* h, int t0, int nT)) {
+    if (h->t < h->gamma_t0 || h->t >= h->gamma_t0 + h->gamma_rows) {
+        draw(h, h->t, kStepGammaChunk);
+        h->gamma_t0 = h->t; h->gamma_rows = kStepGammaChunk;
+    }
+    return h->t - h->gamma_t0;
+}
+
+}  // namespace ssme

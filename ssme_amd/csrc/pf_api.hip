@@ -5,6 +5,7 @@
 #include "pf_kernels.h"
 #include "lw_kernels.h"
 #include "pf_small.h"
+#include "handle_core.h"
 #include "shard_driver.h"
 
 #include <atomic>
@@ -19,76 +20,46 @@
 
 using namespace ssme;
 
-struct ssme_pf_s {
+struct ssme_pf_s : HandleCore {
     ssme_pf_config cfg;
-    int N, R, Npad, B, Bs, Bpow2, rshift;
-    int tile;                // particles per tile: 2048, 1024 or 512 (cfg.tile_particles, or by N: default_tile)
-    size_t lds_bytes;
-    int t;                   // next time index
     bool params_set;
     int debug_anc, keep_logw;
     int graph_mode;
-    int shard_rank, shard_world;   // particle-sharded filter: this handle computes tiles [rank*Bl, rank*Bl + sh_Bown); world = 0: unsharded
-    int sh_Bl, sh_Bown;            // Bl = ceil(B / world) tiles per rank in every layout (gathers, halos); the last rank owns B - (world-1) Bl >= 1 of them
-    hipStream_t own_stream;  // the stream created with the handle (stream may be replaced by ssme_pf_set_stream)
-    int32_t* plan_dev;       // [world][2] source-tile ranges (k_shard_plan)
-    int split_l2;            // 1: level-2 by k_level2_plan (filters of more than 2048 tiles, or forced by set_debug bit 2)
     double *l2_T, *l2_R;     // [R][Bs] split level-2 outputs
     double* l2_work;         // [R][Bs] + [R][32]: scratch of the multi-workgroup level-2
     int32_t *l2_lo, *l2_hi;
     int32_t* l2_ticket;      // [R] arrival counters of the one-launch level-2 (StepArgs::l2_inkernel)
     int l2_tables;           // set_debug bit 4: the split level-2 writes its tables and ranges (k_level2_plan / k_l2_ranges), as sharded filters do
-    size_t lds_bytes_big, lds_bytes_plan;
     double* small_ms;        // [R][tcap][2] scratch of the one-tile whole-series kernel
     double* yz_step;         // device [2]: y and z of the step API, uploaded by ONE copy
     int32_t* ticket;         // device [R]: arrival counters of the step API's in-kernel accounting (zero between launches)
-    double* pin;             // pinned, device-mapped host staging: [2 .. 2+R) log conditional likelihoods of the step API (written by the accounting kernel)
-    double* pin_dev;         // the same memory as the device sees it
-    int gamma_t0, gamma_rows;   // step API: the Gamma tables hold time indices gamma_t0 .. gamma_t0 + gamma_rows - 1
     int num_cus;             // compute units of the device (priority schedule of the step kernel)
     int small_series;        // 1: one-tile filters run the whole series in one launch (k_filter_series_small)
     double y_step_v[3];      // step API: components 1 .. of this call's vector observation
     int dx, dy;              // state / observation dimension: 1, or the user model's dim_x / dim_y (model_api.h)
     int nt;                  // threads per 2048-particle tile of k_filter_step (256, 512, 1024)
     // C++ shard driver (ssme_pf_shard_run_series): halo buffers [margin | own tiles | margin] x 2048 doubles, ping-pong;
-    // this rank's tile sums / maxima, their gathered and repacked forms; exact-path window buffers; flag + statistics
-    double *sh_x[2], *sh_c[2], *sh_loc, *sh_raw, *sh_tsum, *sh_tmax, *sh_winx, *sh_winc;
-    int32_t* sh_flag;        // [0] a window left the halo ON THIS RANK, [1] / [2] widest reach left / right of the own tiles (in tiles),
-                             // [3] max of [0] over all ranks (ncclAllReduce after the time loop): what the fallback decision reads
-    int32_t sh_stats[4];     // host copy of sh_flag after the last native series
-    int sh_margin, sh_rows, sh_path;   // sh_path: path of the last native series (1 fixed halo, 2 exact)
-    int sh_check;            // 1 while the driver's fixed-halo path launches a step: the kernel verifies its source tiles
-    long sh_exchanged;       // tiles received from other ranks during the last native series
-    hipStream_t stream;
-    hipEvent_t ev0, ev1;
-    float last_ms;
+    // this rank's tile sums / maxima, their gathered forms; exact-path window buffers
+    double *sh_x[2], *sh_c[2], *sh_loc, *sh_tsum, *sh_tmax, *sh_winx, *sh_winc;
+    int sh_path;             // path of the last native series (1 fixed halo, 2 exact)
     // device state; [2] = ping-pong (step t reads cur, writes cur ^ 1)
     double* x[2];
     double* cdf[2];          // integer-valued doubles (< 2^53)
     double* tsum[2];
     double* tmax[2];
-    double *logw, *ybuf, *zbuf, *per_step, *scratchR;
+    double *logw, *scratchR;
     double *exp_part, *exp_out;  // expectations: [R][Bs][4] per-tile numerators; [5][R] per-filter values + [5] means over filters
     double* wscratch;            // [Npad] weights of one filter (host-side functionals), allocated on first use
     double *gam, *pgam, *gtot;   // Gamma tables of the multinomial resampler, gcap time rows
     uint32_t* anc;
-    uint32_t* keybuf;        // [2] Philox key = seed (lo, hi)
     FilterScalars* scal;
     ModelConst* mc;
     int cur;                 // buffer index holding the latest step's output
-    int ycap, tcap, gcap;
     // graph cache
     hipGraphExec_t gexec;
     int g_T, g_has_z, g_debug, g_logw, g_nt;
     std::vector<ModelConst> h_mc;
-    std::string err;
 };
-
-static int fail(ssme_pf_handle h, int code, const char* what, hipError_t e) {
-    if (h) { h->err = std::string(what) + ": " + hipGetErrorString(e); }
-    return code;
-}
-#define HIPCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail(h, SSME_ERR_HIP, #call, e_); } while (0)
 
 // Wait for a stream with the latency of a poll: hipStreamSynchronize spins only briefly and then sleeps on an interrupt,
 // which adds ~200 us to a filter() call whose kernels take longer than that window (measured: 512 filters x 2^14
@@ -132,9 +103,6 @@ static void round_out(const ssme_pf_handle h, double* p, size_t n) {
     if (h->cfg.dtype == SSME_F32 && p) for (size_t i = 0; i < n; ++i) p[i] = f32r(p[i]);
 }
 
-static int next_pow2(int n) { int p = 1; while (p < n) p <<= 1; return p; }
-static int ceil_log2(int n) { int k = 0; while ((1ll << k) < n) ++k; return k; }
-
 // Derived constants; operation order mirrors oracle/ssme_oracle.cpp derive().
 static ModelConst derive(int model, const double* th) {
     ModelConst c{};
@@ -166,7 +134,6 @@ static ModelConst derive(int model, const double* th) {
     return c;
 }
 
-constexpr int kStepGammaChunk = 64;
 // state / observation dimension of a model: 1 for the built-in models, dim_x / dim_y of a compiled-in user model
 static void dims_of(int model, int* dx, int* dy) {
     *dx = 1; *dy = 1;
@@ -429,52 +396,35 @@ static void enqueue_series_small(ssme_pf_handle h, int T, bool has_z) {
     h->cur = 1;
 }
 
+static void drop_graph(ssme_pf_handle h) {
+    if (h->gexec) { hipGraphExecDestroy(h->gexec); h->gexec = nullptr; }
+}
+
 // Gamma tables of the multinomial resampler for T time rows (nothing else moves: the step API grows them on its own)
 static int ensure_gamma_capacity(ssme_pf_handle h, int T) {
     if (h->cfg.resampler == SSME_RESAMP_MULTINOMIAL && T > h->gcap) {
-        if (h->gam) hipFree(h->gam);
-        if (h->pgam) hipFree(h->pgam);
-        if (h->gtot) hipFree(h->gtot);
-        h->gam = h->pgam = h->gtot = nullptr;
-        HIPCHK(hipMalloc(&h->gam, sizeof(double) * (size_t)T * h->R * h->B));
-        HIPCHK(hipMalloc(&h->pgam, sizeof(double) * (size_t)T * h->R * h->B));
-        HIPCHK(hipMalloc(&h->gtot, sizeof(double) * (size_t)T * h->R));
+        HIPCHK(own_alloc(h, h->gam, sizeof(double) * (size_t)T * h->R * h->B));
+        HIPCHK(own_alloc(h, h->pgam, sizeof(double) * (size_t)T * h->R * h->B));
+        HIPCHK(own_alloc(h, h->gtot, sizeof(double) * (size_t)T * h->R));
         h->gcap = T;
-        if (h->gexec) { hipGraphExecDestroy(h->gexec); h->gexec = nullptr; }
+        drop_graph(h);
     }
     return SSME_OK;
 }
 
 static int ensure_series_capacity(ssme_pf_handle h, int T) {
-    if (T > h->ycap) {
-        if (h->ybuf) hipFree(h->ybuf);
-        if (h->zbuf) hipFree(h->zbuf);
-        h->ybuf = h->zbuf = nullptr;
-        HIPCHK(hipMalloc(&h->ybuf, sizeof(double) * T * h->dy));
-        HIPCHK(hipMalloc(&h->zbuf, sizeof(double) * T));
-        h->ycap = T;
-        if (h->gexec) { hipGraphExecDestroy(h->gexec); h->gexec = nullptr; }
-    }
-    int rcg = ensure_gamma_capacity(h, T);
-    if (rcg != SSME_OK) return rcg;
-    if (T > h->tcap) {
-        if (h->per_step) hipFree(h->per_step);
-        if (h->small_ms) hipFree(h->small_ms);
-        h->per_step = h->small_ms = nullptr;
-        HIPCHK(hipMalloc(&h->per_step, sizeof(double) * (size_t)T * h->R));
-        if (h->B == 1) HIPCHK(hipMalloc(&h->small_ms, sizeof(double) * (size_t)T * h->R * 2));
-        h->tcap = T;
-        if (h->gexec) { hipGraphExecDestroy(h->gexec); h->gexec = nullptr; }
-    }
+    const bool grow_small = T > h->tcap && h->B == 1;
+    bool moved = false;
+    int rc = ensure_series_buffers(h, T, h->dy, &moved);
+    if (rc == SSME_OK) rc = ensure_gamma_capacity(h, T);
+    if (rc != SSME_OK) return rc;
+    if (grow_small) HIPCHK(own_alloc(h, h->small_ms, sizeof(double) * (size_t)T * h->R * 2));
+    if (moved) drop_graph(h);
     return SSME_OK;
 }
 
 static int ensure_logw(ssme_pf_handle h) {
-    if (logw_needed(h) && !h->logw) {
-        const size_t np = (size_t)h->R * h->Npad;
-        HIPCHK(hipMalloc(&h->logw, sizeof(double) * np));
-        HIPCHK(hipMemset(h->logw, 0, sizeof(double) * np));
-    }
+    if (logw_needed(h) && !h->logw) HIPCHK(own_alloc(h, h->logw, sizeof(double) * (size_t)h->R * h->Npad, Mem::zeroed));
     return SSME_OK;
 }
 
@@ -514,7 +464,7 @@ const char* ssme_pf_strerror(int s) {
         default: return "unknown status";
     }
 }
-const char* ssme_pf_last_error(ssme_pf_handle h) { return h ? h->err.c_str() : ""; }
+const char* ssme_pf_last_error(ssme_pf_handle h) { return last_error(h); }
 
 static int create_impl(const ssme_pf_config* cfg, int shard_rank, int shard_world, ssme_pf_handle* out) {
     if (!cfg || !out) return SSME_ERR_INVALID_ARG;
@@ -535,25 +485,11 @@ static int create_impl(const ssme_pf_config* cfg, int shard_rank, int shard_worl
     if (cfg->n_filters_total < 0 || (cfg->n_filters_total > 0 && cfg->n_filters_total < cfg->n_filters)) return SSME_ERR_INVALID_ARG;
     const int tile = shard_world > 0 ? kTile : (cfg->tile_particles ? cfg->tile_particles
                                                 : default_tile(cfg->n_particles, cfg->n_filters_total > 0 ? cfg->n_filters_total : cfg->n_filters));
-    const int B = (cfg->n_particles + tile - 1) / tile;
-    if (B > kMaxTilesSplit) return SSME_ERR_UNSUPPORTED;   // at most 16384 tiles per filter (N <= 2^25 with 2048-particle tiles)
     ssme_pf_handle h = new (std::nothrow) ssme_pf_s();
     if (!h) return SSME_ERR_INVALID_ARG;
+    set_layout(h, cfg->n_particles, cfg->n_filters, tile, shard_rank, shard_world);
+    if (h->B > kMaxTilesSplit) { delete h; return SSME_ERR_UNSUPPORTED; }   // at most 16384 tiles per filter (N <= 2^25 with 2048-particle tiles)
     h->cfg = *cfg;
-    h->shard_rank = shard_rank; h->shard_world = shard_world;
-    if (shard_world > 0) {
-        h->sh_Bl = (B + shard_world - 1) / shard_world;
-        h->sh_Bown = B - shard_rank * h->sh_Bl < h->sh_Bl ? B - shard_rank * h->sh_Bl : h->sh_Bl;
-    }
-    h->tile = tile;
-    h->N = cfg->n_particles; h->R = cfg->n_filters; h->B = B; h->Npad = B * tile;
-    h->Bs = (B + 1) & ~1; h->Bpow2 = next_pow2(B);
-    h->rshift = 52 - ceil_log2(h->Npad);
-    h->split_l2 = B > kSplitLevel2Above ? 1 : 0;
-    // in-kernel level-2 keeps T' and A/A' of all tiles in LDS (possible up to 2048 tiles, whichever policy is the default)
-    h->lds_bytes = sizeof(double) * (2 * (size_t)(B > kMaxTilesPerFilter ? 2 : (h->Bpow2 < 2 ? 2 : h->Bpow2)) + (size_t)kStageTiles * tile);
-    h->lds_bytes_big = sizeof(double) * (4 + (size_t)kStageTiles * tile);
-    h->lds_bytes_plan = sizeof(double) * (size_t)(h->Bpow2 < 2 ? 2 : h->Bpow2);
     h->graph_mode = 1;
     h->small_series = 1;
     dims_of(cfg->model, &h->dx, &h->dy);
@@ -566,21 +502,15 @@ static int create_impl(const ssme_pf_config* cfg, int shard_rank, int shard_worl
         h->num_cus = (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, cfg->device) == hipSuccess && cus > 0) ? cus : 256;
     }
     int rc = [&]() -> int {
-        HIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-        h->own_stream = h->stream;
-        HIPCHK(hipEventCreate(&h->ev0));
-        HIPCHK(hipEventCreate(&h->ev1));
+        int rc2 = create_stream(h);
+        if (rc2 != SSME_OK) return rc2;
         const size_t np = (size_t)h->R * h->Npad, nb = (size_t)h->R * h->Bs;
-        if (h->shard_world > 0) HIPCHK(hipMalloc(&h->plan_dev, sizeof(int32_t) * 2 * h->shard_world));
+        if (h->shard_world > 0) HIPCHK(own_alloc(h, h->plan_dev, sizeof(int32_t) * 2 * h->shard_world));
         for (int i = 0; i < 2 && h->shard_world == 0; ++i) {   // a sharded handle works on the caller's buffers
-            HIPCHK(hipMalloc(&h->x[i], sizeof(double) * np * h->dx));          // dim_x planes of [R][Npad]
-            HIPCHK(hipMalloc(&h->cdf[i], sizeof(double) * np));
-            HIPCHK(hipMalloc(&h->tsum[i], sizeof(double) * nb));
-            HIPCHK(hipMalloc(&h->tmax[i], sizeof(double) * nb));
-            HIPCHK(hipMemset(h->x[i], 0, sizeof(double) * np * h->dx));
-            HIPCHK(hipMemset(h->cdf[i], 0, sizeof(double) * np));
-            HIPCHK(hipMemset(h->tsum[i], 0, sizeof(double) * nb));
-            HIPCHK(hipMemset(h->tmax[i], 0, sizeof(double) * nb));
+            HIPCHK(own_alloc(h, h->x[i], sizeof(double) * np * h->dx, Mem::zeroed));          // dim_x planes of [R][Npad]
+            HIPCHK(own_alloc(h, h->cdf[i], sizeof(double) * np, Mem::zeroed));
+            HIPCHK(own_alloc(h, h->tsum[i], sizeof(double) * nb, Mem::zeroed));
+            HIPCHK(own_alloc(h, h->tmax[i], sizeof(double) * nb, Mem::zeroed));
         }
         grant_step_lds(h);
         HIPCHK(hipGetLastError());
@@ -588,35 +518,25 @@ static int create_impl(const ssme_pf_config* cfg, int shard_rank, int shard_worl
                                    (int)h->lds_bytes_plan));
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_l2_ranges), hipFuncAttributeMaxDynamicSharedMemorySize,
                                    (int)h->lds_bytes_plan));
-        HIPCHK(hipMalloc(&h->l2_work, sizeof(double) * ((size_t)h->R * h->Bs + (size_t)h->R * kL2Scratch + 32)));
-        HIPCHK(hipMemset(h->l2_work, 0, sizeof(double) * ((size_t)h->R * h->Bs + (size_t)h->R * kL2Scratch + 32)));
-        HIPCHK(hipMalloc(&h->l2_T, sizeof(double) * (size_t)h->R * h->Bs));
-        HIPCHK(hipMalloc(&h->l2_R, sizeof(double) * (size_t)h->R * h->Bs));
-        HIPCHK(hipMalloc(&h->l2_lo, sizeof(int32_t) * (size_t)h->R * h->Bs));
-        HIPCHK(hipMalloc(&h->l2_hi, sizeof(int32_t) * (size_t)h->R * h->Bs));
-        HIPCHK(hipMemset(h->l2_lo, 0, sizeof(int32_t) * (size_t)h->R * h->Bs));
-        HIPCHK(hipMemset(h->l2_hi, 0, sizeof(int32_t) * (size_t)h->R * h->Bs));
-        HIPCHK(hipMalloc(&h->scal, sizeof(FilterScalars) * h->R));
-        HIPCHK(hipMalloc(&h->mc, sizeof(ModelConst) * h->R));
-        HIPCHK(hipMalloc(&h->scratchR, sizeof(double) * h->R));
-        HIPCHK(hipMalloc(&h->exp_part, sizeof(double) * (size_t)h->R * h->Bs * kMaxFunctionals));
-        HIPCHK(hipMalloc(&h->exp_out, sizeof(double) * ((size_t)(kMaxFunctionals + 1) * h->R + kMaxFunctionals + 1)));
-        HIPCHK(hipMalloc(&h->keybuf, sizeof(uint32_t) * 2));
-        HIPCHK(hipMalloc(&h->yz_step, sizeof(double) * 2));
-        HIPCHK(hipMalloc(&h->ticket, sizeof(int32_t) * h->R));
-        HIPCHK(hipMalloc(&h->l2_ticket, sizeof(int32_t) * h->R));
-        HIPCHK(hipMemsetAsync(h->l2_ticket, 0, sizeof(int32_t) * h->R, h->stream));
-        HIPCHK(hipMemsetAsync(h->ticket, 0, sizeof(int32_t) * h->R, h->stream));
-        HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&h->pin), sizeof(double) * (2 + (size_t)h->R + 64 + 8), hipHostMallocMapped));   // + 128 ints for the shard plan + 8 swarm aggregates
+        HIPCHK(own_alloc(h, h->l2_work, sizeof(double) * (nb + (size_t)h->R * kL2Scratch + 32), Mem::zeroed));
+        HIPCHK(own_alloc(h, h->l2_T, sizeof(double) * nb));
+        HIPCHK(own_alloc(h, h->l2_R, sizeof(double) * nb));
+        HIPCHK(own_alloc(h, h->l2_lo, sizeof(int32_t) * nb, Mem::zeroed));
+        HIPCHK(own_alloc(h, h->l2_hi, sizeof(int32_t) * nb, Mem::zeroed));
+        HIPCHK(own_alloc(h, h->scal, sizeof(FilterScalars) * h->R));
+        HIPCHK(own_alloc(h, h->mc, sizeof(ModelConst) * h->R));
+        HIPCHK(own_alloc(h, h->scratchR, sizeof(double) * h->R));
+        HIPCHK(own_alloc(h, h->exp_part, sizeof(double) * nb * kMaxFunctionals));
+        HIPCHK(own_alloc(h, h->exp_out, sizeof(double) * ((size_t)(kMaxFunctionals + 1) * h->R + kMaxFunctionals + 1)));
+        HIPCHK(own_alloc(h, h->keybuf, sizeof(uint32_t) * 2));
+        HIPCHK(own_alloc(h, h->yz_step, sizeof(double) * 2));
+        HIPCHK(own_alloc(h, h->ticket, sizeof(int32_t) * h->R, Mem::zeroed));
+        HIPCHK(own_alloc(h, h->l2_ticket, sizeof(int32_t) * h->R, Mem::zeroed));
+        HIPCHK(own_alloc(h, h->pin, sizeof(double) * (2 + (size_t)h->R + 64 + 8), Mem::pinned));   // + 128 ints for the shard plan + 8 swarm aggregates
         HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->pin_dev), h->pin, 0));
-        int rc2 = upload_key(h);
+        rc2 = upload_key(h);
         if (rc2 != SSME_OK) return rc2;
-        if (h->shard_world > 0) {
-            rc2 = ensure_logw(h);                // resamp_sched > 1: the carried log-weights of this rank's particles (local offsets)
-            if (rc2 != SSME_OK) return rc2;
-            return ensure_series_capacity(h, 1);
-        }
-        rc2 = ensure_logw(h);
+        rc2 = ensure_logw(h);                    // sharded, resamp_sched > 1: the carried log-weights of this rank's particles (local offsets)
         if (rc2 != SSME_OK) return rc2;
         return ensure_series_capacity(h, 1);
     }();
@@ -628,17 +548,8 @@ static int create_impl(const ssme_pf_config* cfg, int shard_rank, int shard_worl
 int ssme_pf_destroy(ssme_pf_handle h) {
     if (!h) return SSME_ERR_INVALID_ARG;
     hipSetDevice(h->cfg.device);
-    if (h->stream) hipStreamSynchronize(h->stream);
-    h->stream = h->own_stream;
-    if (h->gexec) hipGraphExecDestroy(h->gexec);
-    void* bufs[] = {h->x[0], h->x[1], h->cdf[0], h->cdf[1], h->tsum[0], h->tsum[1], h->tmax[0], h->tmax[1], h->logw,
-                    h->ybuf, h->zbuf, h->per_step, h->scratchR, h->anc, h->scal, h->mc, h->gam, h->pgam, h->gtot, h->keybuf, h->plan_dev, h->l2_T, h->l2_R, h->l2_work, h->l2_lo, h->l2_hi, h->yz_step, h->ticket, h->l2_ticket, h->small_ms, h->exp_part, h->exp_out, h->wscratch,
-                    h->sh_x[0], h->sh_x[1], h->sh_c[0], h->sh_c[1], h->sh_loc, h->sh_raw, h->sh_tsum, h->sh_tmax, h->sh_winx, h->sh_winc, h->sh_flag};
-    for (void* p : bufs) if (p) hipFree(p);
-    if (h->pin) hipHostFree(h->pin);
-    if (h->ev0) hipEventDestroy(h->ev0);
-    if (h->ev1) hipEventDestroy(h->ev1);
-    if (h->stream) hipStreamDestroy(h->stream);
+    if (h->gexec) { hipStreamSynchronize(h->stream); hipGraphExecDestroy(h->gexec); }
+    release_core(h);
     delete h;
     return SSME_OK;
 }
@@ -673,29 +584,17 @@ int ssme_pf_shard_create(const ssme_pf_config* cfg, int32_t rank, int32_t world,
     if (world < 1 || world > 64 || rank < 0 || rank >= world) return SSME_ERR_INVALID_ARG;
     if (cfg->n_filters != 1 || cfg->resamp_sched < 1) return SSME_ERR_UNSUPPORTED;
     if (cfg->n_particles < 1) return SSME_ERR_UNSUPPORTED;
-    {
-        // ceil(B / world) tiles per rank; the last rank takes what is left (fewer tiles, a ragged last tile) and must own at least one
-        const int B = (cfg->n_particles + kTile - 1) / kTile, Bl = (B + world - 1) / world;
-        if ((world - 1) * Bl >= B) return SSME_ERR_UNSUPPORTED;
-    }
+    Layout l;
+    if (!set_layout(&l, cfg->n_particles, 1, kTile, rank, world)) return SSME_ERR_UNSUPPORTED;   // every rank must own a tile
     return create_impl(cfg, rank, world, out);
 }
 
-int ssme_pf_shard_layout(ssme_pf_handle h, int32_t* out4) {
-    if (!h || !out4) return SSME_ERR_INVALID_ARG;
-    if (h->shard_world < 1) return SSME_ERR_STATE;
-    const long first = (long)h->shard_rank * h->sh_Bl * kTile, own = (long)h->sh_Bown * kTile;
-    out4[0] = h->B; out4[1] = h->sh_Bl; out4[2] = h->sh_Bown; out4[3] = (int32_t)(h->N - first < own ? h->N - first : own);
-    return SSME_OK;
-}
+int ssme_pf_shard_layout(ssme_pf_handle h, int32_t* out4) { return shard_layout(h, out4); }
 
 int ssme_pf_set_stream(ssme_pf_handle h, void* hip_stream) {
-    if (!h) return SSME_ERR_INVALID_ARG;
-    HIPCHK(hipSetDevice(h->cfg.device));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    h->stream = hip_stream ? reinterpret_cast<hipStream_t>(hip_stream) : h->own_stream;
-    if (h->gexec) { hipGraphExecDestroy(h->gexec); h->gexec = nullptr; }
-    return SSME_OK;
+    const int rc = set_stream(h, hip_stream);
+    if (rc == SSME_OK) drop_graph(h);
+    return rc;
 }
 
 int ssme_pf_shard_prepare(ssme_pf_handle h, const double* y, const double* z, int32_t T) {
@@ -809,11 +708,9 @@ int ssme_pf_shard_finalize(ssme_pf_handle h, int32_t t, const double* tsum_all, 
 }
 
 // ---- C++ driver of the sharded filter over RCCL (shard_driver.h) ----------------------------------------------------------
-#define NCCLCHK(call) do { ncclResult_t r_ = (call); if (r_ != ncclSuccess) { \
-    if (h) h->err = std::string(#call) + ": " + (rccl().GetErrorString ? rccl().GetErrorString(r_) : "RCCL error"); return SSME_ERR_HIP; } } while (0)
 
 int ssme_shard_comm_get_unique_id(void* id128) {
-    ssme_pf_handle h = nullptr;
+    HandleCore* h = nullptr;
     if (!id128) return SSME_ERR_INVALID_ARG;
     if (!rccl().ok) return SSME_ERR_UNSUPPORTED;
     static_assert(sizeof(ncclUniqueId) == 128, "ncclUniqueId is 128 bytes");
@@ -821,7 +718,7 @@ int ssme_shard_comm_get_unique_id(void* id128) {
     return SSME_OK;
 }
 int ssme_shard_comm_init(const void* id128, int32_t rank, int32_t world, int32_t device, void** comm_out) {
-    ssme_pf_handle h = nullptr;
+    HandleCore* h = nullptr;
     if (!id128 || !comm_out || world < 1 || rank < 0 || rank >= world) return SSME_ERR_INVALID_ARG;
     if (!rccl().ok) return SSME_ERR_UNSUPPORTED;
     if (hipSetDevice(device) != hipSuccess) return SSME_ERR_HIP;
@@ -833,7 +730,7 @@ int ssme_shard_comm_init(const void* id128, int32_t rank, int32_t world, int32_t
     return SSME_OK;
 }
 int ssme_shard_comm_destroy(void* comm) {
-    ssme_pf_handle h = nullptr;
+    HandleCore* h = nullptr;
     if (!comm) return SSME_ERR_INVALID_ARG;
     if (!rccl().ok) return SSME_ERR_UNSUPPORTED;
     NCCLCHK(rccl().CommDestroy(reinterpret_cast<ncclComm_t>(comm)));
@@ -841,55 +738,38 @@ int ssme_shard_comm_destroy(void* comm) {
 }
 
 static int shard_alloc(ssme_pf_handle h, bool exact) {
-    const int world = h->shard_world, Bl = h->sh_Bl;
+    const int Bl = h->sh_Bl;
     if (!h->sh_x[0]) {
-        // halo margin: a rank's resampling window normally reaches a tile or two into its neighbours (the cumulative tile
-        // weights wander like sqrt(tiles) around the uniform split); 4 tiles or 1/64 of the share, never more than the share
-        int m = Bl / 64 > 4 ? Bl / 64 : 4;
-        if (m > Bl) m = Bl;
-        if (world == 1) m = 0;
-        h->sh_margin = m; h->sh_rows = Bl + 2 * m;
+        h->sh_margin = halo_margin(Bl, h->shard_world); h->sh_rows = Bl + 2 * h->sh_margin;
         const size_t nb = sizeof(double) * (size_t)h->sh_rows * kTile;
         for (int i = 0; i < 2; ++i) {
-            HIPCHK(hipMalloc(&h->sh_x[i], nb)); HIPCHK(hipMemset(h->sh_x[i], 0, nb));
-            HIPCHK(hipMalloc(&h->sh_c[i], nb)); HIPCHK(hipMemset(h->sh_c[i], 0, nb));
+            HIPCHK(own_alloc(h, h->sh_x[i], nb, Mem::zeroed));
+            HIPCHK(own_alloc(h, h->sh_c[i], nb, Mem::zeroed));
         }
-        HIPCHK(hipMalloc(&h->sh_loc, sizeof(double) * 2 * Bl));
-        const size_t nall = (size_t)world * Bl > (size_t)h->Bs ? (size_t)world * Bl : (size_t)h->Bs;   // gathered: world x Bl entries, the first B are tiles
-        HIPCHK(hipMalloc(&h->sh_raw, sizeof(double) * 2 * nall));
-        HIPCHK(hipMalloc(&h->sh_tsum, sizeof(double) * nall));
-        HIPCHK(hipMalloc(&h->sh_tmax, sizeof(double) * nall));
-        HIPCHK(hipMemset(h->sh_loc, 0, sizeof(double) * 2 * Bl));
-        HIPCHK(hipMalloc(&h->sh_flag, sizeof(int32_t) * 4));
+        HIPCHK(own_alloc(h, h->sh_loc, sizeof(double) * 2 * Bl, Mem::zeroed));
+        HIPCHK(own_alloc(h, h->sh_tsum, sizeof(double) * gathered_len(h)));
+        HIPCHK(own_alloc(h, h->sh_tmax, sizeof(double) * gathered_len(h)));
+        HIPCHK(own_alloc(h, h->sh_flag, sizeof(int32_t) * 4));
     }
     if (exact && !h->sh_winx) {
-        HIPCHK(hipMalloc(&h->sh_winx, sizeof(double) * (size_t)h->B * kTile));
-        HIPCHK(hipMalloc(&h->sh_winc, sizeof(double) * (size_t)h->B * kTile));
+        HIPCHK(own_alloc(h, h->sh_winx, sizeof(double) * (size_t)h->B * kTile));
+        HIPCHK(own_alloc(h, h->sh_winc, sizeof(double) * (size_t)h->B * kTile));
     }
-    return SSME_OK;
-}
-
-// tile sums and tile maxima of all ranks, each straight into its final [B] array: two all-gathers in one group (one launch)
-static int shard_gather(ssme_pf_handle h, ncclComm_t comm) {
-    const int world = h->shard_world, Bl = h->sh_Bl;
-    (void)world;
-    NCCLCHK(rccl().GroupStart());
-    NCCLCHK(rccl().AllGather(h->sh_loc, h->sh_tsum, (size_t)Bl, ncclDouble, comm, h->stream));
-    NCCLCHK(rccl().AllGather(h->sh_loc + Bl, h->sh_tmax, (size_t)Bl, ncclDouble, comm, h->stream));
-    NCCLCHK(rccl().GroupEnd());
     return SSME_OK;
 }
 
 // One series on one path.  fast: fixed halo exchange, no host synchronisation inside the loop; exact: planned exchange.
 static int shard_series(ssme_pf_handle h, ncclComm_t comm, const double* y, const double* z, int T, bool fast, bool* overflow) {
-    const int world = h->shard_world, rank = h->shard_rank, Bl = h->sh_Bl, m = h->sh_margin, tile0 = rank * Bl;
+    const int rank = h->shard_rank, Bl = h->sh_Bl, m = h->sh_margin, tile0 = rank * Bl;
     const size_t TL = kTile;
     int rc = ssme_pf_shard_prepare(h, y, z, T);
     if (rc != SSME_OK) return rc;
     HIPCHK(hipMemsetAsync(h->sh_flag, 0, sizeof(int32_t) * 4, h->stream));
     h->sh_exchanged = 0;
     int cur = 0;
-    std::vector<int32_t> lo_hi(2 * (size_t)world);
+    std::vector<int32_t> lo_hi(2 * (size_t)h->shard_world);
+    // tile sums and tile maxima of all ranks, each straight into its final [B] array
+    auto gather = [&] { return all_gather(h, comm, {{h->sh_loc, h->sh_tsum, (size_t)Bl}, {h->sh_loc + Bl, h->sh_tmax, (size_t)Bl}}); };
     for (int t = 0; t < T; ++t) {
         double* xs = h->sh_x[cur]; double* cs = h->sh_c[cur];                     // sources: own rows + halos
         double* xo = h->sh_x[cur ^ 1] + (size_t)m * TL; double* co = h->sh_c[cur ^ 1] + (size_t)m * TL;   // outputs: the own rows of the other pair
@@ -897,7 +777,7 @@ static int shard_series(ssme_pf_handle h, ncclComm_t comm, const double* y, cons
         int win0 = 0;
         const bool resampled = t > 0 && (t % h->cfg.resamp_sched) == 0;     // the draw that closes step t - 1 runs now (lazily)
         if (t > 0) {
-            rc = shard_gather(h, comm);
+            rc = gather();
             if (rc != SSME_OK) return rc;
             if (!resampled) {
                 // no draw: every particle continues itself with its carried log-weight -- sources = this rank's own tiles, no exchange;
@@ -911,49 +791,14 @@ static int shard_series(ssme_pf_handle h, ncclComm_t comm, const double* y, cons
                     shard_plan_device(h, t, h->sh_tsum, h->sh_tmax, m, h->sh_flag);
                     HIPCHK(hipGetLastError());
                 }
-                if (world > 1) {
-                    // fixed halo: my first m tiles are the left neighbour's right halo, my last m tiles the right neighbour's left halo
-                    NCCLCHK(rccl().GroupStart());
-                    for (double* buf : {xs, cs}) {
-                        if (rank > 0) {
-                            NCCLCHK(rccl().Send(buf + (size_t)m * TL, (size_t)m * TL, ncclDouble, rank - 1, comm, h->stream));
-                            NCCLCHK(rccl().Recv(buf, (size_t)m * TL, ncclDouble, rank - 1, comm, h->stream));
-                        }
-                        if (rank + 1 < world) {
-                            NCCLCHK(rccl().Send(buf + (size_t)Bl * TL, (size_t)m * TL, ncclDouble, rank + 1, comm, h->stream));
-                            NCCLCHK(rccl().Recv(buf + (size_t)(m + Bl) * TL, (size_t)m * TL, ncclDouble, rank + 1, comm, h->stream));
-                        }
-                    }
-                    NCCLCHK(rccl().GroupEnd());
-                    h->sh_exchanged += (long)m * ((rank > 0) + (rank + 1 < world));
-                }
+                rc = halo_exchange(h, comm, {{xs, TL}, {cs, TL}});
+                if (rc != SSME_OK) return rc;
                 xw = xs; cw = cs; win0 = tile0 - m;                                   // row 0 of the halo buffer is global tile tile0 - m
             } else {
                 rc = ssme_pf_shard_plan(h, h->sh_tsum, h->sh_tmax, t, lo_hi.data());   // synchronises: the exact path is host-planned
+                if (rc == SSME_OK) rc = planned_exchange(h, comm, lo_hi.data(), {{xs + (size_t)m * TL, h->sh_winx, TL}, {cs + (size_t)m * TL, h->sh_winc, TL}});
                 if (rc != SSME_OK) return rc;
-                const int lo = lo_hi[2 * rank], hi = lo_hi[2 * rank + 1];
-                NCCLCHK(rccl().GroupStart());
-                for (int pass = 0; pass < 2; ++pass) {
-                    const double* own = (pass == 0 ? xs : cs) + (size_t)m * TL;          // my tiles tile0 .. tile0 + Bl - 1
-                    double* win = pass == 0 ? h->sh_winx : h->sh_winc;               // window: global tiles lo .. hi
-                    for (int p = 0; p < world; ++p) {
-                        // what I need from rank p: [lo, hi] x p's tiles
-                        const int a1 = lo > p * Bl ? lo : p * Bl, b1 = hi < (p + 1) * Bl - 1 ? hi : (p + 1) * Bl - 1;
-                        if (b1 >= a1) {
-                            if (p == rank) HIPCHK(hipMemcpyAsync(win + (size_t)(a1 - lo) * TL, own + (size_t)(a1 - tile0) * TL, sizeof(double) * (size_t)(b1 - a1 + 1) * TL,
-                                                                 hipMemcpyDeviceToDevice, h->stream));
-                            else { NCCLCHK(rccl().Recv(win + (size_t)(a1 - lo) * TL, (size_t)(b1 - a1 + 1) * TL, ncclDouble, p, comm, h->stream)); if (pass == 0) h->sh_exchanged += b1 - a1 + 1; }
-                        }
-                        // what rank p needs from me: [lo_p, hi_p] x my tiles
-                        if (p != rank) {
-                            const int lp = lo_hi[2 * p], hp = lo_hi[2 * p + 1];
-                            const int a2 = lp > tile0 ? lp : tile0, b2 = hp < tile0 + Bl - 1 ? hp : tile0 + Bl - 1;
-                            if (b2 >= a2) NCCLCHK(rccl().Send(own + (size_t)(a2 - tile0) * TL, (size_t)(b2 - a2 + 1) * TL, ncclDouble, p, comm, h->stream));
-                        }
-                    }
-                }
-                NCCLCHK(rccl().GroupEnd());
-                xw = h->sh_winx; cw = h->sh_winc; win0 = lo;
+                xw = h->sh_winx; cw = h->sh_winc; win0 = lo_hi[2 * rank];
             }
         }
         h->sh_check = (fast && t > 0) ? 1 : 0;                                         // the step kernel checks its sources against the halo
@@ -962,18 +807,15 @@ static int shard_series(ssme_pf_handle h, ncclComm_t comm, const double* y, cons
         if (rc != SSME_OK) return rc;
         cur ^= 1;
     }
-    rc = shard_gather(h, comm);
+    rc = gather();
     if (rc != SSME_OK) return rc;
     rc = ssme_pf_shard_finalize(h, T - 1, h->sh_tsum, h->sh_tmax);                    // synchronises
     if (rc != SSME_OK) return rc;
     h->cur = cur;                                                                     // sh_x[cur] holds the final particles
-    // The fallback decision must be the SAME on every rank: a rank's own flag only says what its own workgroups saw (up to
-    // 1024 tiles no plan kernel runs), so the flags are reduced over the ranks before anyone reads them.  One int, once per series.
     *overflow = false;
     if (fast) {           // (the exact path has no halo to leave; sh_stats keeps the record of the fixed-halo pass it may be the rerun of)
-        NCCLCHK(rccl().AllReduce(h->sh_flag, h->sh_flag + 3, 1, ncclInt32, ncclMax, comm, h->stream));
-        HIPCHK(hipMemcpyAsync(h->sh_stats, h->sh_flag, sizeof(h->sh_stats), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
+        rc = reduce_flags(h, comm);
+        if (rc != SSME_OK) return rc;
         *overflow = h->sh_stats[3] != 0;
     }
     return SSME_OK;
@@ -1014,9 +856,7 @@ int ssme_pf_shard_download(ssme_pf_handle h, double* x_local, uint64_t* cdf_loca
     if (!h) return SSME_ERR_INVALID_ARG;
     if (h->shard_world < 1 || !h->sh_x[0]) return SSME_ERR_STATE;
     HIPCHK(hipSetDevice(h->cfg.device));
-    // this rank's particles: Bl tiles, fewer on the last rank (and its last tile may be ragged)
-    const size_t first = (size_t)h->shard_rank * h->sh_Bl * kTile, off = (size_t)h->sh_margin * kTile;
-    const size_t n = (size_t)h->N - first < (size_t)h->sh_Bown * kTile ? (size_t)h->N - first : (size_t)h->sh_Bown * kTile;
+    const size_t off = (size_t)h->sh_margin * kTile, n = own_particles(h);
     if (x_local) HIPCHK(hipMemcpy(x_local, h->sh_x[h->cur] + off, sizeof(double) * n, hipMemcpyDeviceToHost));
     if (cdf_local) {
         HIPCHK(hipMemcpy(cdf_local, h->sh_c[h->cur] + off, sizeof(double) * n, hipMemcpyDeviceToHost));
@@ -1078,10 +918,7 @@ int ssme_pf_set_debug(ssme_pf_handle h, int32_t flags) {
     if (!h) return SSME_ERR_INVALID_ARG;
     if (h->shard_world > 0) return SSME_ERR_STATE;
     HIPCHK(hipSetDevice(h->cfg.device));
-    if ((flags & 1) && !h->anc) {
-        HIPCHK(hipMalloc(&h->anc, sizeof(uint32_t) * (size_t)h->R * h->Npad));
-        HIPCHK(hipMemset(h->anc, 0, sizeof(uint32_t) * (size_t)h->R * h->Npad));
-    }
+    if ((flags & 1) && !h->anc) HIPCHK(own_alloc(h, h->anc, sizeof(uint32_t) * (size_t)h->R * h->Npad, Mem::zeroed));
     h->debug_anc = (flags & 1) ? 1 : 0;
     h->keep_logw = (flags & 2) ? 1 : 0;
     {
@@ -1132,16 +969,7 @@ int ssme_pf_step(ssme_pf_handle h, const double* y, const double* z, double* out
     h->pin[0] = *y; h->pin[1] = z ? *z : 0.0;
     for (int d = 1; d < h->dy; ++d) h->y_step_v[d - 1] = y[d];
     if (h->cfg.dtype == SSME_F32) { h->pin[0] = f32r(h->pin[0]); h->pin[1] = f32r(h->pin[1]); }
-    // Gamma tables are drawn kStepGammaChunk time steps at a time (data independent), so that the two table launches are paid
-    // once per chunk and not once per filter() call
-    int gi = 0;
-    if (h->cfg.resampler == SSME_RESAMP_MULTINOMIAL) {
-        if (h->t < h->gamma_t0 || h->t >= h->gamma_t0 + h->gamma_rows) {
-            launch_gamma(h, h->t, kStepGammaChunk);
-            h->gamma_t0 = h->t; h->gamma_rows = kStepGammaChunk;
-        }
-        gi = h->t - h->gamma_t0;
-    }
+    const int gi = h->cfg.resampler == SSME_RESAMP_MULTINOMIAL ? step_gamma_row(h, launch_gamma) : 0;
     // out == NULL (the swarm classes: the aggregation that follows hands the data back): the step is only queued -- no result
     // slots, no wait; anything that reads the handle afterwards is ordered behind it on the stream
     const bool want = out != nullptr;
@@ -1213,36 +1041,25 @@ int ssme_pf_run_series(ssme_pf_handle h, const double* y, const double* z, int32
     }
     HIPCHK(hipGetLastError());
     h->t = T;
-    std::vector<FilterScalars> sc(h->R);
-    HIPCHK(hipMemcpyAsync(sc.data(), h->scal, sizeof(FilterScalars) * h->R, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
+    rc = read_loglik(h, loglik_out);
+    if (rc != SSME_OK) return rc;
     HIPCHK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
-    if (loglik_out) for (int r = 0; r < h->R; ++r) loglik_out[r] = sc[r].loglik;
     round_out(h, loglik_out, h->R);
     return SSME_OK;
 }
 
 int ssme_pf_get_per_step(ssme_pf_handle h, double* out, int32_t T) {
-    if (!h || !out || T < 1 || T > h->tcap) return SSME_ERR_INVALID_ARG;
-    HIPCHK(hipSetDevice(h->cfg.device));
-    // device layout is [R][tcap]; return [R][T]
-    for (int r = 0; r < h->R; ++r)
-        HIPCHK(hipMemcpyAsync(out + (size_t)r * T, h->per_step + (size_t)r * h->tcap, sizeof(double) * T,
-                              hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    round_out(h, out, (size_t)h->R * T);
-    return SSME_OK;
+    const int rc = read_per_step(h, out, T);
+    if (rc == SSME_OK) round_out(h, out, (size_t)h->R * T);
+    return rc;
 }
 
 int ssme_pf_get_loglik(ssme_pf_handle h, double* out) {
     if (!h || !out) return SSME_ERR_INVALID_ARG;
     HIPCHK(hipSetDevice(h->cfg.device));
-    std::vector<FilterScalars> sc(h->R);
-    HIPCHK(hipMemcpyAsync(sc.data(), h->scal, sizeof(FilterScalars) * h->R, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    for (int r = 0; r < h->R; ++r) out[r] = sc[r].loglik;
-    round_out(h, out, h->R);
-    return SSME_OK;
+    const int rc = read_loglik(h, out);
+    if (rc == SSME_OK) round_out(h, out, h->R);
+    return rc;
 }
 
 int ssme_pf_log_mean_exp(ssme_pf_handle h, double* out) {
@@ -1336,7 +1153,7 @@ int ssme_pf_download_weights(ssme_pf_handle h, int32_t f, double* x, double* w) 
     if (h->shard_world > 0) return SSME_ERR_STATE;
     if (h->t < 1) return SSME_ERR_STATE;
     HIPCHK(hipSetDevice(h->cfg.device));
-    if (!h->wscratch) HIPCHK(hipMalloc(&h->wscratch, sizeof(double) * (size_t)h->Npad));
+    if (!h->wscratch) HIPCHK(own_alloc(h, h->wscratch, sizeof(double) * (size_t)h->Npad));
     const size_t off = (size_t)f * h->Npad;
     hipLaunchKernelGGL(k_weights, dim3(h->B), dim3(kThreads), 0, h->stream, (const double*)(h->cdf[h->cur] + off),
                        (const double*)(h->tmax[h->cur] + (size_t)f * h->Bs), h->N, h->B, h->tile, h->wscratch);
@@ -1400,11 +1217,7 @@ int ssme_pf_get_layout(ssme_pf_handle h, int32_t* tile_particles, int32_t* n_til
     return SSME_OK;
 }
 
-int ssme_pf_last_elapsed_ms(ssme_pf_handle h, float* ms) {
-    if (!h || !ms) return SSME_ERR_INVALID_ARG;
-    *ms = h->last_ms;
-    return SSME_OK;
-}
+int ssme_pf_last_elapsed_ms(ssme_pf_handle h, float* ms) { return elapsed_ms(h, ms); }
 
 int ssme_pf_profile_series(ssme_pf_handle h, const double* y, const double* z, int32_t T, double* mean_us,
                            int32_t* launches) {
@@ -1635,56 +1448,31 @@ done:
 // =============================================================================================
 // Liu-West filter (LWFilterWithCovs, include/ssme/liu_west_filter.h:971-1159)
 // =============================================================================================
-struct ssme_lw_s {
+struct ssme_lw_s : HandleCore {
     ssme_lw_config cfg;
-    int N, R, Npad, B, Bs, Bpow2, rshift;
-    size_t lds_bytes;
-    int t, debug;
-    hipStream_t stream;
-    hipEvent_t ev0, ev1;
-    float last_ms;
+    int debug;
     double *xB, *thB, *xr, *thr, *lw1, *cdfA, *tsumA, *tmaxA, *cdfB, *tsumB, *tmaxB, *mom, *prop;
     double* momtot;                  // [R][16] moment totals of k_lw_mom_totals (filters of more than 1024 tiles)
     double* lwB;                     // carried second-stage log-weights (resamp_sched > 1 only)
     double* wscratch;                // [5][Npad] weights + untransformed parameters of one filter (host-side functionals)
     int form, rs;                    // 0 auxiliary form / 1 SISR form; resampling schedule m_rs
-    double *ybuf, *zbuf, *per_step, *scratch;
+    double* scratch;
     double *gamA, *pgamA, *gtotA, *gamB, *pgamB, *gtotB;
-    uint32_t *anc, *kidx, *keybuf;
+    uint32_t *anc, *kidx;
     uint32_t* ancbuf;        // unsharded handles: this step's resampling ancestors, stage 1 -> stage 2 (compose mode, lw_kernels.h)
-    int shard_rank, shard_world;     // particle-sharded filter (world = 0: unsharded)
     int fixed_trans;                 // the transform set is (logit, null, log, twice_fisher): stage kernels with it compiled in (lw_trans_kind)
     int th_plane_tiles;              // sharded: rows (tiles) per theta plane of the caller's OUTPUT buffers (default Bl)
-    int sh_Bl, sh_Bown;              // Bl = ceil(B / world) tiles per rank in every layout; the last rank owns B - (world-1) Bl >= 1 of them
-    hipStream_t own_stream;
-    int32_t* plan_dev;
     int32_t* plan_pin;               // pinned staging of the plan download
-    double *pin, *pin_dev;           // step API: device-mapped pinned buffer for the R log conditional likelihoods
     // C++ shard driver (ssme_lw_shard_run_series): halo buffers ([margin | own | margin] rows of 2048 doubles; theta rows of 8192),
-    // this rank's stage outputs for the gathers, the gathered arrays, flag
+    // this rank's stage outputs for the gathers, the gathered arrays
     double *sh_xB, *sh_thB, *sh_cdfB, *sh_xr, *sh_thr, *sh_g1, *sh_cdfA;
     double *sh_locB, *sh_locA, *sh_allB_s, *sh_allB_m, *sh_allA_s, *sh_allA_m, *sh_mom_all;
-    int32_t* sh_flag;        // [0] a window left the halo on this rank, [3] max of [0] over all ranks
-    int32_t sh_stats[4];
-    int sh_margin, sh_rows, sh_check;
-    long sh_exchanged;
-    int gamma_t0, gamma_rows;        // step API: the Gamma tables hold time indices gamma_t0 .. gamma_t0 + gamma_rows - 1
-    int split_l2;                    // level-2 of both draws by the split level-2 kernels (more than 1024 tiles)
     double *l2T[2], *l2R[2];         // [draw: 0 resampling (B), 1 k draw (A)][R][Bs]
     double* l2_work;                 // scratch of the multi-workgroup level-2 (the two draws run one after the other)
     int32_t *l2lo[2], *l2hi[2];
     FilterScalars* l2s[2];
-    size_t lds_bytes_big, lds_bytes_plan;
     LwScalars* scal;
-    int ycap, tcap, gcap;
-    std::string err;
 };
-
-static int lw_fail(ssme_lw_handle h, const char* what, hipError_t e) {
-    if (h) h->err = std::string(what) + ": " + hipGetErrorString(e);
-    return SSME_ERR_HIP;
-}
-#define LWCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return lw_fail(h, #call, e_); } while (0)
 
 static LwArgs lw_args(ssme_lw_handle h) {
     LwArgs a{};
@@ -1710,32 +1498,18 @@ static LwArgs lw_args(ssme_lw_handle h) {
 
 static int lw_ensure_gamma(ssme_lw_handle h, int T) {
     if (T > h->gcap) {
-        double** tabs[] = {&h->gamA, &h->pgamA, &h->gtotA, &h->gamB, &h->pgamB, &h->gtotB};
-        for (auto t : tabs) { if (*t) hipFree(*t); *t = nullptr; }
         const size_t nb = sizeof(double) * (size_t)T * h->R * h->B, nr = sizeof(double) * (size_t)T * h->R;
-        LWCHK(hipMalloc(&h->gamA, nb)); LWCHK(hipMalloc(&h->pgamA, nb)); LWCHK(hipMalloc(&h->gtotA, nr));
-        LWCHK(hipMalloc(&h->gamB, nb)); LWCHK(hipMalloc(&h->pgamB, nb)); LWCHK(hipMalloc(&h->gtotB, nr));
+        HIPCHK(own_alloc(h, h->gamA, nb)); HIPCHK(own_alloc(h, h->pgamA, nb)); HIPCHK(own_alloc(h, h->gtotA, nr));
+        HIPCHK(own_alloc(h, h->gamB, nb)); HIPCHK(own_alloc(h, h->pgamB, nb)); HIPCHK(own_alloc(h, h->gtotB, nr));
         h->gcap = T;
     }
     return SSME_OK;
 }
 
 static int lw_ensure_capacity(ssme_lw_handle h, int T) {
-    if (T > h->ycap) {
-        if (h->ybuf) hipFree(h->ybuf);
-        if (h->zbuf) hipFree(h->zbuf);
-        LWCHK(hipMalloc(&h->ybuf, sizeof(double) * T));
-        LWCHK(hipMalloc(&h->zbuf, sizeof(double) * T));
-        LWCHK(hipMemset(h->zbuf, 0, sizeof(double) * T));
-        h->ycap = T;
-    }
-    { int rcg = lw_ensure_gamma(h, T); if (rcg != SSME_OK) return rcg; }
-    if (T > h->tcap) {
-        if (h->per_step) hipFree(h->per_step);
-        LWCHK(hipMalloc(&h->per_step, sizeof(double) * (size_t)T * h->R));
-        h->tcap = T;
-    }
-    return SSME_OK;
+    bool moved = false;
+    const int rc = ensure_series_buffers(h, T, 1, &moved);
+    return rc == SSME_OK ? lw_ensure_gamma(h, T) : rc;
 }
 
 // Gamma tables of both draws for time indices t0 .. t0+nT-1 into rows 0 .. nT-1
@@ -1831,8 +1605,8 @@ static int lw_reset(ssme_lw_handle h) {
     std::vector<LwScalars> sc(h->R);
     const double logN = dlog((double)h->N);
     for (auto& s : sc) { std::memset(&s, 0, sizeof(s)); s.prev = logN; }
-    LWCHK(hipMemcpyAsync(h->scal, sc.data(), sizeof(LwScalars) * h->R, hipMemcpyHostToDevice, h->stream));
-    LWCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpyAsync(h->scal, sc.data(), sizeof(LwScalars) * h->R, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
     h->t = 0;
     h->gamma_rows = 0;
     return SSME_OK;
@@ -1843,20 +1617,7 @@ extern "C" {
 int ssme_lw_destroy(ssme_lw_handle h) {
     if (!h) return SSME_ERR_INVALID_ARG;
     hipSetDevice(h->cfg.device);
-    if (h->stream) hipStreamSynchronize(h->stream);
-    h->stream = h->own_stream;
-    void* bufs[] = {h->xB, h->thB, h->xr, h->thr, h->lw1, h->cdfA, h->tsumA, h->tmaxA, h->cdfB, h->tsumB, h->tmaxB, h->mom, h->prop, h->momtot,
-                    h->ybuf, h->zbuf, h->per_step, h->scratch, h->gamA, h->pgamA, h->gtotA, h->gamB, h->pgamB, h->gtotB, h->anc, h->ancbuf,
-                    h->kidx, h->scal, h->keybuf, h->plan_dev, h->l2_work, h->l2T[0], h->l2T[1], h->l2R[0], h->l2R[1], h->l2lo[0], h->l2lo[1],
-                    h->l2hi[0], h->l2hi[1], h->l2s[0], h->l2s[1], h->lwB, h->wscratch,
-                    h->sh_xB, h->sh_thB, h->sh_cdfB, h->sh_xr, h->sh_thr, h->sh_g1, h->sh_cdfA, h->sh_locB, h->sh_locA, h->sh_allB_s, h->sh_allB_m,
-                    h->sh_allA_s, h->sh_allA_m, h->sh_mom_all, h->sh_flag};
-    for (void* p : bufs) if (p) hipFree(p);
-    if (h->plan_pin) hipHostFree(h->plan_pin);
-    if (h->pin) hipHostFree(h->pin);
-    if (h->ev0) hipEventDestroy(h->ev0);
-    if (h->ev1) hipEventDestroy(h->ev1);
-    if (h->stream) hipStreamDestroy(h->stream);
+    release_core(h);
     delete h;
     return SSME_OK;
 }
@@ -1871,88 +1632,64 @@ static int lw_create_impl(const ssme_lw_config* cfg, int shard_rank, int shard_w
         if (cfg->transforms[d] < 0 || cfg->transforms[d] > 3) return SSME_ERR_INVALID_ARG;     // parameters.h:283 invalid_argument
         if (!(cfg->prior_lo[d] <= cfg->prior_hi[d])) return SSME_ERR_INVALID_ARG;
     }
-    const int B = (cfg->n_particles + kTile - 1) / kTile;
-    if (B > kMaxTilesSplit) return SSME_ERR_UNSUPPORTED;          // N <= 2^25
     ssme_lw_handle h = new (std::nothrow) ssme_lw_s();
     if (!h) return SSME_ERR_INVALID_ARG;
+    set_layout(h, cfg->n_particles, cfg->n_filters, kTile, shard_rank, shard_world);
+    if (h->B > kMaxTilesSplit) { delete h; return SSME_ERR_UNSUPPORTED; }          // N <= 2^25
     h->cfg = *cfg;
     h->form = cfg->form; h->rs = cfg->resamp_sched < 1 ? 1 : cfg->resamp_sched;
-    h->shard_rank = shard_rank; h->shard_world = shard_world;
     h->fixed_trans = (cfg->transforms[0] == TR_LOGIT && cfg->transforms[1] == TR_NULL && cfg->transforms[2] == TR_LOG && cfg->transforms[3] == TR_TWICE_FISHER) ? 1 : 0;
-    if (shard_world > 0) {
-        h->sh_Bl = (B + shard_world - 1) / shard_world;
-        h->sh_Bown = B - shard_rank * h->sh_Bl < h->sh_Bl ? B - shard_rank * h->sh_Bl : h->sh_Bl;
-    }
-    h->N = cfg->n_particles; h->R = cfg->n_filters; h->B = B; h->Npad = B * kTile;
-    h->Bs = (B + 1) & ~1; h->Bpow2 = next_pow2(B);
-    h->rshift = 52 - ceil_log2(h->Npad);
-    h->split_l2 = B > kSplitLevel2Above ? 1 : 0;
-    h->lds_bytes = sizeof(double) * (2 * (size_t)(B > kMaxTilesPerFilter ? 2 : (h->Bpow2 < 2 ? 2 : h->Bpow2)) + (size_t)kStageTiles * kTile);
-    h->lds_bytes_big = sizeof(double) * (4 + (size_t)kStageTiles * kTile);
-    h->lds_bytes_plan = sizeof(double) * (size_t)(h->Bpow2 < 2 ? 2 : h->Bpow2);
     if (hipSetDevice(cfg->device) != hipSuccess) { delete h; return SSME_ERR_HIP; }
     int rc = [&]() -> int {
-        LWCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-        h->own_stream = h->stream;
-        LWCHK(hipMalloc(&h->l2_work, sizeof(double) * ((size_t)h->R * h->Bs + (size_t)h->R * kL2Scratch)));
-        for (int d = 0; d < 2; ++d) {
-            LWCHK(hipMalloc(&h->l2T[d], sizeof(double) * (size_t)h->R * h->Bs));
-            LWCHK(hipMalloc(&h->l2R[d], sizeof(double) * (size_t)h->R * h->Bs));
-            LWCHK(hipMalloc(&h->l2lo[d], sizeof(int32_t) * (size_t)h->R * h->Bs));
-            LWCHK(hipMalloc(&h->l2hi[d], sizeof(int32_t) * (size_t)h->R * h->Bs));
-            LWCHK(hipMalloc(&h->l2s[d], sizeof(FilterScalars) * (size_t)h->R));
-            LWCHK(hipMemset(h->l2lo[d], 0, sizeof(int32_t) * (size_t)h->R * h->Bs));
-            LWCHK(hipMemset(h->l2hi[d], 0, sizeof(int32_t) * (size_t)h->R * h->Bs));
-            LWCHK(hipMemset(h->l2s[d], 0, sizeof(FilterScalars) * (size_t)h->R));
-        }
-        LWCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_level2_plan), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)h->lds_bytes_plan));
-        LWCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_l2_ranges), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)h->lds_bytes_plan));
-        LWCHK(hipEventCreate(&h->ev0));
-        LWCHK(hipEventCreate(&h->ev1));
+        int rc2 = create_stream(h);
+        if (rc2 != SSME_OK) return rc2;
         const size_t np = (size_t)h->R * h->Npad, nb = (size_t)h->R * h->Bs;
-        if (h->shard_world == 0) {               // a sharded handle works on the caller's buffers
-            double** big[] = {&h->xB, &h->xr, &h->lw1, &h->cdfA, &h->cdfB};
-            for (auto p : big) { LWCHK(hipMalloc(p, sizeof(double) * np)); LWCHK(hipMemset(*p, 0, sizeof(double) * np)); }
-            if (h->rs > 1) { LWCHK(hipMalloc(&h->lwB, sizeof(double) * np)); LWCHK(hipMemset(h->lwB, 0, sizeof(double) * np)); }
-            double** big4[] = {&h->thB, &h->thr};
-            for (auto p : big4) { LWCHK(hipMalloc(p, sizeof(double) * np * kDP)); LWCHK(hipMemset(*p, 0, sizeof(double) * np * kDP)); }
-            double** small[] = {&h->tsumA, &h->tmaxA, &h->tsumB, &h->tmaxB};
-            for (auto p : small) { LWCHK(hipMalloc(p, sizeof(double) * nb)); LWCHK(hipMemset(*p, 0, sizeof(double) * nb)); }
-            LWCHK(hipMalloc(&h->ancbuf, sizeof(uint32_t) * np));
-            LWCHK(hipMemset(h->ancbuf, 0, sizeof(uint32_t) * np));
-        } else {
-            LWCHK(hipMalloc(&h->plan_dev, sizeof(int32_t) * 2 * h->shard_world));
-            LWCHK(hipHostMalloc(reinterpret_cast<void**>(&h->plan_pin), sizeof(int32_t) * 2 * h->shard_world, hipHostMallocDefault));
-            h->th_plane_tiles = h->sh_Bl;
-            if (h->rs > 1) {                     // the carried second-stage log-weights of this rank's own particles (local offsets)
-                LWCHK(hipMalloc(&h->lwB, sizeof(double) * (size_t)h->sh_Bl * kTile));
-                LWCHK(hipMemset(h->lwB, 0, sizeof(double) * (size_t)h->sh_Bl * kTile));
-            }
+        HIPCHK(own_alloc(h, h->l2_work, sizeof(double) * (nb + (size_t)h->R * kL2Scratch + 32), Mem::zeroed));
+        for (int d = 0; d < 2; ++d) {
+            HIPCHK(own_alloc(h, h->l2T[d], sizeof(double) * nb));
+            HIPCHK(own_alloc(h, h->l2R[d], sizeof(double) * nb));
+            HIPCHK(own_alloc(h, h->l2lo[d], sizeof(int32_t) * nb, Mem::zeroed));
+            HIPCHK(own_alloc(h, h->l2hi[d], sizeof(int32_t) * nb, Mem::zeroed));
+            HIPCHK(own_alloc(h, h->l2s[d], sizeof(FilterScalars) * (size_t)h->R, Mem::zeroed));
         }
-        LWCHK(hipMalloc(&h->mom, sizeof(double) * (size_t)h->R * h->B * 16));
-        LWCHK(hipMalloc(&h->prop, sizeof(double) * (size_t)h->R * 16));
-        LWCHK(hipMalloc(&h->momtot, sizeof(double) * (size_t)h->R * 16));
-        LWCHK(hipMemset(h->prop, 0, sizeof(double) * (size_t)h->R * 16));
-        LWCHK(hipMalloc(&h->scal, sizeof(LwScalars) * h->R));
-        LWCHK(hipMalloc(&h->scratch, sizeof(double) * h->R * kLwNExp));
-        LWCHK(hipHostMalloc(reinterpret_cast<void**>(&h->pin), sizeof(double) * (size_t)h->R, hipHostMallocMapped));
-        LWCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->pin_dev), h->pin, 0));
-        LWCHK(hipMalloc(&h->keybuf, sizeof(uint32_t) * 2));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_level2_plan), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)h->lds_bytes_plan));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_l2_ranges), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)h->lds_bytes_plan));
+        if (h->shard_world == 0) {               // a sharded handle works on the caller's buffers
+            for (double** p : {&h->xB, &h->xr, &h->lw1, &h->cdfA, &h->cdfB}) HIPCHK(own_alloc(h, *p, sizeof(double) * np, Mem::zeroed));
+            if (h->rs > 1) HIPCHK(own_alloc(h, h->lwB, sizeof(double) * np, Mem::zeroed));
+            for (double** p : {&h->thB, &h->thr}) HIPCHK(own_alloc(h, *p, sizeof(double) * np * kDP, Mem::zeroed));
+            for (double** p : {&h->tsumA, &h->tmaxA, &h->tsumB, &h->tmaxB}) HIPCHK(own_alloc(h, *p, sizeof(double) * nb, Mem::zeroed));
+            HIPCHK(own_alloc(h, h->ancbuf, sizeof(uint32_t) * np, Mem::zeroed));
+        } else {
+            HIPCHK(own_alloc(h, h->plan_dev, sizeof(int32_t) * 2 * h->shard_world));
+            HIPCHK(own_alloc(h, h->plan_pin, sizeof(int32_t) * 2 * h->shard_world, Mem::pinned));
+            h->th_plane_tiles = h->sh_Bl;
+            if (h->rs > 1)                       // the carried second-stage log-weights of this rank's own particles (local offsets)
+                HIPCHK(own_alloc(h, h->lwB, sizeof(double) * (size_t)h->sh_Bl * kTile, Mem::zeroed));
+        }
+        HIPCHK(own_alloc(h, h->mom, sizeof(double) * (size_t)h->R * h->B * 16));
+        HIPCHK(own_alloc(h, h->prop, sizeof(double) * (size_t)h->R * 16, Mem::zeroed));
+        HIPCHK(own_alloc(h, h->momtot, sizeof(double) * (size_t)h->R * 16));
+        HIPCHK(own_alloc(h, h->scal, sizeof(LwScalars) * h->R));
+        HIPCHK(own_alloc(h, h->scratch, sizeof(double) * h->R * kLwNExp));
+        HIPCHK(own_alloc(h, h->pin, sizeof(double) * (size_t)h->R, Mem::pinned));
+        HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->pin_dev), h->pin, 0));
+        HIPCHK(own_alloc(h, h->keybuf, sizeof(uint32_t) * 2));
         {
             const uint32_t k[2] = {(uint32_t)h->cfg.seed, (uint32_t)(h->cfg.seed >> 32)};
-            LWCHK(hipMemcpy(h->keybuf, k, sizeof(k), hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(h->keybuf, k, sizeof(k), hipMemcpyHostToDevice));
         }
-        LWCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lw_stage1<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
-        LWCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lw_stage2<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
-        LWCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lw_stage1<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes_big));
-        LWCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lw_stage2<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes_big));
-        LWCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lw_stage1<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
-        LWCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lw_stage2<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
-        LWCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lw_stage1<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes_big));
-        LWCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lw_stage2<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes_big));
-        int rc2 = lw_ensure_capacity(h, 1);
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lw_stage1<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lw_stage2<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lw_stage1<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes_big));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lw_stage2<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes_big));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lw_stage1<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lw_stage2<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lw_stage1<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes_big));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lw_stage2<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes_big));
+        rc2 = lw_ensure_capacity(h, 1);
         if (rc2 != SSME_OK) return rc2;
         return lw_reset(h);
     }();
@@ -1972,29 +1709,14 @@ int ssme_lw_shard_create(const ssme_lw_config* cfg, int32_t rank, int32_t world,
     if (world < 1 || world > 64 || rank < 0 || rank >= world) return SSME_ERR_INVALID_ARG;
     if (cfg->n_filters != 1) return SSME_ERR_UNSUPPORTED;
     if (cfg->n_particles < 1) return SSME_ERR_UNSUPPORTED;
-    {
-        // ceil(B / world) tiles per rank; the last rank takes what is left and must own at least one tile (ssme_pf_shard_create)
-        const int B = (cfg->n_particles + kTile - 1) / kTile, Bl = (B + world - 1) / world;
-        if ((world - 1) * Bl >= B) return SSME_ERR_UNSUPPORTED;
-    }
+    Layout l;
+    if (!set_layout(&l, cfg->n_particles, 1, kTile, rank, world)) return SSME_ERR_UNSUPPORTED;   // every rank must own a tile
     return lw_create_impl(cfg, rank, world, out);
 }
 
-int ssme_lw_shard_layout(ssme_lw_handle h, int32_t* out4) {
-    if (!h || !out4) return SSME_ERR_INVALID_ARG;
-    if (h->shard_world < 1) return SSME_ERR_STATE;
-    const long first = (long)h->shard_rank * h->sh_Bl * kTile, own = (long)h->sh_Bown * kTile;
-    out4[0] = h->B; out4[1] = h->sh_Bl; out4[2] = h->sh_Bown; out4[3] = (int32_t)(h->N - first < own ? h->N - first : own);
-    return SSME_OK;
-}
+int ssme_lw_shard_layout(ssme_lw_handle h, int32_t* out4) { return shard_layout(h, out4); }
 
-int ssme_lw_set_stream(ssme_lw_handle h, void* hip_stream) {
-    if (!h) return SSME_ERR_INVALID_ARG;
-    LWCHK(hipSetDevice(h->cfg.device));
-    LWCHK(hipStreamSynchronize(h->stream));
-    h->stream = hip_stream ? reinterpret_cast<hipStream_t>(hip_stream) : h->own_stream;
-    return SSME_OK;
-}
+int ssme_lw_set_stream(ssme_lw_handle h, void* hip_stream) { return set_stream(h, hip_stream); }
 
 int ssme_lw_shard_set_plane_tiles(ssme_lw_handle h, int32_t tiles) {
     if (!h || tiles < 1) return SSME_ERR_INVALID_ARG;
@@ -2008,16 +1730,16 @@ int ssme_lw_shard_prepare(ssme_lw_handle h, const double* y, const double* z, in
     if (!h || !y) return SSME_ERR_INVALID_ARG;
     if (h->shard_world < 1) return SSME_ERR_STATE;
     if (T < 1) return SSME_ERR_LENGTH;
-    LWCHK(hipSetDevice(h->cfg.device));
+    HIPCHK(hipSetDevice(h->cfg.device));
     int rc = lw_ensure_capacity(h, T);
     if (rc != SSME_OK) return rc;
-    LWCHK(hipMemcpyAsync(h->ybuf, y, sizeof(double) * T, hipMemcpyHostToDevice, h->stream));
-    if (z) LWCHK(hipMemcpyAsync(h->zbuf, z, sizeof(double) * T, hipMemcpyHostToDevice, h->stream));
-    else LWCHK(hipMemsetAsync(h->zbuf, 0, sizeof(double) * T, h->stream));
+    HIPCHK(hipMemcpyAsync(h->ybuf, y, sizeof(double) * T, hipMemcpyHostToDevice, h->stream));
+    if (z) HIPCHK(hipMemcpyAsync(h->zbuf, z, sizeof(double) * T, hipMemcpyHostToDevice, h->stream));
+    else HIPCHK(hipMemsetAsync(h->zbuf, 0, sizeof(double) * T, h->stream));
     rc = lw_reset(h);
     if (rc != SSME_OK) return rc;
     lw_launch_gamma(h, 0, T);
-    LWCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     return SSME_OK;
 }
 
@@ -2035,11 +1757,11 @@ static LwArgs lw_shard_args(ssme_lw_handle h, int t) {
 int ssme_lw_shard_init(ssme_lw_handle h, double* xB, double* thB, double* cdfB, double* tsumB, double* tmaxB) {
     if (!h || !xB || !thB || !cdfB || !tsumB || !tmaxB) return SSME_ERR_INVALID_ARG;
     if (h->shard_world < 1) return SSME_ERR_STATE;
-    LWCHK(hipSetDevice(h->cfg.device));
+    HIPCHK(hipSetDevice(h->cfg.device));
     LwArgs a = lw_shard_args(h, 0);
     a.xB = xB; a.thB = thB; a.cdfB = cdfB; a.tsumB = tsumB; a.tmaxB = tmaxB;
     hipLaunchKernelGGL(k_lw_init, dim3(h->sh_Bown, 1), dim3(kLwNT), 0, h->stream, a);
-    LWCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     h->t = 1;
     return SSME_OK;
 }
@@ -2048,17 +1770,17 @@ int ssme_lw_shard_init(ssme_lw_handle h, double* xB, double* thB, double* cdfB, 
 int ssme_lw_shard_plan(ssme_lw_handle h, int32_t which, int32_t t, const double* tsum_all, const double* tmax_all, int32_t* lo_hi) {
     if (!h || !tsum_all || !tmax_all || !lo_hi || t < 1 || which < 0 || which > 1) return SSME_ERR_INVALID_ARG;
     if (h->shard_world < 1) return SSME_ERR_STATE;
-    LWCHK(hipSetDevice(h->cfg.device));
+    HIPCHK(hipSetDevice(h->cfg.device));
     if (h->split_l2) {
         lw_launch_plan(h, which, t, t, tsum_all, tmax_all, true);
-        LWCHK(hipGetLastError());
+        HIPCHK(hipGetLastError());
         const int Bl = h->sh_Bl;
         for (int d = 0; d < h->shard_world; ++d) {
             const size_t last = (size_t)(d + 1) * Bl - 1 < (size_t)h->B - 1 ? (size_t)(d + 1) * Bl - 1 : (size_t)h->B - 1;
-            LWCHK(hipMemcpyAsync(h->plan_pin + 2 * d, h->l2lo[which] + (size_t)d * Bl, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-            LWCHK(hipMemcpyAsync(h->plan_pin + 2 * d + 1, h->l2hi[which] + last, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(hipMemcpyAsync(h->plan_pin + 2 * d, h->l2lo[which] + (size_t)d * Bl, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(hipMemcpyAsync(h->plan_pin + 2 * d + 1, h->l2hi[which] + last, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
         }
-        LWCHK(wait_stream_low_latency(h->stream));
+        HIPCHK(wait_stream_low_latency(h->stream));
         for (int d = 0; d < 2 * h->shard_world; ++d) lo_hi[d] = h->plan_pin[d];
         return SSME_OK;
     }
@@ -2071,9 +1793,9 @@ int ssme_lw_shard_plan(ssme_lw_handle h, int32_t which, int32_t t, const double*
     a.keyp = h->keybuf; a.first_filter = h->cfg.first_filter_id;
     hipLaunchKernelGGL(k_shard_plan, dim3(1), dim3(512), sizeof(double) * (h->Bpow2 < 2 ? 2 : h->Bpow2), h->stream, a,
                        h->shard_world, h->sh_Bl, h->plan_dev);
-    LWCHK(hipGetLastError());
-    LWCHK(hipMemcpyAsync(h->plan_pin, h->plan_dev, sizeof(int32_t) * 2 * h->shard_world, hipMemcpyDeviceToHost, h->stream));
-    LWCHK(wait_stream_low_latency(h->stream));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h->plan_pin, h->plan_dev, sizeof(int32_t) * 2 * h->shard_world, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(wait_stream_low_latency(h->stream));
     for (int d = 0; d < 2 * h->shard_world; ++d) lo_hi[d] = h->plan_pin[d];
     return SSME_OK;
 }
@@ -2086,7 +1808,7 @@ int ssme_lw_shard_stage1(ssme_lw_handle h, int32_t t, int32_t win_tile0, int32_t
         return SSME_ERR_INVALID_ARG;
     if (h->shard_world < 1) return SSME_ERR_STATE;
     if (t >= h->tcap) return SSME_ERR_STATE;
-    LWCHK(hipSetDevice(h->cfg.device));
+    HIPCHK(hipSetDevice(h->cfg.device));
     LwArgs a = lw_shard_args(h, t);
     a.xB = const_cast<double*>(w_xB); a.thB = const_cast<double*>(w_thB); a.cdfB = const_cast<double*>(w_cdfB);
     a.tsumB = const_cast<double*>(tsumB_all); a.tmaxB = const_cast<double*>(tmaxB_all);
@@ -2095,14 +1817,14 @@ int ssme_lw_shard_stage1(ssme_lw_handle h, int32_t t, int32_t win_tile0, int32_t
     a.anc = anc;
     if (h->split_l2) lw_launch_stage1<true>(h, dim3(h->sh_Bown, 1), h->lds_bytes_big, a);
     else lw_launch_stage1<false>(h, dim3(h->sh_Bown, 1), h->lds_bytes, a);
-    LWCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     return SSME_OK;
 }
 
 int ssme_lw_shard_mid(ssme_lw_handle h, int32_t t, const double* tsumA_all, const double* tmaxA_all, const double* mom_all) {
     if (!h || t < 1 || !tsumA_all || !tmaxA_all || !mom_all) return SSME_ERR_INVALID_ARG;
     if (h->shard_world < 1) return SSME_ERR_STATE;
-    LWCHK(hipSetDevice(h->cfg.device));
+    HIPCHK(hipSetDevice(h->cfg.device));
     LwArgs a = lw_shard_args(h, t);
     a.tsumA = const_cast<double*>(tsumA_all); a.tmaxA = const_cast<double*>(tmaxA_all); a.mom = const_cast<double*>(mom_all);
     // split level-2: the plan of the k draw (ssme_lw_shard_plan(which = 1)) must precede this call -- it provides m and S
@@ -2116,7 +1838,7 @@ int ssme_lw_shard_mid(ssme_lw_handle h, int32_t t, const double* tsumA_all, cons
         hipLaunchKernelGGL(k_lw_mom_totals, dim3(kNMom, 1), dim3(64), 0, h->stream, a);
         hipLaunchKernelGGL(k_lw_mid<false>, dim3(1), dim3(kThreads), 0, h->stream, a);
     } else hipLaunchKernelGGL(k_lw_mid<false>, dim3(1), dim3(kThreads), 0, h->stream, a);
-    LWCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     return SSME_OK;
 }
 
@@ -2127,7 +1849,7 @@ int ssme_lw_shard_stage2(ssme_lw_handle h, int32_t t, int32_t win_tile0, int32_t
         !cdfB || !tsumB || !tmaxB)
         return SSME_ERR_INVALID_ARG;
     if (h->shard_world < 1) return SSME_ERR_STATE;
-    LWCHK(hipSetDevice(h->cfg.device));
+    HIPCHK(hipSetDevice(h->cfg.device));
     LwArgs a = lw_shard_args(h, t);
     a.xr = const_cast<double*>(w_xr); a.thr = const_cast<double*>(w_thr); a.lw1 = const_cast<double*>(w_lw1);
     a.cdfA = const_cast<double*>(w_cdfA); a.tsumA = const_cast<double*>(tsumA_all); a.tmaxA = const_cast<double*>(tmaxA_all);
@@ -2136,7 +1858,7 @@ int ssme_lw_shard_stage2(ssme_lw_handle h, int32_t t, int32_t win_tile0, int32_t
     a.kidx = kidx;
     if (h->split_l2) lw_launch_stage2<true>(h, dim3(h->sh_Bown, 1), h->lds_bytes_big, a);
     else lw_launch_stage2<false>(h, dim3(h->sh_Bown, 1), h->lds_bytes, a);
-    LWCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     h->t = t + 1;
     return SSME_OK;
 }
@@ -2144,7 +1866,7 @@ int ssme_lw_shard_stage2(ssme_lw_handle h, int32_t t, int32_t win_tile0, int32_t
 int ssme_lw_shard_finalize(ssme_lw_handle h, int32_t t, const double* tsumB_all, const double* tmaxB_all) {
     if (!h || t < 0 || !tsumB_all || !tmaxB_all) return SSME_ERR_INVALID_ARG;
     if (h->shard_world < 1) return SSME_ERR_STATE;
-    LWCHK(hipSetDevice(h->cfg.device));
+    HIPCHK(hipSetDevice(h->cfg.device));
     LwArgs a = lw_shard_args(h, t);
     a.tsumB = const_cast<double*>(tsumB_all); a.tmaxB = const_cast<double*>(tmaxB_all);
     if (h->split_l2) {
@@ -2152,8 +1874,8 @@ int ssme_lw_shard_finalize(ssme_lw_handle h, int32_t t, const double* tsumB_all,
         hipLaunchKernelGGL(k_lw_finalize<true>, dim3(1), dim3(kThreads), 0, h->stream, a);
     } else
         hipLaunchKernelGGL(k_lw_finalize<false>, dim3(1), dim3(kThreads), 0, h->stream, a);
-    LWCHK(hipGetLastError());
-    LWCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(h->stream));
     return SSME_OK;
 }
 
@@ -2163,52 +1885,19 @@ int ssme_lw_shard_finalize(ssme_lw_handle h, int32_t t, const double* tsumB_all,
 //   grouped all-gather (tsumA, tmaxA, 16 moment slots per tile)  [-> plan(1)]  -> mid  -> halo exchange of (xr, theta r, g1, cdfA)  -> stage 2
 // The stage kernels check their own source tiles against the exchanged window and raise a flag (read once, after the
 // series): SSME_ERR_STATE then tells the caller to run the exact, host-planned loop (ssme_amd/sharded.py: ShardedLiuWest).
-#define LWNCCL(call) do { ncclResult_t r_ = (call); if (r_ != ncclSuccess) { \
-    h->err = std::string(#call) + ": " + (rccl().GetErrorString ? rccl().GetErrorString(r_) : "RCCL error"); return SSME_ERR_HIP; } } while (0)
 
 static int lw_shard_alloc(ssme_lw_handle h) {
     if (h->sh_xB) return SSME_OK;
-    const int world = h->shard_world, Bl = h->sh_Bl;
-    int m = Bl / 64 > 4 ? Bl / 64 : 4;
-    if (m > Bl) m = Bl;
-    if (world == 1) m = 0;
-    h->sh_margin = m; h->sh_rows = Bl + 2 * m;
-    const size_t row = sizeof(double) * kTile, rows = (size_t)h->sh_rows;
-    double** one[] = {&h->sh_xB, &h->sh_cdfB, &h->sh_xr, &h->sh_g1, &h->sh_cdfA};
-    for (auto p : one) { LWCHK(hipMalloc(p, row * rows)); LWCHK(hipMemset(*p, 0, row * rows)); }
-    double** four[] = {&h->sh_thB, &h->sh_thr};
-    for (auto p : four) { LWCHK(hipMalloc(p, row * rows * kDP)); LWCHK(hipMemset(*p, 0, row * rows * kDP)); }
-    LWCHK(hipMalloc(&h->sh_locB, sizeof(double) * 2 * Bl));
-    LWCHK(hipMalloc(&h->sh_locA, sizeof(double) * 18 * Bl));                 // tile sums | tile maxima | 16 moment slots per tile
-    LWCHK(hipMemset(h->sh_locA, 0, sizeof(double) * 18 * Bl));
-    double** all[] = {&h->sh_allB_s, &h->sh_allB_m, &h->sh_allA_s, &h->sh_allA_m};
-    const size_t nall = (size_t)world * Bl > (size_t)h->Bs ? (size_t)world * Bl : (size_t)h->Bs;        // gathered: world x Bl entries, the first B are tiles
-    for (auto p : all) LWCHK(hipMalloc(p, sizeof(double) * nall));
-    LWCHK(hipMalloc(&h->sh_mom_all, sizeof(double) * nall * 16));
-    LWCHK(hipMemset(h->sh_locB, 0, sizeof(double) * 2 * Bl));
-    LWCHK(hipMalloc(&h->sh_flag, sizeof(int32_t) * 4));
-    return SSME_OK;
-}
-
-// halo exchange with the two neighbouring ranks for a list of buffers (rows of `width` doubles per tile)
-static int lw_halo_exchange(ssme_lw_handle h, ncclComm_t comm, std::initializer_list<std::pair<double*, size_t>> bufs) {
-    const int world = h->shard_world, rank = h->shard_rank, Bl = h->sh_Bl, m = h->sh_margin;
-    if (world == 1 || m == 0) return SSME_OK;
-    LWNCCL(rccl().GroupStart());
-    for (auto& bw : bufs) {
-        double* buf = bw.first;
-        const size_t w = bw.second;
-        if (rank > 0) {
-            LWNCCL(rccl().Send(buf + (size_t)m * w, (size_t)m * w, ncclDouble, rank - 1, comm, h->stream));
-            LWNCCL(rccl().Recv(buf, (size_t)m * w, ncclDouble, rank - 1, comm, h->stream));
-        }
-        if (rank + 1 < world) {
-            LWNCCL(rccl().Send(buf + (size_t)Bl * w, (size_t)m * w, ncclDouble, rank + 1, comm, h->stream));
-            LWNCCL(rccl().Recv(buf + (size_t)(m + Bl) * w, (size_t)m * w, ncclDouble, rank + 1, comm, h->stream));
-        }
-    }
-    LWNCCL(rccl().GroupEnd());
-    h->sh_exchanged += (long)m * ((rank > 0) + (rank + 1 < world));
+    const int Bl = h->sh_Bl;
+    h->sh_margin = halo_margin(Bl, h->shard_world); h->sh_rows = Bl + 2 * h->sh_margin;
+    const size_t rows = sizeof(double) * kTile * h->sh_rows, nall = gathered_len(h);
+    for (double** p : {&h->sh_xB, &h->sh_cdfB, &h->sh_xr, &h->sh_g1, &h->sh_cdfA}) HIPCHK(own_alloc(h, *p, rows, Mem::zeroed));
+    for (double** p : {&h->sh_thB, &h->sh_thr}) HIPCHK(own_alloc(h, *p, rows * kDP, Mem::zeroed));
+    HIPCHK(own_alloc(h, h->sh_locB, sizeof(double) * 2 * Bl, Mem::zeroed));
+    HIPCHK(own_alloc(h, h->sh_locA, sizeof(double) * 18 * Bl, Mem::zeroed));        // tile sums | tile maxima | 16 moment slots per tile
+    for (double** p : {&h->sh_allB_s, &h->sh_allB_m, &h->sh_allA_s, &h->sh_allA_m}) HIPCHK(own_alloc(h, *p, sizeof(double) * nall));
+    HIPCHK(own_alloc(h, h->sh_mom_all, sizeof(double) * nall * 16));
+    HIPCHK(own_alloc(h, h->sh_flag, sizeof(int32_t) * 4));
     return SSME_OK;
 }
 
@@ -2217,28 +1906,21 @@ int ssme_lw_shard_run_series(ssme_lw_handle h, void* nccl_comm, const double* y,
     if (h->shard_world < 1) return SSME_ERR_STATE;
     if (T < 1) return SSME_ERR_LENGTH;
     if (!rccl().ok) { h->err = "RCCL (librccl.so) not found in this process"; return SSME_ERR_UNSUPPORTED; }
-    LWCHK(hipSetDevice(h->cfg.device));
+    HIPCHK(hipSetDevice(h->cfg.device));
     ncclComm_t comm = reinterpret_cast<ncclComm_t>(nccl_comm);
     int rc = lw_shard_alloc(h);
     if (rc != SSME_OK) return rc;
-    const int world = h->shard_world, Bl = h->sh_Bl, m = h->sh_margin, tile0 = h->shard_rank * Bl;
-    (void)world;
+    const int Bl = h->sh_Bl, m = h->sh_margin, tile0 = h->shard_rank * Bl;
     const size_t TL = kTile, off = (size_t)m * TL;
     rc = ssme_lw_shard_set_plane_tiles(h, h->sh_rows);
     if (rc != SSME_OK) return rc;
     rc = ssme_lw_shard_prepare(h, y, z, T);
     if (rc != SSME_OK) return rc;
-    LWCHK(hipMemsetAsync(h->sh_flag, 0, sizeof(int32_t) * 4, h->stream));
+    HIPCHK(hipMemsetAsync(h->sh_flag, 0, sizeof(int32_t) * 4, h->stream));
     h->sh_exchanged = 0;
     double *tsB = h->sh_locB, *tmB = h->sh_locB + Bl;
     double *tsA = h->sh_locA, *tmA = h->sh_locA + Bl, *momL = h->sh_locA + 2 * Bl;
-    auto gatherB = [&]() -> int {
-        LWNCCL(rccl().GroupStart());
-        LWNCCL(rccl().AllGather(tsB, h->sh_allB_s, (size_t)Bl, ncclDouble, comm, h->stream));
-        LWNCCL(rccl().AllGather(tmB, h->sh_allB_m, (size_t)Bl, ncclDouble, comm, h->stream));
-        LWNCCL(rccl().GroupEnd());
-        return SSME_OK;
-    };
+    auto gatherB = [&] { return all_gather(h, comm, {{tsB, h->sh_allB_s, (size_t)Bl}, {tmB, h->sh_allB_m, (size_t)Bl}}); };
     rc = ssme_lw_shard_init(h, h->sh_xB + off, h->sh_thB + off * kDP, h->sh_cdfB + off, tsB, tmB);
     if (rc != SSME_OK) return rc;
     for (int t = 1; t < T; ++t) {
@@ -2247,9 +1929,9 @@ int ssme_lw_shard_run_series(ssme_lw_handle h, void* nccl_comm, const double* y,
         const bool resampled = (t % h->rs) == 0;
         rc = gatherB();
         if (rc != SSME_OK) return rc;
-        if (h->split_l2) { lw_launch_plan(h, 0, t, t, h->sh_allB_s, h->sh_allB_m, resampled); LWCHK(hipGetLastError()); }
+        if (h->split_l2) { lw_launch_plan(h, 0, t, t, h->sh_allB_s, h->sh_allB_m, resampled); HIPCHK(hipGetLastError()); }
         if (resampled) {
-            rc = lw_halo_exchange(h, comm, {{h->sh_xB, TL}, {h->sh_thB, TL * kDP}, {h->sh_cdfB, TL}});
+            rc = halo_exchange(h, comm, {{h->sh_xB, TL}, {h->sh_thB, TL * kDP}, {h->sh_cdfB, TL}});
             if (rc != SSME_OK) return rc;
             h->sh_check = 1;
             rc = ssme_lw_shard_stage1(h, t, tile0 - m, h->sh_rows, h->sh_xB, h->sh_thB, h->sh_cdfB, h->sh_allB_s, h->sh_allB_m,
@@ -2260,19 +1942,16 @@ int ssme_lw_shard_run_series(ssme_lw_handle h, void* nccl_comm, const double* y,
                                       h->sh_xr + off, h->sh_thr + off * kDP, h->sh_g1 + off, h->sh_cdfA + off, tsA, tmA, momL, nullptr);
         }
         if (rc != SSME_OK) return rc;
-        LWNCCL(rccl().GroupStart());
-        LWNCCL(rccl().AllGather(tsA, h->sh_allA_s, (size_t)Bl, ncclDouble, comm, h->stream));
-        LWNCCL(rccl().AllGather(tmA, h->sh_allA_m, (size_t)Bl, ncclDouble, comm, h->stream));
-        LWNCCL(rccl().AllGather(momL, h->sh_mom_all, (size_t)Bl * 16, ncclDouble, comm, h->stream));
-        LWNCCL(rccl().GroupEnd());
+        rc = all_gather(h, comm, {{tsA, h->sh_allA_s, (size_t)Bl}, {tmA, h->sh_allA_m, (size_t)Bl}, {momL, h->sh_mom_all, (size_t)Bl * 16}});
+        if (rc != SSME_OK) return rc;
         // the plan of the k draw first: above 1024 tiles it provides the (m, S) that mid turns into the first-stage log-sum-exp
         // (SISR form, form 1: no first-stage weights and no k draw -- every particle continues itself, so stage 2 reads this
         //  rank's own stage-1 outputs and the second exchange does not exist: ONE exchange per step)
-        if (h->split_l2 && h->form == 0) { lw_launch_plan(h, 1, t, t, h->sh_allA_s, h->sh_allA_m, true); LWCHK(hipGetLastError()); }
+        if (h->split_l2 && h->form == 0) { lw_launch_plan(h, 1, t, t, h->sh_allA_s, h->sh_allA_m, true); HIPCHK(hipGetLastError()); }
         rc = ssme_lw_shard_mid(h, t, h->sh_allA_s, h->sh_allA_m, h->sh_mom_all);
         if (rc != SSME_OK) return rc;
         if (h->form == 0) {
-            rc = lw_halo_exchange(h, comm, {{h->sh_xr, TL}, {h->sh_thr, TL * kDP}, {h->sh_g1, TL}, {h->sh_cdfA, TL}});
+            rc = halo_exchange(h, comm, {{h->sh_xr, TL}, {h->sh_thr, TL * kDP}, {h->sh_g1, TL}, {h->sh_cdfA, TL}});
             if (rc != SSME_OK) return rc;
         }
         h->sh_check = 1;
@@ -2285,10 +1964,8 @@ int ssme_lw_shard_run_series(ssme_lw_handle h, void* nccl_comm, const double* y,
     if (rc != SSME_OK) return rc;
     rc = ssme_lw_shard_finalize(h, T - 1, h->sh_allB_s, h->sh_allB_m);           // synchronises
     if (rc != SSME_OK) return rc;
-    // every rank must take the same branch (see shard_series): reduce the per-rank flags before reading them
-    LWNCCL(rccl().AllReduce(h->sh_flag, h->sh_flag + 3, 1, ncclInt32, ncclMax, comm, h->stream));
-    LWCHK(hipMemcpyAsync(h->sh_stats, h->sh_flag, sizeof(h->sh_stats), hipMemcpyDeviceToHost, h->stream));
-    LWCHK(hipStreamSynchronize(h->stream));
+    rc = reduce_flags(h, comm);
+    if (rc != SSME_OK) return rc;
     if (h->sh_stats[3]) { h->err = "a resampling window left the fixed halo on some rank: run the exact host-planned loop"; return SSME_ERR_STATE; }
     if (loglik_out) return ssme_lw_get_loglik(h, loglik_out);
     return SSME_OK;
@@ -2298,13 +1975,12 @@ int ssme_lw_shard_run_series(ssme_lw_handle h, void* nccl_comm, const double* y,
 int ssme_lw_shard_download(ssme_lw_handle h, double* x_local, double* theta_local, int64_t* exchanged_tiles) {
     if (!h) return SSME_ERR_INVALID_ARG;
     if (h->shard_world < 1 || !h->sh_xB) return SSME_ERR_STATE;
-    LWCHK(hipSetDevice(h->cfg.device));
-    const size_t first = (size_t)h->shard_rank * h->sh_Bl * kTile, off = (size_t)h->sh_margin * kTile;
-    const size_t n = (size_t)h->N - first < (size_t)h->sh_Bown * kTile ? (size_t)h->N - first : (size_t)h->sh_Bown * kTile;      // fewer on the last rank
-    if (x_local) LWCHK(hipMemcpy(x_local, h->sh_xB + off, sizeof(double) * n, hipMemcpyDeviceToHost));
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const size_t off = (size_t)h->sh_margin * kTile, n = own_particles(h);
+    if (x_local) HIPCHK(hipMemcpy(x_local, h->sh_xB + off, sizeof(double) * n, hipMemcpyDeviceToHost));
     if (theta_local) {
         std::vector<double> rec(n * kDP);
-        LWCHK(hipMemcpy(rec.data(), h->sh_thB + off * kDP, sizeof(double) * rec.size(), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(rec.data(), h->sh_thB + off * kDP, sizeof(double) * rec.size(), hipMemcpyDeviceToHost));
         for (size_t i = 0; i < n; ++i) for (int d = 0; d < kDP; ++d) theta_local[(size_t)d * n + i] = rec[i * kDP + d];
     }
     if (exchanged_tiles) *exchanged_tiles = h->sh_exchanged;
@@ -2320,29 +1996,23 @@ int ssme_lw_shard_stats(ssme_lw_handle h, int32_t* out4) {
 
 int ssme_lw_get_loglik(ssme_lw_handle h, double* out) {
     if (!h || !out) return SSME_ERR_INVALID_ARG;
-    LWCHK(hipSetDevice(h->cfg.device));
-    std::vector<LwScalars> sc(h->R);
-    LWCHK(hipMemcpyAsync(sc.data(), h->scal, sizeof(LwScalars) * h->R, hipMemcpyDeviceToHost, h->stream));
-    LWCHK(hipStreamSynchronize(h->stream));
-    for (int r = 0; r < h->R; ++r) out[r] = sc[r].loglik;
-    return SSME_OK;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    return read_loglik(h, out);
 }
 
 int ssme_lw_reset(ssme_lw_handle h) {
     if (!h) return SSME_ERR_INVALID_ARG;
-    LWCHK(hipSetDevice(h->cfg.device));
+    HIPCHK(hipSetDevice(h->cfg.device));
     return lw_reset(h);
 }
 
 int ssme_lw_set_debug(ssme_lw_handle h, int32_t flags) {
     if (!h) return SSME_ERR_INVALID_ARG;
     if (h->shard_world > 0 && (flags & 1)) return SSME_ERR_STATE;   // index recording needs the handle's own buffers
-    LWCHK(hipSetDevice(h->cfg.device));
+    HIPCHK(hipSetDevice(h->cfg.device));
     if ((flags & 1) && !h->anc) {
-        LWCHK(hipMalloc(&h->anc, sizeof(uint32_t) * (size_t)h->R * h->Npad));
-        LWCHK(hipMalloc(&h->kidx, sizeof(uint32_t) * (size_t)h->R * h->Npad));
-        LWCHK(hipMemset(h->anc, 0, sizeof(uint32_t) * (size_t)h->R * h->Npad));
-        LWCHK(hipMemset(h->kidx, 0, sizeof(uint32_t) * (size_t)h->R * h->Npad));
+        HIPCHK(own_alloc(h, h->anc, sizeof(uint32_t) * (size_t)h->R * h->Npad, Mem::zeroed));
+        HIPCHK(own_alloc(h, h->kidx, sizeof(uint32_t) * (size_t)h->R * h->Npad, Mem::zeroed));
     }
     h->debug = flags;
     h->split_l2 = (h->B > kMaxTilesPerFilter || (flags & 4)) ? 1 : ((flags & 8) ? 0 : (h->B > kSplitLevel2Above ? 1 : 0));
@@ -2352,7 +2022,7 @@ int ssme_lw_set_debug(ssme_lw_handle h, int32_t flags) {
 int ssme_lw_step(ssme_lw_handle h, const double* y, const double* z, double* out) {
     if (!h || !y) return SSME_ERR_INVALID_ARG;
     if (h->shard_world > 0) return SSME_ERR_STATE;     // sharded handles own no particle buffers: ssme_lw_shard_* drives them
-    LWCHK(hipSetDevice(h->cfg.device));
+    HIPCHK(hipSetDevice(h->cfg.device));
     const double z0 = z ? *z : 0.0;
     if (h->gcap < kStepGammaChunk) {
         int rc = lw_ensure_gamma(h, kStepGammaChunk);
@@ -2361,19 +2031,12 @@ int ssme_lw_step(ssme_lw_handle h, const double* y, const double* z, double* out
     // y and z travel in the kernel arguments, the R results come back through device-mapped pinned memory written by the
     // accounting kernel: no copy operation in either direction
     const double yz[2] = {*y, z0};
-    int gi = 0;
-    if (h->t > 0) {                              // Gamma tables of both draws, kStepGammaChunk steps at a time
-        if (h->t < h->gamma_t0 || h->t >= h->gamma_t0 + h->gamma_rows) {
-            lw_launch_gamma(h, h->t, kStepGammaChunk);
-            h->gamma_t0 = h->t; h->gamma_rows = kStepGammaChunk;
-        }
-        gi = h->t - h->gamma_t0;
-    }
+    const int gi = h->t > 0 ? step_gamma_row(h, lw_launch_gamma) : 0;      // Gamma tables of both draws
     mark_results_pending(h->pin, h->R);
     lw_enqueue_step(h, h->t, 0, gi, false, /*finalize_prev=*/false, yz);
     lw_enqueue_finalize(h, h->t, false, h->pin_dev);          // the step API accounts each step right away
-    LWCHK(hipGetLastError());
-    LWCHK(wait_results(h->stream, h->pin, h->R));
+    HIPCHK(hipGetLastError());
+    HIPCHK(wait_results(h->stream, h->pin, h->R));
     if (out) for (int r = 0; r < h->R; ++r) out[r] = h->pin[r];
     h->t += 1;
     return SSME_OK;
@@ -2383,37 +2046,28 @@ int ssme_lw_run_series(ssme_lw_handle h, const double* y, const double* z, int32
     if (!h || !y) return SSME_ERR_INVALID_ARG;
     if (h->shard_world > 0) return SSME_ERR_STATE;     // sharded handles own no particle buffers: ssme_lw_shard_* drives them
     if (T < 1) return SSME_ERR_LENGTH;
-    LWCHK(hipSetDevice(h->cfg.device));
+    HIPCHK(hipSetDevice(h->cfg.device));
     int rc = lw_ensure_capacity(h, T);
     if (rc != SSME_OK) return rc;
-    LWCHK(hipMemcpyAsync(h->ybuf, y, sizeof(double) * T, hipMemcpyHostToDevice, h->stream));
-    if (z) LWCHK(hipMemcpyAsync(h->zbuf, z, sizeof(double) * T, hipMemcpyHostToDevice, h->stream));
-    else LWCHK(hipMemsetAsync(h->zbuf, 0, sizeof(double) * T, h->stream));
+    HIPCHK(hipMemcpyAsync(h->ybuf, y, sizeof(double) * T, hipMemcpyHostToDevice, h->stream));
+    if (z) HIPCHK(hipMemcpyAsync(h->zbuf, z, sizeof(double) * T, hipMemcpyHostToDevice, h->stream));
+    else HIPCHK(hipMemsetAsync(h->zbuf, 0, sizeof(double) * T, h->stream));
     rc = lw_reset(h);
     if (rc != SSME_OK) return rc;
-    LWCHK(hipEventRecord(h->ev0, h->stream));
+    HIPCHK(hipEventRecord(h->ev0, h->stream));
     lw_launch_gamma(h, 0, T);
     for (int t = 0; t < T; ++t) lw_enqueue_step(h, t, t, t, true, /*finalize_prev=*/t > 0);
     lw_enqueue_finalize(h, T - 1, true);
-    LWCHK(hipEventRecord(h->ev1, h->stream));
-    LWCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(h->ev1, h->stream));
+    HIPCHK(hipGetLastError());
     h->t = T;
-    std::vector<LwScalars> sc(h->R);
-    LWCHK(hipMemcpyAsync(sc.data(), h->scal, sizeof(LwScalars) * h->R, hipMemcpyDeviceToHost, h->stream));
-    LWCHK(hipStreamSynchronize(h->stream));
-    LWCHK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
-    if (loglik_out) for (int r = 0; r < h->R; ++r) loglik_out[r] = sc[r].loglik;
+    rc = read_loglik(h, loglik_out);
+    if (rc != SSME_OK) return rc;
+    HIPCHK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
     return SSME_OK;
 }
 
-int ssme_lw_get_per_step(ssme_lw_handle h, double* out, int32_t T) {
-    if (!h || !out || T < 1 || T > h->tcap) return SSME_ERR_INVALID_ARG;
-    LWCHK(hipSetDevice(h->cfg.device));
-    for (int r = 0; r < h->R; ++r)
-        LWCHK(hipMemcpyAsync(out + (size_t)r * T, h->per_step + (size_t)r * h->tcap, sizeof(double) * T, hipMemcpyDeviceToHost, h->stream));
-    LWCHK(hipStreamSynchronize(h->stream));
-    return SSME_OK;
-}
+int ssme_lw_get_per_step(ssme_lw_handle h, double* out, int32_t T) { return read_per_step(h, out, T); }
 
 // [R][8] on the host: E[theta_d] (4), E[x], E[x^2], E[exp(x/2)], E[42] under the last step's weights
 static int lw_expect_table(ssme_lw_handle h, std::vector<double>& tab) {
@@ -2421,10 +2075,10 @@ static int lw_expect_table(ssme_lw_handle h, std::vector<double>& tab) {
     // the per-tile moment scratch is free between steps (stage 1 rewrites it before k_lw_mid reads it)
     hipLaunchKernelGGL(k_lw_param_partials, dim3(h->B, h->R), dim3(kThreads), 0, h->stream, a);
     hipLaunchKernelGGL(k_lw_param_means, dim3(h->R), dim3(kWave), 0, h->stream, a, h->scratch);
-    LWCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     tab.resize((size_t)h->R * kLwNExp);
-    LWCHK(hipMemcpyAsync(tab.data(), h->scratch, sizeof(double) * tab.size(), hipMemcpyDeviceToHost, h->stream));
-    LWCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpyAsync(tab.data(), h->scratch, sizeof(double) * tab.size(), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
     return SSME_OK;
 }
 
@@ -2432,7 +2086,7 @@ int ssme_lw_get_param_means(ssme_lw_handle h, double* out) {
     if (!h || !out) return SSME_ERR_INVALID_ARG;
     if (h->shard_world > 0) return SSME_ERR_STATE;     // sharded handles own no particle buffers: ssme_lw_shard_* drives them
     if (h->t < 1) return SSME_ERR_STATE;
-    LWCHK(hipSetDevice(h->cfg.device));
+    HIPCHK(hipSetDevice(h->cfg.device));
     std::vector<double> tab;
     int rc = lw_expect_table(h, tab);
     if (rc != SSME_OK) return rc;
@@ -2445,7 +2099,7 @@ int ssme_lw_get_expectations(ssme_lw_handle h, const int32_t* functionals, int32
     for (int i = 0; i < n; ++i) if (functionals[i] < 0 || functionals[i] > 7) return SSME_ERR_INVALID_ARG;
     if (h->shard_world > 0) return SSME_ERR_STATE;
     if (h->t < 1) return SSME_ERR_STATE;
-    LWCHK(hipSetDevice(h->cfg.device));
+    HIPCHK(hipSetDevice(h->cfg.device));
     std::vector<double> tab;
     int rc = lw_expect_table(h, tab);
     if (rc != SSME_OK) return rc;
@@ -2458,16 +2112,16 @@ int ssme_lw_download_weights(ssme_lw_handle h, int32_t f, double* x, double* the
     if (!h || f < 0 || f >= h->R || !w) return SSME_ERR_INVALID_ARG;
     if (h->shard_world > 0) return SSME_ERR_STATE;
     if (h->t < 1) return SSME_ERR_STATE;
-    LWCHK(hipSetDevice(h->cfg.device));
-    if (!h->wscratch) LWCHK(hipMalloc(&h->wscratch, sizeof(double) * (size_t)h->Npad * (1 + kDP)));
+    HIPCHK(hipSetDevice(h->cfg.device));
+    if (!h->wscratch) HIPCHK(own_alloc(h, h->wscratch, sizeof(double) * (size_t)h->Npad * (1 + kDP)));
     LwArgs a = lw_args(h);
     hipLaunchKernelGGL(k_lw_weights, dim3(h->B), dim3(kThreads), 0, h->stream, a, (int)f, h->wscratch);
-    LWCHK(hipGetLastError());
-    LWCHK(hipMemcpyAsync(w, h->wscratch, sizeof(double) * h->N, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(w, h->wscratch, sizeof(double) * h->N, hipMemcpyDeviceToHost, h->stream));
     if (theta_untrans) for (int d = 0; d < kDP; ++d)
-        LWCHK(hipMemcpyAsync(theta_untrans + (size_t)d * h->N, h->wscratch + (size_t)(1 + d) * h->Npad, sizeof(double) * h->N, hipMemcpyDeviceToHost, h->stream));
-    if (x) LWCHK(hipMemcpyAsync(x, h->xB + (size_t)f * h->Npad, sizeof(double) * h->N, hipMemcpyDeviceToHost, h->stream));
-    LWCHK(hipStreamSynchronize(h->stream));
+        HIPCHK(hipMemcpyAsync(theta_untrans + (size_t)d * h->N, h->wscratch + (size_t)(1 + d) * h->Npad, sizeof(double) * h->N, hipMemcpyDeviceToHost, h->stream));
+    if (x) HIPCHK(hipMemcpyAsync(x, h->xB + (size_t)f * h->Npad, sizeof(double) * h->N, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
     return SSME_OK;
 }
 
@@ -2475,34 +2129,30 @@ int ssme_lw_download_state(ssme_lw_handle h, int32_t f, double* x, double* theta
                            double* chol) {
     if (!h || f < 0 || f >= h->R) return SSME_ERR_INVALID_ARG;
     if (h->shard_world > 0) return SSME_ERR_STATE;     // sharded handles own no particle buffers: ssme_lw_shard_* drives them
-    LWCHK(hipSetDevice(h->cfg.device));
+    HIPCHK(hipSetDevice(h->cfg.device));
     const size_t off = (size_t)f * h->Npad;
-    if (x) LWCHK(hipMemcpyAsync(x, h->xB + off, sizeof(double) * h->N, hipMemcpyDeviceToHost, h->stream));
+    if (x) HIPCHK(hipMemcpyAsync(x, h->xB + off, sizeof(double) * h->N, hipMemcpyDeviceToHost, h->stream));
     std::vector<double> rec;                       // the device keeps one [4]-record per particle; callers get parameter planes
     if (theta) {
         rec.resize((size_t)h->N * kDP);
-        LWCHK(hipMemcpyAsync(rec.data(), h->thB + (size_t)f * h->Npad * kDP, sizeof(double) * rec.size(), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipMemcpyAsync(rec.data(), h->thB + (size_t)f * h->Npad * kDP, sizeof(double) * rec.size(), hipMemcpyDeviceToHost, h->stream));
     }
     if (kidx || anc) {
         if (!h->anc) return SSME_ERR_STATE;
-        if (kidx) LWCHK(hipMemcpyAsync(kidx, h->kidx + off, sizeof(uint32_t) * h->N, hipMemcpyDeviceToHost, h->stream));
-        if (anc) LWCHK(hipMemcpyAsync(anc, h->anc + off, sizeof(uint32_t) * h->N, hipMemcpyDeviceToHost, h->stream));
+        if (kidx) HIPCHK(hipMemcpyAsync(kidx, h->kidx + off, sizeof(uint32_t) * h->N, hipMemcpyDeviceToHost, h->stream));
+        if (anc) HIPCHK(hipMemcpyAsync(anc, h->anc + off, sizeof(uint32_t) * h->N, hipMemcpyDeviceToHost, h->stream));
     }
     double p[16];
-    LWCHK(hipMemcpyAsync(p, h->prop + (size_t)f * 16, sizeof(p), hipMemcpyDeviceToHost, h->stream));
-    LWCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpyAsync(p, h->prop + (size_t)f * 16, sizeof(p), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
     if (theta) for (int i = 0; i < h->N; ++i) for (int d = 0; d < kDP; ++d) theta[(size_t)d * h->N + i] = rec[(size_t)i * kDP + d];
     if (thetabar) for (int d = 0; d < kDP; ++d) thetabar[d] = p[d];
     if (chol) { int q = kDP; for (int d = 0; d < kDP; ++d) for (int e = 0; e < kDP; ++e) chol[d * kDP + e] = (e <= d) ? p[q++] : 0.0; }
     return SSME_OK;
 }
 
-int ssme_lw_last_elapsed_ms(ssme_lw_handle h, float* ms) {
-    if (!h || !ms) return SSME_ERR_INVALID_ARG;
-    *ms = h->last_ms;
-    return SSME_OK;
-}
+int ssme_lw_last_elapsed_ms(ssme_lw_handle h, float* ms) { return elapsed_ms(h, ms); }
 
-const char* ssme_lw_last_error(ssme_lw_handle h) { return h ? h->err.c_str() : ""; }
+const char* ssme_lw_last_error(ssme_lw_handle h) { return last_error(h); }
 
 }  // extern "C"

@@ -402,11 +402,7 @@ class svol_lw_1_par:
     __del__ = close
 
     def _chk(self, status):
-        if status != capi.OK:
-            msg = capi.lib().ssme_pf_strerror(status).decode()
-            if status == capi.ERR_HIP:
-                msg += " (" + capi.lib().ssme_lw_last_error(self._h).decode() + ")"
-            raise SsmeError(status, msg)
+        capi.check(status, self._h, last_error=capi.lib().ssme_lw_last_error)
 
     def set_debug(self, on=True, split_level2=None):
         """Record k / ancestor indices; split_level2: True / False force the level-2 policy (None: split above 1024 tiles)."""

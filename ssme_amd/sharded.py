@@ -193,11 +193,13 @@ def exchange_halos(bufs, tile0, plan, tiles_per_rank, rank, group=None, stage_th
     return lo, hi - lo + 1
 
 
-class ShardedParticleFilter:
-    """Bootstrap filter with its N particles sharded over the ranks of a torch.distributed group."""
+class _ShardedFilter:
+    """What the sharded bootstrap and Liu-West filters share: the process group and this rank's layout, the handle's side
+    stream, its life cycle, the native communicator and the statistics.  _api: the C ABI's prefix of the handle type."""
 
-    def __init__(self, model, n_particles, seed=0, resampler=capi.RESAMP_MULTINOMIAL, device=None, group=None, filter_id=0,
-                 resamp_sched=1):
+    _api = "ssme_pf"
+
+    def __init__(self, n_particles, device, group):
         import torch
         import torch.distributed as dist
         assert dist.is_initialized(), "init_process_group first (one process per GPU)"
@@ -208,15 +210,66 @@ class ShardedParticleFilter:
         self.n, self.B, self.Bl, self.Bown, self.n_local = shard_layout(n_particles, self.rank, self.world)
         self.tile0 = self.rank * self.Bl
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.exchanged_tiles = 0                                # tiles received from other ranks (statistics)
+        self._T = 0
+        self._h = C.c_void_p()
+        self._comm = None
+
+    def _fn(self, name):
+        return getattr(capi.lib(), self._api + "_" + name)
+
+    def _chk(self, status):
+        capi.check(status, self._h, last_error=self._fn("last_error"))
+
+    def _use_side_stream(self):
+        """One side stream for kernels, staging copies and (nccl) collectives: torch's default stream has handle 0, which
+        set_stream reads as "use the handle's own stream"."""
+        import torch
+        self._stream = torch.cuda.Stream(self.device)
+        self._chk(self._fn("set_stream")(self._h, C.c_void_p(self._stream.cuda_stream)))
+
+    def close(self):
+        if getattr(self, "_comm", None) is not None:
+            capi.lib().ssme_shard_comm_destroy(self._comm)
+            self._comm = None
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self._fn("destroy")(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+    @staticmethod
+    def _ptr(t):
+        return C.c_void_p(t.data_ptr())
+
+    def _count_exchanged(self, lo, hi):
+        """Tiles of the window [lo, hi] that other ranks own."""
+        self.exchanged_tiles += max(0, min(hi + 1, self.tile0) - lo) + max(0, hi - max(lo - 1, self.tile0 + self.Bl - 1))
+
+    def _native_comm(self):
+        """An RCCL communicator for the C++ driver: rank 0 makes the unique id, torch.distributed ships its 128 bytes."""
+        if self._comm is None:
+            self._comm = make_native_comm(self.rank, self.world, self.device.index or 0, self.group)
+        return self._comm
+
+    def per_step(self):
+        out = np.empty((1, self._T))
+        self._chk(self._fn("get_per_step")(self._h, capi.dptr(out), self._T))
+        return out[0]
+
+
+class ShardedParticleFilter(_ShardedFilter):
+    """Bootstrap filter with its N particles sharded over the ranks of a torch.distributed group."""
+
+    def __init__(self, model, n_particles, seed=0, resampler=capi.RESAMP_MULTINOMIAL, device=None, group=None, filter_id=0,
+                 resamp_sched=1):
+        import torch
+        super().__init__(n_particles, device, group)
         self.resamp_sched = int(resamp_sched)
         cfg = capi.Config(model=model, n_particles=n_particles, n_filters=1, dtype=capi.F64, resampler=resampler,
                           resamp_sched=self.resamp_sched, seed=seed, device=self.device.index or 0, first_filter_id=filter_id)
-        self._h = C.c_void_p()
         capi.check(capi.lib().ssme_pf_shard_create(C.byref(cfg), self.rank, self.world, C.byref(self._h)))
-        # one side stream for kernels, staging copies and (nccl) collectives: torch's default stream has handle 0,
-        # which ssme_pf_set_stream reads as "use the handle's own stream"
-        self._stream = torch.cuda.Stream(self.device)
-        self._chk(capi.lib().ssme_pf_set_stream(self._h, C.c_void_p(self._stream.cuda_stream)))
+        self._use_side_stream()
         f64 = dict(dtype=torch.float64, device=self.device)
         # particles and tile-local integer cdf (integers < 2^53 in fp64) after the last step: ping-pong halo buffers
         margin = min(self.B - self.Bl, max(2, self.Bl // 2)) if self.world > 1 else 0
@@ -226,26 +279,7 @@ class ShardedParticleFilter:
         self.tiles_loc = torch.zeros((2, self.Bl), **f64)       # row 0: tile sums, row 1: tile maxima
         self.tiles_all = torch.zeros((2, self.world * self.Bl), **f64)      # gathered: world x Bl entries, the first B are tiles
         self.anc = None
-        self.exchanged_tiles = 0                                # tiles received from other ranks (statistics)
-        self._T = 0
         torch.cuda.synchronize(self.device)
-
-    def close(self):
-        if getattr(self, "_comm", None) is not None:
-            capi.lib().ssme_shard_comm_destroy(self._comm)
-            self._comm = None
-        if getattr(self, "_h", None) is not None and self._h.value:
-            capi.lib().ssme_pf_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = close
-
-    def _chk(self, status):
-        if status != capi.OK:
-            msg = capi.lib().ssme_pf_strerror(status).decode()
-            if status in (capi.ERR_HIP, capi.ERR_STATE, capi.ERR_UNSUPPORTED):
-                msg += " (" + capi.lib().ssme_pf_last_error(self._h).decode() + ")"
-            raise SsmeError(status, msg)
 
     def set_params(self, theta):
         th = np.ascontiguousarray(theta, dtype=np.float64).reshape(1, -1)
@@ -261,9 +295,6 @@ class ShardedParticleFilter:
         G = gather_flat(self.tiles_loc.reshape(-1), self.world, self.group, self.stage)          # [world, 2 * Bl]
         self.tiles_all[0].view(self.world, self.Bl).copy_(G[:, :self.Bl])
         self.tiles_all[1].view(self.world, self.Bl).copy_(G[:, self.Bl:])
-
-    def _ptr(self, t):
-        return C.c_void_p(t.data_ptr())
 
     # ---- the series loop ------------------------------------------------------------------------------------------
     def run_series(self, y, z=None):
@@ -309,8 +340,7 @@ class ShardedParticleFilter:
                 else:
                     win0, wt = got
                     cw, xw = hc.rows(win0, wt, self.tile0), hx.rows(win0, wt, self.tile0)
-                lo_r, hi_r = plan[self.rank]
-                self.exchanged_tiles += max(0, min(hi_r + 1, self.tile0) - lo_r) + max(0, hi_r - max(lo_r - 1, self.tile0 + self.Bl - 1))
+                self._count_exchanged(*plan[self.rank])
             self._chk(L.ssme_pf_shard_step(
                 self._h, t, None if xw is None else self._ptr(xw), None if cw is None else self._ptr(cw), win0,
                 self._ptr(ts), self._ptr(tm), self._ptr(ox.own()), self._ptr(oc.own()), self._ptr(self.tiles_loc[0]),
@@ -323,11 +353,6 @@ class ShardedParticleFilter:
         self._chk(L.ssme_pf_get_loglik(self._h, capi.dptr(out)))
         return float(out[0])
 
-    def per_step(self):
-        out = np.empty((1, self._T))
-        self._chk(capi.lib().ssme_pf_get_per_step(self._h, capi.dptr(out), self._T))
-        return out[0]
-
     def local_particles(self):
         return self._hx[self._cur].own().reshape(-1)[:self.n_local].cpu().numpy()
 
@@ -335,12 +360,6 @@ class ShardedParticleFilter:
         return self._hc[self._cur].own().reshape(-1)[:self.n_local].cpu().numpy()
 
     # ---- the same loop in C++ over RCCL (ssme_pf_shard_run_series): no Python, no host synchronisation per step ----
-    def _native_comm(self):
-        """An RCCL communicator for the C++ driver: rank 0 makes the unique id, torch.distributed ships its 128 bytes."""
-        if getattr(self, "_comm", None) is None:
-            self._comm = make_native_comm(self.rank, self.world, self.device.index or 0, self.group)
-        return self._comm
-
     def run_series_native(self, y, z=None, mode=0):
         """log p(y_{1:T}) through the C++ driver.  mode 0: fixed-halo fast path with an exact rerun if a window ever left
         the halo; 1: fast path only; 2: exact (host-planned) path.  Needs one GPU per rank (RCCL)."""
@@ -363,7 +382,7 @@ class ShardedParticleFilter:
         return x, cdf, path.value, ex.value
 
 
-class ShardedLiuWest:
+class ShardedLiuWest(_ShardedFilter):
     """Liu-West filter (svol_lw_1_par: test/test_liu_west.cpp:22-157) with its particles sharded over the ranks of a
     torch.distributed group -- BASELINE.json configs[4].  Two exchanges per time step (module docstring scheme, twice):
 
@@ -374,6 +393,8 @@ class ShardedLiuWest:
     Bit-identical to the unsharded `svol_lw_1_par.run_series` with the same N and seed (tests/test_sharded_gpu.py).
     """
 
+    _api = "ssme_lw"
+
     def __init__(self, delta, phi_l, phi_u, mu_l, mu_u, sig_l, sig_u, rho_l, rho_u, nparts, seed=0, transforms=(2, 0, 3, 1),
                  device=None, group=None, filter_id=0, form=0, rs=1):
         """form 0: auxiliary-particle form (LWFilterWithCovs); 1: SISR form (LWFilter2WithCovs, svol_lw_2_par): no first-stage
@@ -381,24 +402,15 @@ class ShardedLiuWest:
         rs: the resampling schedule m_rs (liu_west_filter.h:1139-1140): steps without a resampling draw exchange nothing for
         stage 1 (every particle continues itself with its carried second-stage weight)."""
         import torch
-        import torch.distributed as dist
-        assert dist.is_initialized(), "init_process_group first (one process per GPU)"
-        self.group = group
-        self.rank, self.world = dist.get_rank(group), dist.get_world_size(group)
-        self.stage = dist.get_backend(group) != "nccl"
-        self.n, self.B, self.Bl, self.Bown, self.n_local = shard_layout(nparts, self.rank, self.world)
-        self.tile0 = self.rank * self.Bl
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        super().__init__(nparts, device, group)
         self.form, self.rs = int(form), int(rs)
         cfg = capi.LwConfig(n_particles=nparts, n_filters=1, seed=seed, device=self.device.index or 0, first_filter_id=filter_id,
                             delta=delta, form=self.form, resamp_sched=self.rs)
         cfg.transforms[:] = list(transforms)
         cfg.prior_lo[:] = [phi_l, mu_l, sig_l, rho_l]
         cfg.prior_hi[:] = [phi_u, mu_u, sig_u, rho_u]
-        self._h = C.c_void_p()
         capi.check(capi.lib().ssme_lw_shard_create(C.byref(cfg), self.rank, self.world, C.byref(self._h)))
-        self._stream = torch.cuda.Stream(self.device)
-        self._chk(capi.lib().ssme_lw_set_stream(self._h, C.c_void_p(self._stream.cuda_stream)))
+        self._use_side_stream()
         f64 = dict(dtype=torch.float64, device=self.device)
         Bl = self.Bl
         margin = min(self.B - Bl, max(2, Bl // 2)) if self.world > 1 else 0
@@ -416,30 +428,7 @@ class ShardedLiuWest:
         self.allB = torch.zeros((2, self.world * Bl), **f64)   # gathered: world x Bl entries, the first B are tiles
         self.allA = torch.zeros((2, self.world * Bl), **f64)
         self.mom_all = torch.zeros((self.world * Bl, 16), **f64)
-        self.exchanged_tiles = 0
-        self._T = 0
         torch.cuda.synchronize(self.device)
-
-    def close(self):
-        if getattr(self, "_comm", None) is not None:
-            capi.lib().ssme_shard_comm_destroy(self._comm)
-            self._comm = None
-        if getattr(self, "_h", None) is not None and self._h.value:
-            capi.lib().ssme_lw_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = close
-
-    def _chk(self, status):
-        if status != capi.OK:
-            msg = capi.lib().ssme_pf_strerror(status).decode()
-            if status == capi.ERR_HIP:
-                msg += " (" + capi.lib().ssme_lw_last_error(self._h).decode() + ")"
-            raise SsmeError(status, msg)
-
-    @staticmethod
-    def _ptr(t):
-        return C.c_void_p(t.data_ptr())
 
     def _gather_B(self):
         G = gather_flat(self.tilesB.reshape(-1), self.world, self.group, self.stage)               # [world, 2 Bl]
@@ -461,7 +450,7 @@ class ShardedLiuWest:
         self._chk(capi.lib().ssme_lw_shard_plan(self._h, which, t, self._ptr(tiles_all[0]), self._ptr(tiles_all[1]), lo_hi))
         plan = [(lo_hi[2 * g], lo_hi[2 * g + 1]) for g in range(self.world)]
         lo_r, hi_r = plan[self.rank]
-        self.exchanged_tiles += max(0, min(hi_r + 1, self.tile0) - lo_r) + max(0, hi_r - max(lo_r - 1, self.tile0 + self.Bl - 1))
+        self._count_exchanged(lo_r, hi_r)
         got = exchange_halos(halos2d + [halo_th], self.tile0, plan, self.Bl, self.rank, self.group, self.stage)
         if got is not None:
             w0, wt = got
@@ -518,11 +507,6 @@ class ShardedLiuWest:
         self._chk(L.ssme_lw_get_loglik(self._h, capi.dptr(out)))
         return float(out[0])
 
-    def per_step(self):
-        out = np.empty((1, self._T))
-        self._chk(capi.lib().ssme_lw_get_per_step(self._h, capi.dptr(out), self._T))
-        return out[0]
-
     def local_particles(self):
         return self.xB.own().reshape(-1)[:self.n_local].cpu().numpy()
 
@@ -539,11 +523,10 @@ class ShardedLiuWest:
         import torch
         yv = capi.as_f64(y)
         zv = None if z is None else capi.as_f64(z)
-        if getattr(self, "_comm", None) is None:
-            self._comm = make_native_comm(self.rank, self.world, self.device.index or 0, self.group)
+        comm = self._native_comm()
         self._stream.wait_stream(torch.cuda.current_stream(self.device))
         out = np.empty(1)
-        st = capi.lib().ssme_lw_shard_run_series(self._h, self._comm, capi.dptr(yv), capi.dptr(zv), yv.size, capi.dptr(out))
+        st = capi.lib().ssme_lw_shard_run_series(self._h, comm, capi.dptr(yv), capi.dptr(zv), yv.size, capi.dptr(out))
         self.native_path = "fixed halo"
         if st == capi.ERR_STATE:
             self.native_path = "exact (Python-driven) after a window left the halo"
