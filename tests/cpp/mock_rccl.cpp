@@ -44,7 +44,10 @@ World* g_pending = nullptr;      // the world being assembled by ncclCommInitRan
 
 ncclResult_t flush() {
     Comm* c = g_comm;
-    if (!c || g_ops.empty()) { g_ops.clear(); return ncclSuccess; }
+    if (!c) { g_ops.clear(); return ncclSuccess; }
+    // A group without operations still takes part in the rendezvous: every flush is a barrier over ALL ranks here, and a rank whose
+    // planned window lies inside its own tiles while nobody reads them posts nothing (real RCCL lets it pass; leaving early here put
+    // it one rendezvous ahead of its peers, which then paired their operations with its NEXT group).
     World* w = c->w;
     if (hipStreamSynchronize(g_stream) != hipSuccess) return ncclUnhandledCudaError;       // my send buffers are final
     { std::lock_guard<std::mutex> lk(w->mu); w->posted[c->rank] = g_ops; }

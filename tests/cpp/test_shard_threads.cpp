@@ -1,19 +1,25 @@
 // test_shard_threads.cpp -- the C++ shard drivers with SEVERAL ranks on one GPU: every rank is a host thread with its own
 // handle, the "RCCL" underneath is tests/cpp/mock_rccl.cpp (linked before anything else, so dlsym finds it).  Prints, per
 // configuration, what every rank got and what the unsharded filter gives; tests/test_sharded_gpu.py compares.
-//   usage: test_shard_threads CSV WORLD N T MODEL RESAMPLER MODE SEED [TAU [YSCALE [RESAMP_SCHED [LW_FORM]]]]     (MODEL -1: Liu-West, RESAMPLER = delta x 1000)
+//   usage: test_shard_threads CSV WORLD N T MODEL RESAMPLER MODE SEED [TAU [YSCALE [RESAMP_SCHED [LW_FORM [DUMP]]]]]     (MODEL -1: Liu-West, RESAMPLER = delta x 1000)
 //   TAU (linear-Gaussian model only): observation noise; a tiny value puts all the weight of a step on the one particle next to
 //   y_t, so every rank's next resampling window is that particle's tile -- far ranks leave their halo, near ranks do not.
 //   YSCALE: the observations are multiplied by it (outliers: the stochastic-volatility weights then degenerate the same way).
+//   DUMP: a file that receives rank 0's per-step log conditional likelihoods and the ranks' concatenated final state, for comparison
+//   with stored oracle records (tests/test_sharded_gpu.py: _read_dump):  "SSMEDMP1", int64 T, N, kind (0 bootstrap, 1 Liu-West),
+//   complete (1 if the state follows), double per[T], then double x[N] and uint64 cdf[N] (bootstrap) or double theta[4][N] (Liu-West).
+#include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <fstream>
 #include <thread>
 #include <vector>
 
 #include "../../include/ssme_pf.h"
 
-static void die(const char* what, int rc, const char* msg) { std::fprintf(stderr, "%s: status %d (%s)\n", what, rc, msg ? msg : ""); std::exit(3); }
+// _Exit: the other ranks' threads are still running (or waiting for this one in a collective); static destructors under them crash
+static void die(const char* what, int rc, const char* msg) { std::fprintf(stderr, "%s: status %d (%s)\n", what, rc, msg ? msg : ""); std::fflush(nullptr); std::_Exit(3); }
 
 int main(int argc, char** argv) {
     if (argc < 9) return 2;
@@ -22,6 +28,7 @@ int main(int argc, char** argv) {
     const unsigned long long seed = std::strtoull(argv[8], nullptr, 10);
     const int sched = argc > 11 ? std::atoi(argv[11]) : 1;
     const int lw_form = argc > 12 ? std::atoi(argv[12]) : 0;
+    const char* dump = argc > 13 ? argv[13] : nullptr;
     std::vector<double> y, z;
     { std::ifstream f(argv[1]); double v; while (f >> v && (int)y.size() < T) y.push_back(v); }
     if (argc > 10) for (double& v : y) v *= std::atof(argv[10]);
@@ -33,9 +40,12 @@ int main(int argc, char** argv) {
     std::vector<double> ll(world, 0.0);
     std::vector<int> path(world, 0), own_flag(world, 0), any_flag(world, 0);
     std::vector<long long> exch(world, 0);
-    std::vector<std::vector<double>> xs(world);
+    std::vector<int> reach_l(world, 0), reach_r(world, 0);
+    std::vector<std::vector<double>> xs(world), ths(world), pers(world);
+    std::vector<std::vector<uint64_t>> cdfs(world);
     std::vector<size_t> first(world, 0);
     std::vector<std::thread> ranks;
+    const auto t_start = std::chrono::steady_clock::now();
     for (int r = 0; r < world; ++r) ranks.emplace_back([&, r] {
         void* comm = nullptr;
         int rc = ssme_shard_comm_init(id, r, world, 0, &comm);
@@ -48,17 +58,20 @@ int main(int argc, char** argv) {
             rc = ssme_pf_shard_create(&c, r, world, &h);
             if (rc) die("shard_create", rc, "");
             if (ssme_pf_shard_layout(h, lay)) die("shard_layout", 1, "");
-            xs[r].resize((size_t)lay[3]); first[r] = (size_t)r * lay[1] * 2048;
+            xs[r].resize((size_t)lay[3]); cdfs[r].resize((size_t)lay[3]); first[r] = (size_t)r * lay[1] * 2048;
             rc = ssme_pf_set_params(h, model == 0 ? th_svol : (model == 1 ? th_lev : th_lg), model == 1 ? 4 : 3, 1);
             if (rc) die("set_params", rc, ssme_pf_last_error(h));
             rc = ssme_pf_shard_run_series(h, comm, y.data(), model == 1 ? z.data() : nullptr, T, mode, &ll[r]);
             if (rc) die("shard_run_series", rc, ssme_pf_last_error(h));
             int32_t p = 0; int64_t e = 0;
-            ssme_pf_shard_download(h, xs[r].data(), nullptr, &p, &e);
+            ssme_pf_shard_download(h, xs[r].data(), cdfs[r].data(), &p, &e);
             path[r] = p; exch[r] = e;
             int32_t st[4] = {0, 0, 0, 0};
             ssme_pf_shard_stats(h, st);
-            any_flag[r] = st[0]; own_flag[r] = st[1];
+            any_flag[r] = st[0]; own_flag[r] = st[1]; reach_l[r] = st[2]; reach_r[r] = st[3];
+            pers[r].resize((size_t)T);
+            rc = ssme_pf_get_per_step(h, pers[r].data(), T);
+            if (rc) die("get_per_step", rc, ssme_pf_last_error(h));
             ssme_pf_destroy(h);
         } else {
             ssme_lw_config c{};
@@ -75,19 +88,26 @@ int main(int argc, char** argv) {
             path[r] = rc == SSME_ERR_STATE ? 2 : 1;                        // 2: a window left the halo (caller falls back)
             if (rc && rc != SSME_ERR_STATE) die("lw_shard_run_series", rc, ssme_lw_last_error(h));
             int64_t e = 0;
-            if (!rc) ssme_lw_shard_download(h, xs[r].data(), nullptr, &e);
+            if (!rc) { ths[r].resize(4 * (size_t)lay[3]); ssme_lw_shard_download(h, xs[r].data(), ths[r].data(), &e); }
             exch[r] = e;
             int32_t st[4] = {0, 0, 0, 0};
             ssme_lw_shard_stats(h, st);
-            any_flag[r] = st[0]; own_flag[r] = st[1];
+            any_flag[r] = st[0]; own_flag[r] = st[1]; reach_l[r] = st[2]; reach_r[r] = st[3];
+            if (!rc) {
+                pers[r].resize((size_t)T);
+                const int rp = ssme_lw_get_per_step(h, pers[r].data(), T);
+                if (rp) die("lw_get_per_step", rp, ssme_lw_last_error(h));
+            }
             ssme_lw_destroy(h);
         }
         ssme_shard_comm_destroy(comm);
     });
     for (auto& t : ranks) t.join();
+    const auto t_sharded = std::chrono::steady_clock::now();
     // the unsharded filter with the same N and seed
     double ll_ref = 0.0;
-    std::vector<double> xref(N);
+    std::vector<double> xref(N), thref, perref((size_t)T);
+    std::vector<uint64_t> cdfref;
     if (model >= 0) {
         ssme_pf_config c{};
         c.model = model; c.n_particles = N; c.n_filters = 1; c.dtype = SSME_F64; c.resampler = rs; c.resamp_sched = sched; c.seed = seed; c.device = 0;
@@ -96,7 +116,9 @@ int main(int argc, char** argv) {
         if (ssme_pf_create(&c, &h)) die("create", 1, "");
         ssme_pf_set_params(h, model == 0 ? th_svol : (model == 1 ? th_lev : th_lg), model == 1 ? 4 : 3, 1);
         ssme_pf_run_series(h, y.data(), model == 1 ? z.data() : nullptr, T, &ll_ref);
-        ssme_pf_download_state(h, 0, xref.data(), nullptr, nullptr, nullptr);
+        cdfref.resize((size_t)N);
+        ssme_pf_download_state(h, 0, xref.data(), nullptr, cdfref.data(), nullptr);
+        ssme_pf_get_per_step(h, perref.data(), T);
         ssme_pf_destroy(h);
     } else {
         ssme_lw_config c{};
@@ -107,19 +129,54 @@ int main(int argc, char** argv) {
         ssme_lw_handle h = nullptr;
         if (ssme_lw_create(&c, &h)) die("lw_create", 1, "");
         ssme_lw_run_series(h, y.data(), z.data(), T, &ll_ref);
-        ssme_lw_download_state(h, 0, xref.data(), nullptr, nullptr, nullptr, nullptr, nullptr);
+        thref.resize(4 * (size_t)N);
+        ssme_lw_download_state(h, 0, xref.data(), thref.data(), nullptr, nullptr, nullptr, nullptr);
+        ssme_lw_get_per_step(h, perref.data(), T);
         ssme_lw_destroy(h);
     }
-    size_t mism = 0, held = 0;
+    const auto t_end = std::chrono::steady_clock::now();
+    auto differ = [](double a, double b) { uint64_t u, v; std::memcpy(&u, &a, 8); std::memcpy(&v, &b, 8); return u != v; };   // bits, not values
+    size_t mism = 0, held = 0, aux_mism = 0, per_ranks = 0, per_ref = 0;
+    int compared = 0;                                  // ranks whose state and per-step values entered the counts below
+    bool complete = true;                              // every rank ended with a state to compare
     for (int r = 0; r < world; ++r) {
         held += xs[r].size();
-        if (path[r] == 1 || model >= 0)
-            for (size_t i = 0; i < xs[r].size(); ++i) mism += xs[r][i] != xref[first[r] + i];
+        const size_t n = xs[r].size();
+        if (path[r] == 1 || model >= 0) {
+            for (size_t i = 0; i < n; ++i) mism += xs[r][i] != xref[first[r] + i];
+            if (model >= 0) for (size_t i = 0; i < n; ++i) aux_mism += cdfs[r][i] != cdfref[first[r] + i];
+            else for (int d = 0; d < 4; ++d) for (size_t i = 0; i < n; ++i) aux_mism += differ(ths[r][d * n + i], thref[(size_t)d * N + first[r] + i]);
+            for (int t = 0; t < T; ++t) per_ranks += differ(pers[r][t], pers[0][t]);
+            ++compared;
+        } else complete = false;
     }
+    if (complete) for (int t = 0; t < T; ++t) per_ref += differ(pers[0][t], perref[t]);
     if (held != (size_t)N) mism += 1;                  // the ranks' shares add up to the filter
+    if (dump) {
+        std::FILE* f = std::fopen(dump, "wb");
+        if (!f) die("dump", 1, dump);
+        const int64_t hdr[4] = {T, N, model < 0 ? 1 : 0, complete ? 1 : 0};
+        std::fwrite("SSMEDMP1", 1, 8, f);
+        std::fwrite(hdr, 8, 4, f);
+        if (complete) {
+            std::fwrite(pers[0].data(), 8, (size_t)T, f);
+            for (int r = 0; r < world; ++r) std::fwrite(xs[r].data(), 8, xs[r].size(), f);
+            if (model >= 0) for (int r = 0; r < world; ++r) std::fwrite(cdfs[r].data(), 8, cdfs[r].size(), f);
+            else for (int d = 0; d < 4; ++d) for (int r = 0; r < world; ++r) std::fwrite(ths[r].data() + d * xs[r].size(), 8, xs[r].size(), f);
+        }
+        if (std::fclose(f)) die("dump close", 1, dump);
+    }
     std::printf("ref %.17g\n", ll_ref);
     // any_left_halo: the reduced flag of the last fixed-halo pass (identical on every rank); own_left_halo: what this rank's own workgroups saw
     for (int r = 0; r < world; ++r) std::printf("rank %d ll %.17g path %d exchanged %lld any_left_halo %d own_left_halo %d\n", r, ll[r], path[r], exch[r], any_flag[r], own_flag[r]);
+    // widest reach left / right of the rank's own tiles (ssme_*_shard_stats out4[2], out4[3]) beside the two flags above
+    for (int r = 0; r < world; ++r) std::printf("stats %d any_left_halo %d own_left_halo %d reach_left %d reach_right %d\n", r, any_flag[r], own_flag[r], reach_l[r], reach_r[r]);
+    std::printf("compared_ranks %d\n", compared);
+    std::printf("per_step_mismatches_between_ranks %zu\n", per_ranks);
+    std::printf("per_step_mismatches_vs_unsharded %zu\n", per_ref);
+    std::printf("%s_mismatches %zu\n", model >= 0 ? "cdf" : "theta", aux_mism);
+    std::printf("seconds sharded %.3f unsharded %.3f\n", std::chrono::duration<double>(t_sharded - t_start).count(),
+                std::chrono::duration<double>(t_end - t_sharded).count());
     std::printf("particle_mismatches %zu\n", mism);
     return 0;
 }

@@ -5,6 +5,8 @@ import os
 import numpy as np
 import pytest
 
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
 
 # ---- Philox4x32-10: Random123 known-answer vectors -------------------------------------------------
 @pytest.mark.parametrize("ctr,key,exp", [
@@ -340,6 +342,73 @@ def test_oracle_full_series_golden(oracle, golden, spy):
         assert ll == golden[f"svol_{tname}_n500_full_ll"][0]
         np.testing.assert_array_equal(per, golden[f"svol_{tname}_n500_full_per"])
     assert len(spy) == 3084
+
+
+# ---- the long-series records (tests/golden/long_series_golden.npz; the device side is tests/test_long_series_gpu.py) ----
+LONG_IDS = ["G1", "G2", "G3", "G4", "G5", "G6", "G7", "L1", "L2", "L3"]
+LONG_KEYS = {"pf": ("kind", "model", "theta", "n", "filters", "seed", "resampler", "sched", "tile", "T", "per", "ll",
+                    "sha_x", "sample_x", "sha_cdf", "sample_cdf"),
+             "lw": ("kind", "model", "n", "filters", "seed", "delta", "form", "m_rs", "tile", "prior_lo", "prior_hi", "T", "per", "ll",
+                    "sha_x", "sample_x", "sha_theta", "sample_theta", "thetabar")}
+
+
+@pytest.fixture(scope="module")
+def long_records():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("make_golden_long", os.path.join(ROOT, "tests", "golden", "make_golden_long.py"))
+    mgl = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mgl)
+    with np.load(os.path.join(ROOT, "tests", "golden", "long_series_golden.npz")) as f:
+        rec = {k: f[k] for k in f.files}
+    cfg = lambda rid: {k[len(rid) + 1:]: (v.item() if v.ndim == 0 else v) for k, v in rec.items() if k.startswith(rid + "_")}
+    return mgl, rec, cfg
+
+
+def test_long_records_carry_every_key_the_gpu_module_reads(long_records):
+    mgl, rec, cfg = long_records
+    assert list(rec["ids"]) == LONG_IDS == list(mgl.RECORDS)
+    for rid in LONG_IDS:
+        c = cfg(rid)
+        assert set(c) == set(LONG_KEYS[c["kind"]]), rid
+        want = mgl.RECORDS[rid]
+        assert c["kind"] == want["kind"] and c["n"] == want["n"] and c["T"] == want["T"] and c["seed"] == want["seed"] and c["filters"] == 1
+        assert c["per"].shape == (c["T"],) and c["per"].dtype == np.float64 and np.isfinite(c["per"]).all() and np.isfinite(c["ll"])
+        assert abs(c["per"].sum() - c["ll"]) <= 1e-8 * abs(c["ll"])          # the stored sum is the oracle's own accumulation of these values
+        assert c["sample_x"].shape == (mgl.N_SAMPLE,) and len(c["sha_x"]) == 64
+        if c["kind"] == "pf":
+            assert c["tile"] == (want["tile"] or oracle_default_tile(c["n"])) and c["sample_cdf"].dtype == np.uint64 and len(c["sha_cdf"]) == 64
+        else:
+            assert c["sample_theta"].shape == (4, mgl.N_SAMPLE) and c["thetabar"].shape == (4,) and len(c["sha_theta"]) == 64
+    # the shapes the sharded cases compare with (tests/test_sharded_gpu.py) need 2048-particle tiles
+    assert all(cfg(r)["tile"] == 2048 for r in ("G1", "G2", "G5", "G6", "G7"))
+    assert cfg("G3")["tile"] == 1024 and cfg("G4")["tile"] == 512
+    for rid, want in mgl.CROSS_CHECK.items():                                 # sums recorded by earlier GPU builds (profiles/r03_*.txt)
+        assert float(cfg(rid)["ll"]) == want
+
+
+def oracle_default_tile(n):
+    from oracle import oracle as O
+    return O.default_tile(n)
+
+
+@pytest.mark.parametrize("rid", LONG_IDS)
+def test_oracle_reproduces_first_steps_of_long_records(oracle, long_records, rid):
+    """The first 8 steps of every record from today's oracle, bit for bit: a fixture left stale by an arithmetic change fails here,
+    without a GPU, and is not mistaken for a kernel bug."""
+    mgl, rec, cfg = long_records
+    c = cfg(rid)
+    _, _, per = mgl.run_oracle(c, 8)
+    np.testing.assert_array_equal(per.view(np.uint64), c["per"][:8].view(np.uint64))
+
+
+def test_oracle_reproduces_long_record_g4_completely(oracle, long_records):
+    """One record regenerated whole (G4: N = 300000, stratified, 512-particle tiles, T = 1000; about a minute of one core): per-step
+    values, sum and the final-state evidence exactly as make_golden_long.py stores them."""
+    mgl, rec, cfg = long_records
+    rid, new, _ = mgl.make_record("G4")
+    assert set(new) == {k for k in rec if k.startswith("G4_")}
+    for k, v in new.items():
+        assert v.dtype == rec[k].dtype and v.shape == rec[k].shape and v.tobytes() == rec[k].tobytes(), k
 
 
 # ---- Liu-West oracle (liu_west_filter.h:971-1159 restated; test_liu_west.cpp model) --------------------------------
