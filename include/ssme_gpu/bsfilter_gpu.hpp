@@ -141,7 +141,7 @@ private:
 // callbacks (example/univ_svol_bootstrap_filter.h:17-41); here the callbacks live in the header that was compiled into the library
 // this program links (build.build_user_model), and this class is the caller-visible rest: filter(y), getLogCondLike(), and
 // getExpectations() of ANY functions h(x) of the whole state, evaluated on the host over the downloaded particles and weights
-// (liu_west_filter.h:1662-1683).  dimx / dimy must be the model's (checked against ssme_pf_user_model_dims).
+// (liu_west_filter.h:1662-1683); functions the model's header itself declares are summed on the device: getModelExpectations().  dimx / dimy must be the model's (checked against ssme_pf_user_model_dims).
 template <std::size_t nparts, std::size_t dimx = 1, std::size_t dimy = 1, typename float_t = double>
 class user_bs_gpu {
 public:
@@ -180,6 +180,16 @@ public:
     }
     float_t getLogCondLike() const { return last_; }
     const std::vector<double>& getExpectations() const { return expectations_; }
+    // the n_h functionals the model's header declares (model_api.h: n_h, h) after the last filter(), summed ON THE DEVICE: one small
+    // download instead of filter(y, fs)'s (dimx + 1) * nparts doubles.  Throws what check throws (std::runtime_error) when the linked
+    // library declares none.
+    std::vector<double> getModelExpectations() const {
+        const int n = ssme_pf_user_model_n_h();
+        if (n < 1) check(SSME_ERR_UNSUPPORTED, h_.get());
+        std::vector<double> out((std::size_t)n);
+        check(ssme_pf_get_user_expectations(h_.get(), out.data()), h_.get());
+        return out;
+    }
     ssme_pf_handle native() const { return h_.get(); }
 
 private:

@@ -145,7 +145,9 @@ int ssme_pf_get_per_step(ssme_pf_handle h, double* out, int32_t T);
 int ssme_pf_get_loglik(ssme_pf_handle h, double* out);
 
 /* E[h(x_t) | y_{1:t}] with the pre-resampling weights of the last step
- * (getExpectations(); twin liu_west_filter.h:1662-1683).  out: R values. */
+ * (getExpectations(); twin liu_west_filter.h:1662-1683).  out: R values.  The built-in functionals see component 0 of a
+ * vector state: users of a vector model declare their functionals in the model header and call
+ * ssme_pf_get_user_expectations (below). */
 int ssme_pf_get_expectations(ssme_pf_handle h, int32_t functional, double* out);
 /* The same for n <= 4 built-in functionals at once (filter(y, z, fs) takes a VECTOR of functions, pswarm_filter.h:87):
  * one pass over the particles, one download.  out[i*R + r] = E[h_i] of filter r. */
@@ -161,6 +163,19 @@ int ssme_pf_swarm_aggregate(ssme_pf_handle h, const int32_t* functionals, int32_
  * fewer counts each of its members more).  num_threads <= 0 or >= R: ssme_pf_swarm_aggregate's plain mean / one member per thread. */
 int ssme_pf_swarm_aggregate_threads(ssme_pf_handle h, const int32_t* functionals, int32_t n, int32_t num_threads,
                                     double* mean_logcondlike /*1*/, double* mean_expectations /*n*/);
+/* Functionals of the user model's own (SSME_MODEL_USER0 whose header declares n_h and h, ssme_amd/csrc/model_api.h): functions
+ * h(x, z, theta) of the WHOLE state, compiled into an expectation kernel.  ssme_pf_user_model_n_h: their number, 0 for the stock
+ * library and for a user model without functionals; needs no device.
+ * ssme_pf_get_user_expectations: out[k*R + r] = E[h_k(x_t) | y_{1:t}] of filter r with the weights ssme_pf_get_expectations uses
+ * (any resamp_sched); z is the covariate of the handle's last step (0 if it had none).  One pass over the particles, one download
+ * of n_h * R doubles -- no ssme_pf_download_weights per filter.  ssme_pf_swarm_aggregate_user: the means over the R members of the
+ * last log conditional likelihoods and of the n_h expectations, as ssme_pf_swarm_aggregate_threads forms them (num_threads <= 0:
+ * plain means); one download of n_h + 1 doubles.  Both: SSME_ERR_UNSUPPORTED when n_h == 0 or the handle's model is not
+ * SSME_MODEL_USER0, SSME_ERR_STATE before the first step and on sharded handles; ordered behind steps queued on the handle's
+ * stream (ssme_pf_step with logcondlike_out = NULL); SSME_F32 handles round the results to float. */
+int ssme_pf_user_model_n_h(void);
+int ssme_pf_get_user_expectations(ssme_pf_handle h, double* out /* [n_h][R] */);
+int ssme_pf_swarm_aggregate_user(ssme_pf_handle h, int32_t num_threads, double* mean_logcondlike /*1*/, double* mean_expectations /*n_h*/);
 /* Arbitrary host-side h (the reference's filt_func is a std::function, pswarm_filter.h:44,87-89): particles x (N,
  * nullable) and weights w (N) of one filter after the last step, w_j = exp(logw_j - max logw) in the 2^-41 fixed point
  * the resampler and ssme_pf_get_expectations use; the caller forms sum h(x_j) w_j / sum w_j.  Needs no debug mode. */

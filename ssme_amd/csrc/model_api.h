@@ -37,6 +37,20 @@
 // component d >= 1 comes from one more Philox call per particle pair (counter stream STREAM_XDIM + d).  Such a model runs on the
 // tiled step kernel at every N (no whole-series kernel), unsharded; device functionals see component 0.
 // tests/models/svol_two_factor.h is the test model (two volatility factors, two observed series).
+//
+// FUNCTIONALS of the model's own (optional; getExpectations() of the functions h the reference's callers pass to filter(y[, z], fs),
+// pswarm_filter.h:47,340: h(x, z, theta)).  Host std::functions cannot run per particle either, so the header may declare
+//     static constexpr int n_h = K;                                // 1 .. 16 scalar outputs: a mean vector, the entries of a moment matrix, ...
+//     static __device__ __forceinline__ void h(const ssme::ModelConst& c, const double* x /*dim_x*/, double zcov,
+//                                              const ssme::ExpTabEntry* etab, double* out /*n_h*/);
+// and they are compiled into an expectation kernel of their own (user_expect.h): E[h_k(x_t) | y_{1:t}] for all K outputs in one pass
+// over the particles, with the weights the built-in functionals and the resampler use.  x is the WHOLE state of one particle (a scalar
+// model gets x[0]), zcov the covariate of the last step (as for prop; 0 when the step had none), theta reaches h through c, and etab is
+// what logg receives (dexp_scaled_t(v, 0, etab)).  The same rule holds as for the callbacks: only + - * fma and the functions of
+// ssme_math.h, written so that out[] and x[] stay in registers (constant indices; the build refuses kernels that use scratch memory).
+// Callers: ssme_pf_user_model_n_h / ssme_pf_get_user_expectations / ssme_pf_swarm_aggregate_user (include/ssme_pf.h),
+// user_bs_gpu::getModelExpectations (bsfilter_gpu.hpp), ParticleFilterBank.user_expectations / swarm_aggregate_user.  A header
+// without n_h compiles and behaves as before (n_h reads 0).  tests/models/svol_two_factor_h.h declares seven of them.
 #pragma once
 #include <type_traits>
 #include "ssme_math.h"
@@ -68,6 +82,13 @@ template <class M, class = void> struct user_dims { static constexpr int dx = 1,
 template <class M> struct user_dims<M, std::void_t<decltype(M::dim_x), decltype(M::dim_y)>> {
     static constexpr int dx = M::dim_x, dy = M::dim_y;
     static_assert(dx >= 1 && dx <= kMaxDim && dy >= 1 && dy <= kMaxDim, "dim_x and dim_y of a user model: 1 .. 4");
+};
+// number of functionals a user model declares (n_h and h above): 0 for a header without them
+constexpr int kMaxUserFunctionals = 16;
+template <class M, class = void> struct user_nh { static constexpr int n = 0; };
+template <class M> struct user_nh<M, std::void_t<decltype(M::n_h)>> {
+    static constexpr int n = M::n_h;
+    static_assert(n >= 1 && n <= kMaxUserFunctionals, "n_h of a user model: 1 .. 16");
 };
 // what the kernels call: a scalar model through its prop / logg, a vector model through its *_vec functions (the other set is a
 // stub that no launch reaches: vector models never run the scalar kernels and the other way round)

@@ -5,6 +5,7 @@
 #include "pf_kernels.h"
 #include "lw_kernels.h"
 #include "pf_small.h"
+#include "user_expect.h"
 #include "handle_core.h"
 #include "shard_driver.h"
 
@@ -50,6 +51,8 @@ struct ssme_pf_s : HandleCore {
     double *logw, *scratchR;
     double *exp_part, *exp_out;  // expectations: [R][Bs][4] per-tile numerators; [5][R] per-filter values + [5] means over filters
     double* wscratch;            // [Npad] weights of one filter (host-side functionals), allocated on first use
+    double *uexp_part, *uexp_out;    // the user model's own functionals (user_expect.h): [R][Bs][n_h] per-tile numerators, [n_h][R] values; allocated on first use
+    double last_z;               // covariate of the last step (0 when it had none): what the user model's h receives
     double *gam, *pgam, *gtot;   // Gamma tables of the multinomial resampler, gcap time rows
     uint32_t* anc;
     FilterScalars* scal;
@@ -449,9 +452,44 @@ static int do_reset(ssme_pf_handle h) {
     return SSME_OK;
 }
 
+// ---- the user model's own functionals (model_api.h: n_h, h; kernels in user_expect.h) -----------------------------------------
+// per-filter expectations of all n_h functionals into uexp_out ([n_h][R], device); two launches, no sync
+template <class M>
+static int enqueue_user_expectations(ssme_pf_handle h) {
+    constexpr int NH = user_nh<M>::n;
+    if constexpr (NH > 0) {
+        if (!h->uexp_part) {
+            HIPCHK(own_alloc(h, h->uexp_part, sizeof(double) * (size_t)h->R * h->Bs * NH));
+            HIPCHK(own_alloc(h, h->uexp_out, sizeof(double) * (size_t)NH * h->R));
+        }
+        hipLaunchKernelGGL(k_user_expect_partials<M>, dim3(h->B, h->R), dim3(kThreads), 0, h->stream, (const double*)h->x[h->cur],
+                           (size_t)h->R * h->Npad, (const double*)h->cdf[h->cur], (const ModelConst*)h->mc, h->last_z, h->N, h->Npad, h->Bs,
+                           h->tile, h->uexp_part);
+        hipLaunchKernelGGL(k_user_expect_final<NH>, dim3(h->R), dim3(kThreads), 0, h->stream, (const double*)h->uexp_part,
+                           (const double*)h->tsum[h->cur], (const double*)h->tmax[h->cur], h->B, h->Bs, h->R, h->uexp_out);
+        HIPCHK(hipGetLastError());
+        return SSME_OK;
+    } else {
+        return SSME_ERR_UNSUPPORTED;
+    }
+}
+
+// what both entry points check first; SSME_OK: the expectations are queued on the handle's stream
+static int user_expectations_checked(ssme_pf_handle h) {
+#if SSME_HAS_USER_MODEL
+    if (user_nh<ssme_user_model0>::n == 0 || h->cfg.model != SSME_MODEL_USER0) return SSME_ERR_UNSUPPORTED;
+    if (h->shard_world > 0) return SSME_ERR_STATE;
+    if (h->t < 1) return SSME_ERR_STATE;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    return enqueue_user_expectations<ssme_user_model0>(h);
+#else
+    return SSME_ERR_UNSUPPORTED;
+#endif
+}
+
 extern "C" {
 
-int ssme_pf_version(void) { return 332; }
+int ssme_pf_version(void) { return 333; }
 
 const char* ssme_pf_strerror(int s) {
     switch (s) {
@@ -532,7 +570,7 @@ static int create_impl(const ssme_pf_config* cfg, int shard_rank, int shard_worl
         HIPCHK(own_alloc(h, h->yz_step, sizeof(double) * 2));
         HIPCHK(own_alloc(h, h->ticket, sizeof(int32_t) * h->R, Mem::zeroed));
         HIPCHK(own_alloc(h, h->l2_ticket, sizeof(int32_t) * h->R, Mem::zeroed));
-        HIPCHK(own_alloc(h, h->pin, sizeof(double) * (2 + (size_t)h->R + 64 + 8), Mem::pinned));   // + 128 ints for the shard plan + 8 swarm aggregates
+        HIPCHK(own_alloc(h, h->pin, sizeof(double) * (2 + (size_t)h->R + 64 + 8 + kMaxUserFunctionals + 1), Mem::pinned));   // + 128 ints for the shard plan + 8 swarm aggregates + 17 of the user model's functionals
         HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->pin_dev), h->pin, 0));
         rc2 = upload_key(h);
         if (rc2 != SSME_OK) return rc2;
@@ -572,6 +610,13 @@ int ssme_pf_user_model_dims(int32_t* dim_x, int32_t* dim_y) {
 #else
     *dim_x = 0; *dim_y = 0;
     return SSME_ERR_UNSUPPORTED;
+#endif
+}
+int ssme_pf_user_model_n_h(void) {
+#if SSME_HAS_USER_MODEL
+    return user_nh<ssme_user_model0>::n;
+#else
+    return 0;
 #endif
 }
 int ssme_pf_default_tile(int32_t n_particles, int32_t bank_filters) { return default_tile(n_particles, bank_filters < 1 ? 1 : bank_filters); }
@@ -969,6 +1014,7 @@ int ssme_pf_step(ssme_pf_handle h, const double* y, const double* z, double* out
     h->pin[0] = *y; h->pin[1] = z ? *z : 0.0;
     for (int d = 1; d < h->dy; ++d) h->y_step_v[d - 1] = y[d];
     if (h->cfg.dtype == SSME_F32) { h->pin[0] = f32r(h->pin[0]); h->pin[1] = f32r(h->pin[1]); }
+    h->last_z = h->pin[1];
     const int gi = h->cfg.resampler == SSME_RESAMP_MULTINOMIAL ? step_gamma_row(h, launch_gamma) : 0;
     // out == NULL (the swarm classes: the aggregation that follows hands the data back): the step is only queued -- no result
     // slots, no wait; anything that reads the handle afterwards is ordered behind it on the stream
@@ -1007,6 +1053,7 @@ int ssme_pf_run_series(ssme_pf_handle h, const double* y, const double* z, int32
     }
     HIPCHK(hipMemcpyAsync(h->ybuf, y, sizeof(double) * T * h->dy, hipMemcpyHostToDevice, h->stream));
     if (z) HIPCHK(hipMemcpyAsync(h->zbuf, z, sizeof(double) * T, hipMemcpyHostToDevice, h->stream));
+    h->last_z = z ? z[T - 1] : 0.0;
     if (h->cfg.dtype == SSME_F32) HIPCHK(hipStreamSynchronize(h->stream));      // the staging vectors go out of scope
     rc = do_reset(h);
     if (rc != SSME_OK) return rc;
@@ -1145,6 +1192,40 @@ int ssme_pf_swarm_aggregate_threads(ssme_pf_handle h, const int32_t* functionals
     return SSME_OK;
 }
 
+// ---- the user model's own functionals: entry points (the launches: enqueue_user_expectations, above) ----
+int ssme_pf_get_user_expectations(ssme_pf_handle h, double* out) {
+    if (!h || !out) return SSME_ERR_INVALID_ARG;
+    const int rc = user_expectations_checked(h);
+    if (rc != SSME_OK) return rc;
+    const size_t n = (size_t)ssme_pf_user_model_n_h() * h->R;
+    HIPCHK(hipMemcpyAsync(out, h->uexp_out, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    round_out(h, out, n);
+    return SSME_OK;
+}
+
+// ssme_pf_swarm_aggregate_threads for the user model's functionals: the same launch of k_swarm_means over n_h rows, its n_h + 1
+// means written into mapped host memory (slots of their own behind the built-ins')
+int ssme_pf_swarm_aggregate_user(ssme_pf_handle h, int32_t num_threads, double* mean_logcondlike, double* mean_expectations) {
+    if (!h || !mean_logcondlike || !mean_expectations) return SSME_ERR_INVALID_ARG;
+    const int rc = user_expectations_checked(h);
+    if (rc != SSME_OK) return rc;
+    const int n = ssme_pf_user_model_n_h();
+    const size_t slot0 = 2 + (size_t)h->R + 64 + 8;
+    double* pin = h->pin + slot0;
+    mark_results_pending(pin, kMaxUserFunctionals + 1);
+    hipLaunchKernelGGL(k_swarm_means, dim3(n + 1), dim3(kThreads), 0, h->stream, (const double*)h->uexp_out, (const FilterScalars*)h->scal,
+                       h->R, n, kMaxUserFunctionals, h->pin_dev + slot0, (int)num_threads);
+    HIPCHK(hipGetLastError());
+    HIPCHK(wait_results(h->stream, pin + kMaxUserFunctionals, 1));
+    HIPCHK(wait_results(h->stream, pin, n));
+    *mean_logcondlike = pin[kMaxUserFunctionals];
+    for (int i = 0; i < n; ++i) mean_expectations[i] = pin[i];
+    round_out(h, mean_logcondlike, 1);
+    round_out(h, mean_expectations, (size_t)n);
+    return SSME_OK;
+}
+
 // Particles and normalisable weights of one filter after the last step, for functionals that cannot run on the device
 // (arbitrary std::function h, pswarm_filter.h:44): w_j = exp(logw_j - max logw) up to the 2^-41 fixed point -- the same
 // weights the device expectations and the resampler use.  No debug mode needed (the weights are rebuilt from the cdf).
@@ -1232,6 +1313,7 @@ int ssme_pf_profile_series(ssme_pf_handle h, const double* y, const double* z, i
     if (z) HIPCHK(hipMemcpyAsync(h->zbuf, z, sizeof(double) * T, hipMemcpyHostToDevice, h->stream));
     rc = do_reset(h);
     if (rc != SSME_OK) return rc;
+    h->last_z = z ? z[T - 1] : 0.0;
     // one event every kGroup launches: an event pair around a single 20-us kernel adds ~3 us of its own
     const int kGroup = 32;
     const int nev = (T + kGroup - 1) / kGroup + 1;

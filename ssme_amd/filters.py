@@ -161,6 +161,21 @@ class ParticleFilterBank:
                                                              capi.dptr(ll), capi.dptr(ex)))
         return float(ll[0]), ex[:fs.size].tolist()
 
+    def user_expectations(self):
+        """E[h_k] of every filter for the n_h functionals the user model's header declares (csrc/model_api.h: n_h, h), functions
+        of the whole state and the last step's covariate, in one device pass: [n_h, R].  Raises SsmeError (unsupported) when the
+        loaded library has none."""
+        out = np.empty((max(int(capi.lib().ssme_pf_user_model_n_h()), 1), self.r))
+        self._chk(capi.lib().ssme_pf_get_user_expectations(self._h, capi.dptr(out)))
+        return out
+
+    def swarm_aggregate_user(self, num_threads=0):
+        """swarm_aggregate for the user model's own functionals: (mean over filters of the last log conditional likelihoods,
+        mean_exp[n_h]) reduced on the device; num_threads as in swarm_aggregate."""
+        ll, ex = np.empty(1), np.empty(max(int(capi.lib().ssme_pf_user_model_n_h()), 1))
+        self._chk(capi.lib().ssme_pf_swarm_aggregate_user(self._h, int(num_threads), capi.dptr(ll), capi.dptr(ex)))
+        return float(ll[0]), ex
+
     def weights(self, f=0):
         """(x, w) of filter f after the last step for host-side functionals: w = exp(logw - max logw); x: [dim_x, N] for a vector model."""
         dx = self._dims()[0]
