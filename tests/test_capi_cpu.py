@@ -179,3 +179,18 @@ def test_mock_rccl_and_thread_harness_compile():
     subprocess.check_call(["/opt/rocm/bin/hipcc", "-std=c++17", "-O1", "-fPIC", "-shared", "-Wno-unused-result", os.path.join(cpp, "mock_rccl.cpp"), "-o", mock])
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-pthread", os.path.join(cpp, "test_shard_threads.cpp"), "-o", os.path.join(cpp, "test_shard_threads"),
                            "-Wl,--no-as-needed", mock, "-Wl,--as-needed", so, "-Wl,-rpath," + cpp, "-Wl,-rpath," + os.path.dirname(so)])
+
+
+def test_user_model_at_the_documented_maxima_builds():
+    """tests/models/lin_gauss_4d_h.h: dim_x = dim_y = 4 and n_h = 16, the top of the range ssme_amd/csrc/model_api.h documents.  The library
+    builds and passes the build's own per-kernel check (no scratch, no vector spills: build._compile raises otherwise), and reports its
+    theta length, dimensions and number of functionals."""
+    from ssme_amd import build, _capi
+    so = build.build_user_model(os.path.join(ROOT, "tests", "models", "lin_gauss_4d_h.h"), "lin_gauss_4d_h")
+    L = C.CDLL(so)
+    for n in _header_functions():
+        assert hasattr(L, n)
+    dx, dy = C.c_int32(-1), C.c_int32(-1)
+    assert L.ssme_pf_user_model_n_theta() == 6
+    assert L.ssme_pf_user_model_dims(C.byref(dx), C.byref(dy)) == _capi.OK and (dx.value, dy.value) == (4, 4)
+    assert L.ssme_pf_user_model_n_h() == 16

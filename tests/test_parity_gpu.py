@@ -12,6 +12,8 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
+from oracle_models import _student_t_oracle, _two_factor_oracle  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
 TOL_LL = 1e-9
@@ -309,23 +311,6 @@ def test_a_filter_does_not_depend_on_how_its_bank_is_split(sa, oracle, spy):
     alone.close()
 
 
-def _student_t_oracle(oracle, n, seed, rep, resampler, tile, th=(1.1, 0.95, 0.25, 7.0)):
-    """tests/models/svol_student_t.h restated with the oracle's own libm-free functions (the operation order is the header's)."""
-    import ctypes, math
-    libm = ctypes.CDLL("libm.so.6")               # the header's std::lgamma is libm's (CPython's math.lgamma is its own code)
-    libm.lgamma.restype = ctypes.c_double
-    libm.lgamma.argtypes = [ctypes.c_double]
-    beta, phi, sigma, nu = th
-    e1 = lambda f, v: float(f(np.array([v]))[0])
-    a2 = sigma / math.sqrt(1.0 - phi * phi)
-    a3 = ((libm.lgamma(0.5 * (nu + 1.0)) - libm.lgamma(0.5 * nu)) - 0.5 * e1(oracle.log, nu * math.pi)) - e1(oracle.log, beta)
-    a4 = 1.0 / (nu * (beta * beta))
-    a5 = 0.5 * (nu + 1.0)
-    prop = lambda x, zn, zcov: phi * x + zn * sigma
-    logg = lambda y, x: (a3 - 0.5 * x) - a5 * e1(oracle.log, 1.0 + ((y * y) * a4) * e1(oracle.exp_t, -x))
-    return oracle.UserModelFilter(n, seed, a2, prop, logg, rep=rep, resampler=resampler, tile=tile)
-
-
 @pytest.mark.parametrize("n,rs,tile", [(1500, 0, 2048), (6000, 0, 512), (6000, 1, 2048)])
 def test_user_model_extension_point_bit_exact_vs_oracle(sa, oracle, spy, tmp_path, n, rs, tile):
     """a FOURTH model (SVOL with Student-t observations, tests/models/svol_student_t.h) compiled in through the
@@ -357,25 +342,6 @@ def test_user_model_extension_point_bit_exact_vs_oracle(sa, oracle, spy, tmp_pat
         ll, per = _student_t_oracle(oracle, n, seed, rep, rs, tile).run_series(spy[:T])
         assert r["series"][rep] == ll
         assert_bits_equal(r["per_step"][rep], per, "user model: series per-step")
-
-
-def _two_factor_oracle(oracle, n, seed, rep, resampler, tile, sched, th=(1.1, 0.95, 0.9, 0.2, 0.15, -0.4)):
-    """tests/models/svol_two_factor.h (dim_x = 2, dim_y = 2) restated with the oracle's own functions, in the header's operation order."""
-    import math
-    beta, phi1, phi2, s1, s2, rho = th
-    e1 = lambda f, v: float(f(np.array([v]))[0])
-    a2, a3, a4 = s1, s2 * rho, s2 * math.sqrt(1.0 - rho * rho)
-    a5, a6 = e1(oracle.log, beta), 1.0 / (beta * beta)
-    half_log_2pi = 0.91893853320467274178
-    init = lambda zn: np.array([zn[0] * a2, zn[1] * a4])
-    prop = lambda x, zn, zcov: np.array([phi1 * x[0] + zn[0] * a2, (phi2 * x[1] + zn[0] * a3) + zn[1] * a4])
-
-    def logg(y, x):
-        u1, u2 = x[0] + x[1], x[1]
-        l1 = (-(a5 + 0.5 * u1) - half_log_2pi) - 0.5 * (((y[0] * y[0]) * a6) * e1(oracle.exp_t, -u1))
-        l2 = (-(a5 + 0.5 * u2) - half_log_2pi) - 0.5 * (((y[1] * y[1]) * a6) * e1(oracle.exp_t, -u2))
-        return l1 + l2
-    return oracle.UserVectorModelFilter(n, seed, 2, 2, init, prop, logg, rep=rep, resampler=resampler, resamp_sched=sched, tile=tile)
 
 
 @pytest.mark.parametrize("n,rs,tile,sched", [(1500, 0, 2048, 1), (6000, 0, 512, 1), (6000, 1, 2048, 1), (5000, 0, 1024, 2), (3 * 2048 + 77, 3, 2048, 1)])

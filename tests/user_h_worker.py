@@ -74,6 +74,33 @@ elif mode == "vector":
             bank.run_series(ys)
             res["ue_series_noz_" + key] = bank.user_expectations()
             bank.close()
+elif mode == "exact":
+    # every case of expect_cases.USER_CASES: state and expectations for tests/test_expectations_gpu.py (no debug mode)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import expect_cases as ec
+    assert L.ssme_pf_user_model_n_h() == 7
+    for case in ec.USER_CASES:
+        y, zs = ec.user_observations(case)
+        bank = ssme_amd.ParticleFilterBank(ssme_amd.MODEL_USER0, case["n"], 1, 21, 0, case["sched"], tile=case["tile"])
+        bank.set_params(TH_2F)
+        res["lls_" + case["name"]] = np.array([bank.step(y[t], zs[t])[0] for t in range(case["T"])])
+        res["ue_" + case["name"]] = bank.user_expectations()
+        g = bank.state(0, logw=False)
+        for k in ("x", "cdf", "A", "mb"):
+            res[k + "_" + case["name"]] = g[k]
+        bank.close()
+elif mode == "swarm_big":
+    # more members than k_swarm_means has threads: R = 300 and 513, every num_threads the bootstrap test uses
+    for R in (300, 513):
+        bank = ssme_amd.ParticleFilterBank(ssme_amd.MODEL_USER0, 600, R, 3)
+        bank.set_params(two_factor_thetas(R))
+        for t in range(3):
+            lcl = bank.step(y2(t), 0.1 * (t + 1))
+        res[f"lcl_{R}"], res[f"ue_{R}"] = lcl, bank.user_expectations()
+        for nt in (0, 7, 256, 299, R, R + 5):
+            ll, ex = bank.swarm_aggregate_user(nt)
+            res[f"ll_{R}_{nt}"], res[f"ex_{R}_{nt}"] = np.array([ll]), ex
+        bank.close()
 elif mode == "determinism":
     n, R = 40000, 3
     th = two_factor_thetas(R)
