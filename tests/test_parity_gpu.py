@@ -588,10 +588,16 @@ def test_reference_style_interface(sa, oracle, spy):
 def test_degenerate_inputs(sa, oracle):
     for th in ([-1.0, 0.5, 0.1], [1.0, 1.5, 0.1]):
         bank = sa.ParticleFilterBank(sa.MODEL_SVOL, 300, 1, 1)
+        bank.set_debug(True)
         bank.set_params(th)
-        assert np.isnan(bank.step(0.3)[0])
-        assert np.isnan(bank.step(0.1)[0])          # the search must not hang or fault on NaN weights
-        bank.close()
+        of = oracle.Filter(oracle.MODEL_SVOL, 300, th, 1)
+        for y in (0.3, 0.1):                        # the search must not hang or fault on NaN weights
+            lg, lo = bank.step(y)[0], of.step(y)
+            assert np.isnan(lg) and np.isnan(lo)
+            g, o = _compare_state(bank, of, f"theta={th} y={y}")          # NaN for NaN, every other value to the bit
+            if y == 0.1:
+                np.testing.assert_array_equal(g["anc"], o["anc"])
+        bank.close()                                # every route and resampler: test_bootstrap_edges_gpu.py (bad-theta-*, bad-row)
     bank = sa.ParticleFilterBank(sa.MODEL_SVOL, 300, 1, 1)
     bank.set_params([1.0, 0.5, 0.1])
     of = oracle.Filter(oracle.MODEL_SVOL, 300, [1.0, 0.5, 0.1], 1)
