@@ -1,7 +1,8 @@
 """Worker of tests/test_sharded_gpu.py: one rank of a particle-sharded filter (gloo rehearsal: every rank uses cuda:0).
 
-usage: shard_worker.py RANK WORLD PORT OUT.npz MODEL N T RESAMPLER SEED [RESAMP_SCHED]
-"""
+usage: shard_worker.py RANK WORLD PORT OUT.npz MODEL N T RESAMPLER SEED [RESAMP_SCHED [YSET ZSET THETA]]
+YSET / ZSET: "t:value,..." overwrite single observations / covariates after z was taken as the lag of y; THETA: "a,b,c[,d]"; "-": none
+(tests/shard_edge_cases.py: apply_overrides)."""
 import os
 import sys
 
@@ -24,6 +25,13 @@ def main():
     z = np.concatenate([[0.0], y[:-1]]) if model == 1 else None
     th = {0: [1.0, 0.95, 0.25], 1: [0.9, 0.0, 1.0, -0.1], 2: [0.9, 0.5, 0.7]}[model]
     sched = int(sys.argv[10]) if len(sys.argv) > 10 else 1
+    if len(sys.argv) > 11:
+        from shard_edge_cases import apply_overrides
+        if z is not None:
+            apply_overrides(z, sys.argv[12] if len(sys.argv) > 12 else None)
+        apply_overrides(y, sys.argv[11])
+        if len(sys.argv) > 13 and sys.argv[13] != "-":
+            th = [float(v) for v in sys.argv[13].split(",")]
     f = ShardedParticleFilter(model, n, seed=seed, resampler=rs, resamp_sched=sched)
     f.set_params(th)
     f.record_ancestors(True)

@@ -1,7 +1,8 @@
 """Worker of tests/test_sharded_gpu.py: one rank of a particle-sharded Liu-West filter (gloo rehearsal on cuda:0).
 
-usage: shard_worker_lw.py RANK WORLD PORT OUT.npz N T SEED DELTA [FORM [RS]]
-"""
+usage: shard_worker_lw.py RANK WORLD PORT OUT.npz N T SEED DELTA [FORM [RS [YSET ZSET YSCALE]]]
+YSCALE multiplies the observations before z is taken as their lag; then YSET / ZSET ("t:value,...", "-": none) overwrite single
+observations / covariates (tests/shard_edge_cases.py: apply_overrides)."""
 import os
 import sys
 
@@ -21,7 +22,13 @@ def main():
     torch.cuda.set_device(0)
     from ssme_amd.sharded import ShardedLiuWest
     y = np.loadtxt(os.path.join(ROOT, "tests", "golden", "spy_returns.csv"))[:T]
+    if len(sys.argv) > 13:
+        y = y * float(sys.argv[13])
     z = np.concatenate([[0.0], y[:-1]])
+    if len(sys.argv) > 11:
+        from shard_edge_cases import apply_overrides
+        apply_overrides(z, sys.argv[12] if len(sys.argv) > 12 else None)
+        apply_overrides(y, sys.argv[11])
     form = int(sys.argv[9]) if len(sys.argv) > 9 else 0
     rs = int(sys.argv[10]) if len(sys.argv) > 10 else 1
     f = ShardedLiuWest(delta, 0.8, 0.99, -0.1, 0.1, 0.01, 0.1, -0.5, -0.01, nparts=n, seed=seed, form=form, rs=rs)

@@ -163,6 +163,33 @@ def test_shard_and_liu_west_entry_points_validate_arguments():
     assert not h.value
 
 
+def test_shard_create_refuses_a_layout_with_an_empty_rank_on_every_rank():
+    """Five tiles over four ranks: Bl = ceil(5 / 4) = 2, so ranks 0-2 would own 2 + 2 + 1 tiles and rank 3 none.  EVERY rank's create
+    must refuse (a rank that went ahead would wait in its first collective for one that never comes), before any HIP call; one particle
+    more than four tiles is the same layout (the fifth tile holds one particle), three ranks are accepted by the argument checks."""
+    from ssme_amd import _capi
+    L = _capi.lib()
+    lw = _capi.LwConfig(n_particles=5 * 2048, n_filters=1, seed=1, device=0, first_filter_id=0, delta=0.99)
+    lw.transforms[:] = [2, 0, 3, 1]
+    lw.prior_lo[:] = [0.8, -0.1, 0.01, -0.5]
+    lw.prior_hi[:] = [0.99, 0.1, 0.1, -0.01]
+    for n in (5 * 2048, 4 * 2048 + 1):
+        cfg = _capi.Config(model=0, n_particles=n, n_filters=1, dtype=0, resampler=0, resamp_sched=1, seed=1, device=0, first_filter_id=0)
+        lw.n_particles = n
+        for rank in range(4):
+            h = C.c_void_p()
+            assert L.ssme_pf_shard_create(C.byref(cfg), rank, 4, C.byref(h)) == _capi.ERR_UNSUPPORTED, rank
+            assert not h.value
+            assert L.ssme_lw_shard_create(C.byref(lw), rank, 4, C.byref(h)) == _capi.ERR_UNSUPPORTED, rank
+            assert not h.value
+        for rank in range(3):                              # 2 + 2 + 1: past the argument checks (no device: the first HIP call fails)
+            h = C.c_void_p()
+            rc = L.ssme_pf_shard_create(C.byref(cfg), rank, 3, C.byref(h))
+            assert rc in (_capi.OK, _capi.ERR_HIP)
+            if rc == _capi.OK:
+                L.ssme_pf_destroy(h)
+
+
 def test_sharded_python_class_requires_process_group():
     from ssme_amd.sharded import ShardedParticleFilter
     with pytest.raises(AssertionError):
