@@ -348,6 +348,35 @@ public:
         x.resize(nparts_); w.resize(nparts_);
         check(ssme_pf_download_weights(h_.get(), (int32_t)i, x.data(), w.data()), h_.get());
     }
+    // sim_future_obs(num_steps) of member i (pswarm_filter.h:247-253, 547-553 call it on every member), which has seen
+    // `member_steps` observations: the first member that asks after an observation forecasts ALL members in one device call
+    // (ssme_pf_sim_future_obs); the others take their slice.  A member that is behind the swarm is refused, as download() refuses it:
+    // the handle's weights are those of the swarm's last observation, not the member's.  The cache key (steps, H, last_obs) is
+    // complete: members and parameters cannot change after the first filter() call, and a forecast is a function of the origin alone.
+    // The host copy is released once every member has taken its slice.  Returns y[time][particle] of the member;
+    // last_obs = the last observation (read by the leverage model only).
+    std::vector<double> sim_future_obs(unsigned i, unsigned long member_steps, unsigned num_steps, double last_obs) {
+        std::lock_guard<std::mutex> lk(mu_);
+        if (!h_) throw std::runtime_error("swarm_context: sim_future_obs before the first filter() call");
+        if (i >= n_members_) throw std::invalid_argument("swarm_context: no such member");
+        if (member_steps != steps_) throw std::runtime_error("swarm_context: the swarm has moved on; this member cannot forecast from its own origin");
+        if (fc_y_.empty() || fc_steps_ != steps_ || fc_H_ != num_steps || fc_last_ != last_obs) {
+            const std::vector<double> lo(n_members_, last_obs);
+            fc_y_.assign(n_members_ * (std::size_t)num_steps * nparts_, 0.0);
+            fc_taken_.assign(n_members_, 0);
+            const int rc = ssme_pf_sim_future_obs(h_.get(), (int32_t)num_steps, lo.data(), fc_y_.data(), nullptr, nullptr);
+            if (rc != SSME_OK) fc_y_.clear();
+            check(rc, h_.get());
+            fc_steps_ = steps_; fc_H_ = num_steps; fc_last_ = last_obs;
+        }
+        const std::size_t per = (std::size_t)num_steps * nparts_;
+        std::vector<double> y(fc_y_.begin() + (std::ptrdiff_t)(i * per), fc_y_.begin() + (std::ptrdiff_t)((i + 1) * per));
+        fc_taken_[i] = 1;
+        bool all = true;
+        for (char t : fc_taken_) all = all && t;
+        if (all) { fc_y_.clear(); fc_y_.shrink_to_fit(); }          // everybody is served: a later call forecasts again (the same bits)
+        return y;
+    }
     std::size_t nparts() const { return nparts_; }
     std::size_t members() const { return n_members_; }
     bool probe() const { return opt_.probe_functionals; }
@@ -374,6 +403,11 @@ private:
     unsigned long steps_ = 0;
     double y_ = 0.0, z_ = 0.0;
     bool has_z_ = false;
+    std::vector<double> fc_y_;            // the last forecast of all members: [member][time][particle], until every member has its slice
+    std::vector<char> fc_taken_;          // which members have taken theirs
+    unsigned long fc_steps_ = 0;
+    unsigned fc_H_ = 0;
+    double fc_last_ = 0.0;
 };
 
 namespace detail {
@@ -421,6 +455,14 @@ public:
         check(ssme_pf_step(h_.get(), &y, z, &out), h_.get());
         last_ = (float_t)out;
         expectations_ = functional_engine<float_t, Mat, Ssv>::expectations(h_.get(), hs, nparts, probe_, declared_);
+    }
+    // y[time][particle] of this member (ssme_pf_sim_future_obs; in a swarm_context one device call serves all members)
+    std::vector<double> sim_future_obs(unsigned num_steps, double last_obs) {
+        if (ctx_) return ctx_->sim_future_obs(idx_, steps_, num_steps, last_obs);
+        if (!h_) throw std::runtime_error("model not constructed");
+        std::vector<double> y((std::size_t)num_steps * nparts);
+        check(ssme_pf_sim_future_obs(h_.get(), (int32_t)num_steps, &last_obs, y.data(), nullptr, nullptr), h_.get());
+        return y;
     }
     float_t last() const { return last_; }
     const std::vector<Mat>& expectations() const { return expectations_; }
@@ -471,6 +513,9 @@ public:
     }
     float_t getLogCondLike() const { return core_.last(); }
     std::vector<Mat> getExpectations() const { return core_.expectations(); }   // E[h(x_t) | y_{1:t}], pre-resampling weights
+    // sim_future_obs(num_future_steps) of the model's GenFutureSimulator add-on (test/test_pswarm.cpp:64-67, 112-116), on the
+    // device: y[time][particle], row-major.  last_obs = the last observation, the covariate of the first future step.
+    std::vector<double> sim_future_obs(unsigned num_future_steps, double last_obs = 0.0) { return core_.sim_future_obs(num_future_steps, last_obs); }
     ssme_pf_handle native() const { return core_.native(); }
 
 private:
@@ -498,6 +543,8 @@ public:
     void filter(const Osv& yt, const std::vector<func>& fs = std::vector<func>()) { core_.step((double)yt(0), nullptr, fs); }
     float_t getLogCondLike() const { return core_.last(); }
     std::vector<Mat> getExpectations() const { return core_.expectations(); }
+    // sim_future_obs(num_future_steps): y[time][particle], row-major (ssme_pf_sim_future_obs; the model reads no last observation)
+    std::vector<double> sim_future_obs(unsigned num_future_steps, double last_obs = 0.0) { return core_.sim_future_obs(num_future_steps, last_obs); }
     ssme_pf_handle native() const { return core_.native(); }
 
 private:
@@ -660,6 +707,14 @@ public:
         if (!ids.empty()) check(ssme_lw_get_expectations(h_.get(), ids.data(), (int32_t)ids.size(), e.data()));
         return e;
     }
+    // sim_future_obs(num_future_steps) of the *FutureSimulator add-ons (liu_west_filter.h:1315-1363), on the device
+    // (ssme_lw_sim_future_obs): y[time][particle], row-major.  last_obs = the last observation.
+    std::vector<double> sim_future_obs(unsigned num_future_steps, double last_obs) {
+        std::vector<double> y((std::size_t)num_future_steps * nparts);
+        const int rc = ssme_lw_sim_future_obs(h_.get(), (int32_t)num_future_steps, &last_obs, y.data(), nullptr, nullptr, nullptr);
+        if (rc != SSME_OK) throw std::runtime_error(std::string(ssme_pf_strerror(rc)) + " (" + ssme_lw_last_error(h_.get()) + ")");
+        return y;
+    }
     ssme_lw_handle native() const { return h_.get(); }
 
 private:
@@ -781,7 +836,17 @@ public:
     }
     float_t getLogCondLike() const { return log_cond_like_; }
     std::vector<double> getExpectations() const { return expectations_; }
+    // SwarmWithCovs::simFutureObs (pswarm_filter.h:547-553): sim_future_obs of every member, here ONE device call for all of them.
+    // Returns y[member][time][particle], row-major ("param, time, then state particle", :49-50).  last_obs = the last observation.
+    std::vector<double> simFutureObs(unsigned num_future_steps, double last_obs = 0.0) {
+        if (!h_) finish_construction();
+        const std::vector<double> lo(n_param_parts, last_obs);
+        std::vector<double> y(n_param_parts * (std::size_t)num_future_steps * n_state_parts);
+        check(ssme_pf_sim_future_obs(h_.get(), (int32_t)num_future_steps, lo.data(), y.data(), nullptr, nullptr), h_.get());
+        return y;
+    }
     const std::vector<double>& params() const { return theta_; }         // [n_param_parts][4]
+    ssme_pf_handle native() const { return h_.get(); }                  // the one handle of all members (null before the first update)
 
 private:
     // intra/inter_agg_func (pswarm_filter.h:96-160): plain means over the members, reduced on the device, one download
@@ -833,6 +898,16 @@ public:
     }
     float_t getLogCondLike() const { return log_cond_like_; }
     std::vector<double> getExpectations() const { return expectations_; }
+    // Swarm::simFutureObs (pswarm_filter.h:247-253): sim_future_obs of every member, here ONE device call for all of them.
+    // Returns y[member][time][particle], row-major ("param, time, then state particle", :49-50).
+    std::vector<double> simFutureObs(unsigned num_future_steps, double last_obs = 0.0) {
+        if (!h_) finish_construction();
+        const std::vector<double> lo(n_param_parts, last_obs);
+        std::vector<double> y(n_param_parts * (std::size_t)num_future_steps * n_state_parts);
+        check(ssme_pf_sim_future_obs(h_.get(), (int32_t)num_future_steps, lo.data(), y.data(), nullptr, nullptr), h_.get());
+        return y;
+    }
+    ssme_pf_handle native() const { return h_.get(); }                  // the one handle of all members (null before the first update)
 
 private:
     // intra/inter_agg_func (pswarm_filter.h:96-160): plain means over the members, reduced on the device, one download

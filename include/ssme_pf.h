@@ -218,6 +218,26 @@ int ssme_pf_set_graph_mode(ssme_pf_handle h, int32_t mode);
  * 8*T-byte upload of y and the 8*R-byte download of the result excluded). */
 int ssme_pf_last_elapsed_ms(ssme_pf_handle h, float* ms);
 
+/* Forecast: simulated future observations from the filtered cloud -- sim_future_obs(num_future_steps) of the reference's
+ * *FutureSimulator add-ons, which Swarm::simFutureObs / SwarmWithCovs::simFutureObs call on every member
+ * (pswarm_filter.h:247-253, 547-553); ONE call for all R filters of the handle, everything on the device.
+ * From a handle that has done t0 >= 1 steps: N ancestors per filter are drawn from the weights ssme_pf_get_expectations uses (an iid
+ * two-level search of the integer weight cdf; always taken, also on a step of a resamp_sched > 1 schedule that did not resample),
+ * then for k = 0 .. num_steps-1:  x <- fSamp(x, y_prev),  y <- gSamp(x),  y_prev <- y   (gSamp: SVOL beta exp(x/2) z, leverage
+ * exp(x/2) z, linear Gaussian x + tau z).  last_obs: y_prev of the first horizon, one value per filter (read by the leverage model
+ * only; NULL = 0).  y_out[(r * num_steps + k) * N + i] ("param, time, then state particle", pswarm_filter.h:49-50); x_out: the
+ * simulated states in the same shape, or NULL; start_out: [R][N] ancestors of the start draw, or NULL.  A filter whose weights are all
+ * zero, -inf or NaN (e.g. `bad` parameters) gets NaN samples and the call returns SSME_OK.  The call changes nothing a later call on
+ * the handle returns (buffers and Philox streams of its own: two forecasts from one origin return the same bits) and is ordered
+ * behind steps queued with logcondlike_out = NULL.  SSME_F32 handles round last_obs on entry and every output to float.
+ * Arguments are validated before any HIP call: NULL handle or y_out, num_steps < 1 or > 65535: SSME_ERR_INVALID_ARG; sharded handles
+ * and SSME_MODEL_USER0 (user models declare no gSamp): SSME_ERR_UNSUPPORTED; before the first step: SSME_ERR_STATE. */
+int ssme_pf_sim_future_obs(ssme_pf_handle h, int32_t num_steps, const double* last_obs /*R or NULL*/,
+                           double* y_out /*[R][num_steps][N]*/, double* x_out /*same shape or NULL*/,
+                           uint32_t* start_out /*[R][N] or NULL*/);
+/* HIP-event times (ms) of the last ssme_pf_sim_future_obs: the horizon kernel alone, and the whole call without the download. */
+int ssme_pf_forecast_elapsed_ms(ssme_pf_handle h, float* horizon_kernel_ms, float* call_ms);
+
 /* Measurement aid for bench.py: runs a T-step series eagerly (no graph) with a HIP event on the handle's
  * stream after every 32 launches of the step kernel (k_filter_step); returns the mean launch duration in
  * microseconds (mean_us_out[0]) and the launch count (launches_out[0]). */
@@ -349,6 +369,15 @@ int ssme_lw_download_state(ssme_lw_handle h, int32_t filter, double* x, double* 
                            double* thetabar, double* chol);
 int ssme_lw_set_debug(ssme_lw_handle h, int32_t flags);
 int ssme_lw_last_elapsed_ms(ssme_lw_handle h, float* ms);
+/* Forecast of the Liu-West filters, both forms (sim_future_obs of the *FutureSimulator add-ons, liu_west_filter.h:1315-1363; see
+ * ssme_pf_sim_future_obs for the start draw, the layout of y_out / x_out / start_out and the error codes).  The start population
+ * carries its parameters; theta-bar and the Cholesky factor L of (1 - a^2) V, a = (3 delta - 1) / (2 delta), are taken once over its
+ * transformed parameters; per horizon  theta <- a theta + (1 - a) theta-bar + L e,  x <- fSamp(x, y_prev, theta),
+ * y <- exp(x / 2) z,  y_prev <- y.  last_obs: R values, required.  prop_out: [R][16] = theta-bar[4], L[10] (lower triangle by rows) as
+ * used, 2 unused, or NULL. */
+int ssme_lw_sim_future_obs(ssme_lw_handle h, int32_t num_steps, const double* last_obs /*R*/, double* y_out /*[R][num_steps][N]*/,
+                           double* x_out /*same shape or NULL*/, uint32_t* start_out /*[R][N] or NULL*/, double* prop_out /*[R][16] or NULL*/);
+int ssme_lw_forecast_elapsed_ms(ssme_lw_handle h, float* horizon_kernel_ms, float* call_ms);
 const char* ssme_lw_last_error(ssme_lw_handle h);
 
 /* ---- particle-sharded Liu-West filter: ONE filter of cfg->n_particles particles over `world` GPUs (BASELINE.json configs[4]).

@@ -24,13 +24,13 @@ EXPORTS = [
     "ssme_pf_shard_download", "ssme_pf_shard_stats", "ssme_pf_shard_layout", "ssme_pf_shard_plan", "ssme_pf_shard_step", "ssme_pf_shard_finalize", "ssme_pf_step",
     "ssme_pf_run_series", "ssme_pf_get_per_step", "ssme_pf_get_loglik", "ssme_pf_get_expectations", "ssme_pf_get_expectations_multi", "ssme_pf_swarm_aggregate", "ssme_pf_swarm_aggregate_threads", "ssme_pf_download_weights", "ssme_pf_get_layout",
     "ssme_pf_log_mean_exp", "ssme_pf_download_state", "ssme_pf_download_scalars", "ssme_pf_set_debug",
-    "ssme_pf_set_graph_mode", "ssme_pf_set_tuning", "ssme_pf_last_elapsed_ms", "ssme_pf_profile_series", "ssme_pf_test_math",
+    "ssme_pf_set_graph_mode", "ssme_pf_set_tuning", "ssme_pf_last_elapsed_ms", "ssme_pf_sim_future_obs", "ssme_pf_forecast_elapsed_ms", "ssme_pf_profile_series", "ssme_pf_test_math",
     "ssme_pf_test_philox", "ssme_pf_test_quantize", "ssme_pf_test_rescale", "ssme_pf_test_block_scan",
     "ssme_pf_test_copy", "ssme_pf_test_gamma",
     "ssme_pf_strerror", "ssme_pf_last_error",
     "ssme_pf_version",
     "ssme_lw_create", "ssme_lw_destroy", "ssme_lw_reset", "ssme_lw_step", "ssme_lw_run_series", "ssme_lw_get_per_step",
-    "ssme_lw_get_param_means", "ssme_lw_get_expectations", "ssme_lw_download_weights", "ssme_lw_download_state", "ssme_lw_set_debug", "ssme_lw_last_elapsed_ms",
+    "ssme_lw_get_param_means", "ssme_lw_get_expectations", "ssme_lw_download_weights", "ssme_lw_download_state", "ssme_lw_set_debug", "ssme_lw_last_elapsed_ms", "ssme_lw_sim_future_obs", "ssme_lw_forecast_elapsed_ms",
     "ssme_lw_last_error",
     "ssme_lw_shard_create", "ssme_lw_set_stream", "ssme_lw_shard_set_plane_tiles", "ssme_lw_shard_prepare", "ssme_lw_shard_init", "ssme_lw_shard_plan",
     "ssme_lw_shard_stage1", "ssme_lw_shard_mid", "ssme_lw_shard_stage2", "ssme_lw_shard_finalize", "ssme_lw_get_loglik", "ssme_lw_shard_run_series", "ssme_lw_shard_download", "ssme_lw_shard_stats", "ssme_lw_shard_layout",
@@ -112,6 +112,8 @@ def lib():
         L.ssme_pf_set_graph_mode.argtypes = [H, C.c_int32]
         L.ssme_pf_set_tuning.argtypes = [H, C.c_int32]
         L.ssme_pf_last_elapsed_ms.argtypes = [H, C.POINTER(C.c_float)]
+        L.ssme_pf_sim_future_obs.argtypes = [H, C.c_int32, dp, dp, dp, u32p]
+        L.ssme_pf_forecast_elapsed_ms.argtypes = [H, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         L.ssme_pf_profile_series.argtypes = [H, dp, dp, C.c_int32, dp, i32p]
         L.ssme_pf_test_math.argtypes = [C.c_int32, C.c_int32, dp, dp, C.c_int64]
         L.ssme_pf_test_philox.argtypes = [C.c_int32, u32p, u32p, u32p]
@@ -148,6 +150,8 @@ def lib():
         L.ssme_lw_download_state.argtypes = [H, C.c_int32, dp, dp, u32p, u32p, dp, dp]
         L.ssme_lw_set_debug.argtypes = [H, C.c_int32]
         L.ssme_lw_last_elapsed_ms.argtypes = [H, C.POINTER(C.c_float)]
+        L.ssme_lw_sim_future_obs.argtypes = [H, C.c_int32, dp, dp, dp, u32p, dp]
+        L.ssme_lw_forecast_elapsed_ms.argtypes = [H, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         vp = C.c_void_p
         L.ssme_lw_shard_create.argtypes = [C.POINTER(LwConfig), C.c_int32, C.c_int32, C.POINTER(H)]
         L.ssme_lw_set_stream.argtypes = [H, vp]

@@ -1,0 +1,309 @@
+// forecast.h -- simulation of future observations from the filtered particle cloud, gfx950.
+//
+// Reference counterpart: sim_future_obs(num_future_steps) of the filters' *FutureSimulator add-ons, called on every member
+// by Swarm::simFutureObs / SwarmWithCovs::simFutureObs (include/ssme/pswarm_filter.h:247-253, 547-553); the in-tree
+// simulation is the Liu-West one (include/ssme/liu_west_filter.h:1315-1363): start from the unweighted (resampled) samples,
+// then per future step propagate the state and draw an observation from it.
+//
+// Two kernels per call (bootstrap models; the Liu-West pair below adds the parameter records and their moments), both on buffers of
+// the forecast's own (nothing a later filter step reads is written):
+//   k_fc_start     draws N ancestors per filter from the last step's weights -- an iid two-level search of the integer
+//                  weight cdf, the search of k_filter_step's general path, on the level-2 tables k_level2_plan leaves
+//                  (T'_b, A_b / A'_b, S') -- and gathers their states.  grid = (tiles, R).
+//   k_fc_horizon   all H horizons in ONE launch: two particles per lane, state / y_prev / model constants in registers across
+//                  the run-time loop over the horizon, one Philox call per particle and horizon (words 0-1 -> the pair
+//                  (z_state, z_obs) by pair_normals), one coalesced 16-byte store per lane and horizon into y[r][k][.]
+//                  (and x[r][k][.] when asked).  Tables of log / sincos / exp in LDS, as in the step kernels.
+#pragma once
+#include "pf_kernels.h"
+#include "lw_kernels.h"
+
+namespace ssme {
+
+// Counter streams of the forecast.  A counter is (particle, t0, filter id, stream + (k << 8)) with t0 = the origin (steps done
+// so far) and k = the horizon (0 for the start draw).  The filters' streams are all below 144 (ssme_math.h, lw_kernels.h,
+// model_api.h) and carry nothing above bit 7, so no forecast counter equals a filter counter; k < 2^16 keeps k << 8 inside the word.
+enum { STREAM_FC_START = 160, STREAM_FC_SIM = 161, STREAM_FC_LW_JIT = 162, STREAM_FC_LW_SIM = 163 };
+constexpr int kFcMaxSteps = 65535;
+constexpr int kFcNT = 256;
+
+struct FcArgs {
+    const double* x;           // [R][Npad] particles of the last step (pre-resampling)
+    const double* cdf;         // [R][Npad] tile-local inclusive integer sums of their fixed-point weights
+    const double* l2_T;        // [R][Bs] inclusive prefixes T'_b of the rescaled tile sums   (k_level2_plan, forecast's own buffers)
+    const double* l2_R;        // [R][Bs] A_b / A'_b
+    const FilterScalars* scal; // [R] S' (forecast's own copy)
+    const ModelConst* mc;      // [R]
+    const double* gscale;      // [R] scale of the observation draw: beta (SVOL), 1 (leverage), tau (linear Gaussian)
+    const double* last_obs;    // [R] y_prev of the first horizon, or null (0)
+    double* x0;                // [R][Npad] states of the start population
+    uint32_t* start;           // [R][Npad] its ancestors
+    double* y_out;             // [R][H][Ns]
+    double* x_out;             // [R][H][Ns] or null
+    const uint32_t* keyp;      // [2] Philox key
+    uint32_t first_filter;
+    int32_t N, Npad, Ns, B, Bs, Bpow2, tile, t0, H;
+};
+
+// The start draw of particle i: u = u01_mid40 of words 0-1 of Philox(i, t0, filter id, STREAM_FC_START), target = ceil(u S'),
+// source tile b = min(#{j < B : T'_j < target}, B - 1), tile-local target tloc = ceil((target - T'_{b-1}) A_b / A'_b),
+// j = #{q : cdf_b[q] < tloc} (count_less_pow2: at most tile - 1), ancestor = min(b tile + j, N - 1).  Probes go to L2.
+// Shared by the bootstrap and the Liu-West start kernels.
+__device__ __forceinline__ int fc_draw_ancestor(const double* T, const double* Rr, const double* cdf_r, double S, int B, int Bpow2,
+                                                int tile, int N, int i, uint32_t t0, uint32_t rep, uint32_t key0, uint32_t key1) {
+    const u32x4 o = philox4x32_10((uint32_t)i, t0, rep, STREAM_FC_START, key0, key1);
+    const double target = __builtin_ceil(u01_mid40(o.v0, o.v1) * S);
+    int bb = count_less_pow2(Bpow2, target, [&](int j) { return j < B ? T[j] : dinf(); });
+    bb = bb < B - 1 ? bb : B - 1;
+    const double Pb = bb ? T[bb - 1] : 0.0;
+    const double tloc = __builtin_ceil((target - Pb) * Rr[bb]);
+    const double* tl = cdf_r + (size_t)bb * tile;
+    const int j = count_less_pow2(tile, tloc, [&](int q) { return tl[q]; });
+    const int an = bb * tile + j;
+    return an < N - 1 ? an : N - 1;
+}
+
+// ---------------------------------------------------------------------------------------
+// Start population of the bootstrap models: every particle's ancestor by fc_draw_ancestor and its state.  A filter without weight
+// (S' not > 0: all weights zero, -inf or NaN) gets NaN states.  grid = (B, R), block = kFcNT.
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kFcNT) void k_fc_start(const FcArgs a) {
+    const int r = blockIdx.y, b = blockIdx.x;
+    const uint32_t rep = a.first_filter + (uint32_t)r;
+    const uint32_t key0 = a.keyp[0], key1 = a.keyp[1];
+    const size_t rowoff = (size_t)r * a.Npad;
+    const double* T = a.l2_T + (size_t)r * a.Bs;
+    const double* Rr = a.l2_R + (size_t)r * a.Bs;
+    const double* cdf_r = a.cdf + rowoff;
+    const double S = a.scal[r].S;
+    const bool alive = S > 0.0;
+    for (int j0 = threadIdx.x; j0 < a.tile; j0 += kFcNT) {
+        const int i = b * a.tile + j0;                       // < Npad
+        uint32_t anc = 0u;
+        double xv = 0.0;
+        if (i < a.N) {
+            const int an = fc_draw_ancestor(T, Rr, cdf_r, S, a.B, a.Bpow2, a.tile, a.N, i, (uint32_t)a.t0, rep, key0, key1);
+            anc = (uint32_t)an;
+            xv = alive ? a.x[rowoff + an] : dnan();
+        }
+        a.start[rowoff + i] = anc;
+        a.x0[rowoff + i] = xv;
+    }
+}
+
+// observation draw gSamp(x, z): SVOL beta exp(x/2) z, leverage exp(x/2) z (test/test_pswarm.cpp:112-116), linear Gaussian x + tau z
+template <int MODEL>
+__device__ __forceinline__ double model_gsamp(double gs, double x, double z, const ExpTabEntry* etab) {
+    if (MODEL == MODEL_LIN_GAUSS) return x + gs * z;
+    const double e = dexp_scaled_t(0.5 * x, 0, etab);
+    if (MODEL == MODEL_SVOL) return (gs * e) * z;
+    return e * z;
+}
+
+// ---------------------------------------------------------------------------------------
+// All H horizons of lane pairs (2p, 2p + 1).  Per horizon k and particle i: (z_s, z_o) = pair_normals of words 0-1 of
+// Philox(i, t0, filter id, STREAM_FC_SIM + (k << 8)); x <- model_prop(x, z_s, y_prev); y <- gSamp(x, z_o); y_prev <- y
+// (propagate, then observe: liu_west_filter.h:1338-1356).  Rows of the outputs are Ns = N rounded up to even doubles long, so
+// every store is an aligned double2; the pad column of an odd N is computed from a zero state and never copied out.
+// grid = (ceil(Ns / 2 / kFcNT), R), block = kFcNT.
+// ---------------------------------------------------------------------------------------
+template <int MODEL>
+__global__ __launch_bounds__(kFcNT) void k_fc_horizon(const FcArgs a) {
+    __shared__ __attribute__((aligned(16))) DrawTabs lds_dtab;
+    __shared__ __attribute__((aligned(16))) ExpTabEntry lds_etab[SSME_EXP_TABLE_SIZE];
+    load_log_table<kFcNT>(&lds_dtab);
+    load_exp_table<kFcNT>(lds_etab);
+    __syncthreads();
+    const int r = blockIdx.y;
+    const int i0 = ((int)blockIdx.x * kFcNT + (int)threadIdx.x) * 2;
+    if (i0 >= a.Ns) return;
+    const uint32_t rep = a.first_filter + (uint32_t)r;
+    const uint32_t key0 = a.keyp[0], key1 = a.keyp[1];
+    const ModelConst mc = a.mc[r];
+    const double gs = a.gscale[r];
+    const bool alive = a.scal[r].S > 0.0;
+    const double2 xs = *reinterpret_cast<const double2*>(a.x0 + (size_t)r * a.Npad + i0);
+    double x[2] = {xs.x, xs.y};
+    const double y0 = a.last_obs ? a.last_obs[r] : 0.0;
+    double yp[2] = {y0, y0};
+    const size_t plane = (size_t)a.Ns;
+    double* yrow = a.y_out + (size_t)r * a.H * plane + i0;
+    double* xrow = a.x_out ? a.x_out + (size_t)r * a.H * plane + i0 : nullptr;
+    for (int k = 0; k < a.H; ++k) {
+        const uint32_t c3 = (uint32_t)STREAM_FC_SIM + ((uint32_t)k << 8);
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            const u32x4 o = philox4x32_10((uint32_t)(i0 + c), (uint32_t)a.t0, rep, c3, key0, key1);
+            double zs, zo;
+            pair_normals(o.v0, o.v1, &lds_dtab, &zs, &zo);
+            x[c] = model_prop<MODEL>(mc, x[c], zs, yp[c], lds_etab);
+            const double yv = model_gsamp<MODEL>(gs, x[c], zo, lds_etab);
+            yp[c] = alive ? yv : dnan();
+        }
+        *reinterpret_cast<double2*>(yrow) = make_double2(yp[0], yp[1]);
+        yrow += plane;
+        if (xrow) { *reinterpret_cast<double2*>(xrow) = make_double2(x[0], x[1]); xrow += plane; }
+    }
+}
+
+// =======================================================================================
+// Liu-West, both forms (liu_west_filter.h:1315-1363): the start population carries its parameters; theta-bar and the Cholesky
+// factor L of (1 - a^2) V are taken ONCE over the transformed parameters of the start population (the reference recomputes them
+// every horizon from the unchanged m_param_particles, so they are constant), by the filter's own moment tree (k_lw_stage1's tile
+// partials, k_lw_mom_totals, lw_proposal_components).  Per horizon, in k_lw_stage2's operation order:
+//   m = a theta + (1 - a) theta-bar;  theta <- m + L e;  tu = tr_inv(theta);
+//   x <- mean(x, y_prev, tu) + z_s tu[2] sqrt(1 - tu[3]^2);  y <- z_o exp(x / 2);  y_prev <- y
+// e: four normals of one Philox call (STREAM_FC_LW_JIT), (z_s, z_o): words 0-1 of a second one (STREAM_FC_LW_SIM).
+// =======================================================================================
+struct FcLwArgs {
+    const double* x;           // [R][Npad] particles of the last step
+    const double* th;          // [R][Npad][4] their transformed parameters
+    const double* cdf;         // [R][Npad] integer cdf of the second-stage weights
+    const double* l2_T; const double* l2_R; const FilterScalars* scal;
+    const double* last_obs;    // [R]
+    double* x0; double* th0;   // [R][Npad], [R][Npad][4]: the start population
+    uint32_t* start;           // [R][Npad]
+    double* mom;               // [R][B][16] tile partials of the 14 moments
+    const double* prop;        // [R][16] theta-bar[4], L[10]
+    double* y_out; double* x_out;
+    const uint32_t* keyp;
+    uint32_t first_filter;
+    int32_t N, Npad, Ns, B, Bs, Bpow2, t0, H;
+    double a_shrink;
+    int32_t trans[kDP];
+};
+
+// grid = (B, R), block = kLwNT, 2048-particle tiles: thread tid holds particles i_first + (k 512 + tid) 2 + c, as k_lw_stage1 does,
+// so that the moment partials run through the same additions
+__global__ __launch_bounds__(kLwNT) void k_fc_lw_start(const FcLwArgs a) {
+    constexpr int NT = kLwNT, NK = 2;
+    __shared__ double lds_mom[8][4][16];
+    const int tid = threadIdx.x, r = blockIdx.y, b = blockIdx.x;
+    const uint32_t rep = a.first_filter + (uint32_t)r;
+    const uint32_t key0 = a.keyp[0], key1 = a.keyp[1];
+    const size_t rowoff = (size_t)r * a.Npad;
+    const double* T = a.l2_T + (size_t)r * a.Bs;
+    const double* Rr = a.l2_R + (size_t)r * a.Bs;
+    const double* cdf_r = a.cdf + rowoff;
+    const double S = a.scal[r].S;
+    const bool alive = S > 0.0;
+    const int i_first = b * kTile;
+    double fold[kNMom][2];
+#pragma unroll
+    for (int k = 0; k < NK; ++k) {
+        const int i0 = i_first + (k * NT + tid) * 2;
+        double xo[2], tt[kDP][2];
+        uint32_t an[2];
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            const int i = i0 + c;
+            const bool valid = i < a.N;
+            int anc = 0;
+            if (valid) anc = fc_draw_ancestor(T, Rr, cdf_r, S, a.B, a.Bpow2, kTile, a.N, i, (uint32_t)a.t0, rep, key0, key1);
+            an[c] = (uint32_t)anc;
+            double trec[kDP];
+            th_load(a.th, rowoff + (size_t)anc, trec);
+            xo[c] = valid ? (alive ? a.x[rowoff + anc] : dnan()) : 0.0;
+            int q = 0;
+#pragma unroll
+            for (int d = 0; d < kDP; ++d) { tt[d][c] = valid ? trec[d] : 0.0; const double v = tt[d][c]; fold[q][c] = (k == 0) ? v : fold[q][c] + v; ++q; }
+#pragma unroll
+            for (int d = 0; d < kDP; ++d) {
+#pragma unroll
+                for (int e = 0; e <= d; ++e) { const double v = valid ? tt[d][c] * tt[e][c] : 0.0; fold[q][c] = (k == 0) ? v : fold[q][c] + v; ++q; }
+            }
+        }
+        *reinterpret_cast<double2*>(a.x0 + rowoff + i0) = make_double2(xo[0], xo[1]);
+        *reinterpret_cast<uint2*>(a.start + rowoff + i0) = make_uint2(an[0], an[1]);
+        th_store_pair(a.th0, rowoff + (size_t)i0, tt);
+    }
+    {
+        double v[16];
+#pragma unroll
+        for (int q = 0; q < kNMom; ++q) v[q] = fold[q][0] + fold[q][1];
+        v[14] = 0.0; v[15] = 0.0;
+        const double rowtot = lw_row_tree14(v, tid);
+        lds_mom[tid >> 6][(tid >> 4) & 3][lw_row_tree_index(tid & 15)] = rowtot;
+    }
+    __syncthreads();
+    if (tid < kNMom) {
+        double s = 0.0;
+#pragma unroll
+        for (int w = 0; w < 8; ++w) s = s + ((lds_mom[w][3][tid] + lds_mom[w][2][tid]) + (lds_mom[w][1][tid] + lds_mom[w][0][tid]));
+        a.mom[((size_t)r * a.B + b) * 16 + tid] = s;
+    }
+}
+
+// theta-bar and L of every filter from its 14 moment totals.  grid = (R), block = 64 (one thread works)
+__global__ __launch_bounds__(64) void k_fc_lw_prop(const double* momtot, int N, double a_shrink, double* prop) {
+    if (threadIdx.x == 0) lw_proposal_components(momtot + (size_t)blockIdx.x * 16, N, a_shrink, prop + (size_t)blockIdx.x * 16);
+}
+
+// grid = (ceil(Ns / 2 / kFcNT), R), block = kFcNT; layout and stores as k_fc_horizon
+__global__ __launch_bounds__(kFcNT) void k_fc_lw_horizon(const FcLwArgs a) {
+    __shared__ __attribute__((aligned(16))) DrawTabs lds_dtab;
+    __shared__ __attribute__((aligned(16))) ExpTabEntry lds_etab[SSME_EXP_TABLE_SIZE];
+    load_log_table<kFcNT>(&lds_dtab);
+    load_exp_table<kFcNT>(lds_etab);
+    __syncthreads();
+    const int r = blockIdx.y;
+    const int i0 = ((int)blockIdx.x * kFcNT + (int)threadIdx.x) * 2;
+    if (i0 >= a.Ns) return;
+    const uint32_t rep = a.first_filter + (uint32_t)r;
+    const uint32_t key0 = a.keyp[0], key1 = a.keyp[1];
+    const bool alive = a.scal[r].S > 0.0;
+    double prop[14];
+#pragma unroll
+    for (int q = 0; q < 14; ++q) prop[q] = a.prop[(size_t)r * 16 + q];       // uniform: scalar loads
+    const size_t rowoff = (size_t)r * a.Npad;
+    const double2 xs = *reinterpret_cast<const double2*>(a.x0 + rowoff + i0);
+    double x[2] = {xs.x, xs.y};
+    double th[kDP][2];
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        double trec[kDP];
+        th_load(a.th0, rowoff + (size_t)(i0 + c), trec);
+#pragma unroll
+        for (int d = 0; d < kDP; ++d) th[d][c] = trec[d];
+    }
+    const double y0 = a.last_obs[r];
+    double yp[2] = {y0, y0};
+    const size_t plane = (size_t)a.Ns;
+    double* yrow = a.y_out + (size_t)r * a.H * plane + i0;
+    double* xrow = a.x_out ? a.x_out + (size_t)r * a.H * plane + i0 : nullptr;
+    const double om = 1.0 - a.a_shrink;
+    for (int k = 0; k < a.H; ++k) {
+        const uint32_t kk = (uint32_t)k << 8;
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            double e[kDP];
+            const u32x4 o1 = philox4x32_10((uint32_t)(i0 + c), (uint32_t)a.t0, rep, (uint32_t)STREAM_FC_LW_JIT + kk, key0, key1);
+            pair_normals(o1.v0, o1.v1, &lds_dtab, &e[0], &e[1]);
+            pair_normals(o1.v2, o1.v3, &lds_dtab, &e[2], &e[3]);
+            double tu[kDP];
+            int q = kDP;
+#pragma unroll
+            for (int d = 0; d < kDP; ++d) {
+                const double mm = a.a_shrink * th[d][c] + om * prop[d];
+                double acc = 0.0;
+#pragma unroll
+                for (int w = 0; w <= d; ++w) { acc = acc + prop[q] * e[w]; ++q; }
+                th[d][c] = mm + acc;
+                tu[d] = tr_inv(a.trans[d], th[d][c], lds_etab);
+            }
+            const u32x4 o2 = philox4x32_10((uint32_t)(i0 + c), (uint32_t)a.t0, rep, (uint32_t)STREAM_FC_LW_SIM + kk, key0, key1);
+            double zs, zo;
+            pair_normals(o2.v0, o2.v1, &lds_dtab, &zs, &zo);
+            const double xk = x[c];
+            const double mean = (tu[1] + tu[0] * (xk - tu[1])) + ((yp[c] * tu[3]) * tu[2]) * dexp_scaled_t(-0.5 * xk, 0, lds_etab);
+            x[c] = mean + zs * (tu[2] * dsqrt(1.0 - tu[3] * tu[3]));
+            const double yv = zo * dexp_scaled_t(0.5 * x[c], 0, lds_etab);
+            yp[c] = alive ? yv : dnan();
+        }
+        *reinterpret_cast<double2*>(yrow) = make_double2(yp[0], yp[1]);
+        yrow += plane;
+        if (xrow) { *reinterpret_cast<double2*>(xrow) = make_double2(x[0], x[1]); xrow += plane; }
+    }
+}
+
+}  // namespace ssme

@@ -6,6 +6,7 @@
 #include "lw_kernels.h"
 #include "pf_small.h"
 #include "user_expect.h"
+#include "forecast.h"
 #include "handle_core.h"
 #include "shard_driver.h"
 
@@ -62,6 +63,17 @@ struct ssme_pf_s : HandleCore {
     hipGraphExec_t gexec;
     int g_T, g_has_z, g_debug, g_logw, g_nt;
     std::vector<ModelConst> h_mc;
+    // forecast (forecast.h, ssme_pf_sim_future_obs): buffers of its own, allocated on first use
+    std::vector<double> h_gscale, h_last_obs;   // per filter: scale of the observation draw (set_params), y_prev of this call
+    double *fc_T, *fc_R;         // [R][Bs] level-2 tables of the start draw
+    FilterScalars* fc_scal;      // [R] S' of the start draw
+    double *fc_gscale, *fc_last; // [R]
+    double* fc_x0;               // [R][Npad] states of the start population
+    uint32_t* fc_start;          // [R][Npad] its ancestors
+    double *fc_y, *fc_x;         // [R][H][Ns] samples, fc_cap doubles each
+    size_t fc_cap_y, fc_cap_x;
+    hipEvent_t fc_ev[3];         // call start, horizon kernel start, horizon kernel end
+    float fc_ms_horizon, fc_ms_call;
 };
 
 // Wait for a stream with the latency of a poll: hipStreamSynchronize spins only briefly and then sleeps on an interrupt,
@@ -487,6 +499,12 @@ static int user_expectations_checked(ssme_pf_handle h) {
 #endif
 }
 
+// the horizon kernel of a forecast (forecast.h), one instantiation per built-in model
+template <int MODEL>
+static void launch_fc_horizon(ssme_pf_handle h, const FcArgs& a) {
+    hipLaunchKernelGGL((k_fc_horizon<MODEL>), dim3((a.Ns / 2 + kFcNT - 1) / kFcNT, h->R), dim3(kFcNT), 0, h->stream, a);
+}
+
 extern "C" {
 
 int ssme_pf_version(void) { return 333; }
@@ -588,6 +606,7 @@ int ssme_pf_destroy(ssme_pf_handle h) {
     hipSetDevice(h->cfg.device);
     if (h->gexec) { hipStreamSynchronize(h->stream); hipGraphExecDestroy(h->gexec); }
     release_core(h);
+    for (hipEvent_t& e : h->fc_ev) if (e) hipEventDestroy(e);      // the forecast's events: after release_core has waited for the stream
     delete h;
     return SSME_OK;
 }
@@ -926,6 +945,7 @@ int ssme_pf_set_params(ssme_pf_handle h, const double* theta, int32_t n_theta, i
     if (n_rows != 1 && n_rows != h->R) return SSME_ERR_INVALID_ARG;
     HIPCHK(hipSetDevice(h->cfg.device));
     h->h_mc.resize(h->R);
+    h->h_gscale.assign(h->R, 1.0);
     for (int r = 0; r < h->R; ++r) {
         double th[8];
         for (int d = 0; d < n_theta; ++d) {
@@ -933,6 +953,8 @@ int ssme_pf_set_params(ssme_pf_handle h, const double* theta, int32_t n_theta, i
             th[d] = h->cfg.dtype == SSME_F32 ? f32r(v) : v;
         }
         h->h_mc[r] = derive(h->cfg.model, th);
+        if (h->cfg.model == SSME_MODEL_SVOL) h->h_gscale[r] = th[0];            // beta
+        else if (h->cfg.model == SSME_MODEL_LIN_GAUSS) h->h_gscale[r] = th[2];  // tau
     }
     HIPCHK(hipMemcpyAsync(h->mc, h->h_mc.data(), sizeof(ModelConst) * h->R, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -1298,6 +1320,76 @@ int ssme_pf_get_layout(ssme_pf_handle h, int32_t* tile_particles, int32_t* n_til
     return SSME_OK;
 }
 
+// ---- forecast: simulated future observations (forecast.h) -------------------------------------------
+int ssme_pf_sim_future_obs(ssme_pf_handle h, int32_t num_steps, const double* last_obs, double* y_out, double* x_out,
+                           uint32_t* start_out) {
+    if (!h || !y_out || num_steps < 1 || num_steps > kFcMaxSteps) return SSME_ERR_INVALID_ARG;
+    if (h->shard_world > 0) { h->err = "forecasts of particle-sharded filters are not implemented"; return SSME_ERR_UNSUPPORTED; }
+    if (h->cfg.model == SSME_MODEL_USER0) { h->err = "user models declare no observation draw (gSamp)"; return SSME_ERR_UNSUPPORTED; }
+    if (!h->params_set || h->t < 1) { h->err = "sim_future_obs before the first step"; return SSME_ERR_STATE; }
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const int H = num_steps, R = h->R, N = h->N;
+    const int Ns = (N + 1) & ~1;
+    const size_t nb = (size_t)R * h->Bs, np = (size_t)R * h->Npad, ns = (size_t)R * H * Ns;
+    if (!h->fc_T) {
+        HIPCHK(own_alloc(h, h->fc_T, sizeof(double) * nb));
+        HIPCHK(own_alloc(h, h->fc_R, sizeof(double) * nb));
+        HIPCHK(own_alloc(h, h->fc_scal, sizeof(FilterScalars) * R, Mem::zeroed));
+        HIPCHK(own_alloc(h, h->fc_gscale, sizeof(double) * R));
+        HIPCHK(own_alloc(h, h->fc_last, sizeof(double) * R));
+        HIPCHK(own_alloc(h, h->fc_x0, sizeof(double) * np));
+        HIPCHK(own_alloc(h, h->fc_start, sizeof(uint32_t) * np));
+        for (hipEvent_t& e : h->fc_ev) HIPCHK(hipEventCreate(&e));
+    }
+    if (ns > h->fc_cap_y) { h->fc_cap_y = 0; HIPCHK(own_alloc(h, h->fc_y, sizeof(double) * ns)); h->fc_cap_y = ns; }
+    if (x_out && ns > h->fc_cap_x) { h->fc_cap_x = 0; HIPCHK(own_alloc(h, h->fc_x, sizeof(double) * ns)); h->fc_cap_x = ns; }
+    h->h_last_obs.assign(R, 0.0);
+    if (last_obs) for (int r = 0; r < R; ++r) h->h_last_obs[r] = h->cfg.dtype == SSME_F32 ? f32r(last_obs[r]) : last_obs[r];
+    HIPCHK(hipEventRecord(h->fc_ev[0], h->stream));
+    HIPCHK(hipMemcpyAsync(h->fc_gscale, h->h_gscale.data(), sizeof(double) * R, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->fc_last, h->h_last_obs.data(), sizeof(double) * R, hipMemcpyHostToDevice, h->stream));
+    {
+        // level-2 of the last step's weights (the weights ssme_pf_get_expectations uses) into the forecast's own tables and scalars
+        StepArgs p = step_args(h);
+        p.tsum_in = h->tsum[h->cur]; p.tmax_in = h->tmax[h->cur];
+        p.l2_T = h->fc_T; p.l2_R = h->fc_R; p.scal = h->fc_scal;
+        p.t = h->t; p.finalize_prev = 0; p.per_step = nullptr; p.ll_host = nullptr;
+        hipLaunchKernelGGL(k_level2_plan, dim3(R), dim3(1024), h->lds_bytes_plan, h->stream, p, 0);
+    }
+    FcArgs a{};
+    a.x = h->x[h->cur]; a.cdf = h->cdf[h->cur]; a.l2_T = h->fc_T; a.l2_R = h->fc_R; a.scal = h->fc_scal; a.mc = h->mc;
+    a.gscale = h->fc_gscale; a.last_obs = h->fc_last; a.x0 = h->fc_x0; a.start = h->fc_start;
+    a.y_out = h->fc_y; a.x_out = x_out ? h->fc_x : nullptr;
+    a.keyp = h->keybuf; a.first_filter = h->cfg.first_filter_id;
+    a.N = N; a.Npad = h->Npad; a.Ns = Ns; a.B = h->B; a.Bs = h->Bs; a.Bpow2 = h->Bpow2; a.tile = h->tile; a.t0 = h->t; a.H = H;
+    hipLaunchKernelGGL(k_fc_start, dim3(h->B, R), dim3(kFcNT), 0, h->stream, a);
+    HIPCHK(hipEventRecord(h->fc_ev[1], h->stream));
+    switch (h->cfg.model) {
+        case SSME_MODEL_SVOL: launch_fc_horizon<MODEL_SVOL>(h, a); break;
+        case SSME_MODEL_SVOL_LEVERAGE: launch_fc_horizon<MODEL_SVOL_LEVERAGE>(h, a); break;
+        default: launch_fc_horizon<MODEL_LIN_GAUSS>(h, a); break;
+    }
+    HIPCHK(hipEventRecord(h->fc_ev[2], h->stream));
+    HIPCHK(hipGetLastError());
+    const size_t rows = (size_t)R * H;
+    HIPCHK(hipMemcpy2DAsync(y_out, sizeof(double) * N, h->fc_y, sizeof(double) * Ns, sizeof(double) * N, rows, hipMemcpyDeviceToHost, h->stream));
+    if (x_out) HIPCHK(hipMemcpy2DAsync(x_out, sizeof(double) * N, h->fc_x, sizeof(double) * Ns, sizeof(double) * N, rows, hipMemcpyDeviceToHost, h->stream));
+    if (start_out) HIPCHK(hipMemcpy2DAsync(start_out, sizeof(uint32_t) * N, h->fc_start, sizeof(uint32_t) * h->Npad, sizeof(uint32_t) * N, R, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipEventElapsedTime(&h->fc_ms_horizon, h->fc_ev[1], h->fc_ev[2]));
+    HIPCHK(hipEventElapsedTime(&h->fc_ms_call, h->fc_ev[0], h->fc_ev[2]));
+    round_out(h, y_out, rows * N);
+    round_out(h, x_out, rows * N);
+    return SSME_OK;
+}
+
+int ssme_pf_forecast_elapsed_ms(ssme_pf_handle h, float* horizon_kernel_ms, float* call_ms) {
+    if (!h) return SSME_ERR_INVALID_ARG;
+    if (horizon_kernel_ms) *horizon_kernel_ms = h->fc_ms_horizon;
+    if (call_ms) *call_ms = h->fc_ms_call;
+    return SSME_OK;
+}
+
 int ssme_pf_last_elapsed_ms(ssme_pf_handle h, float* ms) { return elapsed_ms(h, ms); }
 
 int ssme_pf_profile_series(ssme_pf_handle h, const double* y, const double* z, int32_t T, double* mean_us,
@@ -1554,6 +1646,15 @@ struct ssme_lw_s : HandleCore {
     int32_t *l2lo[2], *l2hi[2];
     FilterScalars* l2s[2];
     LwScalars* scal;
+    // forecast (forecast.h, ssme_lw_sim_future_obs): buffers of its own, allocated on first use
+    std::vector<double> h_last_obs;
+    double *fc_T, *fc_R, *fc_last, *fc_x0, *fc_th0, *fc_mom, *fc_momtot, *fc_prop;
+    FilterScalars* fc_scal;
+    uint32_t* fc_start;
+    double *fc_y, *fc_x;             // [R][H][Ns] samples
+    size_t fc_cap_y, fc_cap_x;
+    hipEvent_t fc_ev[3];             // call start, horizon kernel start, horizon kernel end
+    float fc_ms_horizon, fc_ms_call;
 };
 
 static LwArgs lw_args(ssme_lw_handle h) {
@@ -1700,6 +1801,7 @@ int ssme_lw_destroy(ssme_lw_handle h) {
     if (!h) return SSME_ERR_INVALID_ARG;
     hipSetDevice(h->cfg.device);
     release_core(h);
+    for (hipEvent_t& e : h->fc_ev) if (e) hipEventDestroy(e);      // the forecast's events: after release_core has waited for the stream
     delete h;
     return SSME_OK;
 }
@@ -2230,6 +2332,80 @@ int ssme_lw_download_state(ssme_lw_handle h, int32_t f, double* x, double* theta
     if (theta) for (int i = 0; i < h->N; ++i) for (int d = 0; d < kDP; ++d) theta[(size_t)d * h->N + i] = rec[(size_t)i * kDP + d];
     if (thetabar) for (int d = 0; d < kDP; ++d) thetabar[d] = p[d];
     if (chol) { int q = kDP; for (int d = 0; d < kDP; ++d) for (int e = 0; e < kDP; ++e) chol[d * kDP + e] = (e <= d) ? p[q++] : 0.0; }
+    return SSME_OK;
+}
+
+// Liu-West forecast (forecast.h): start draw with the parameter records and their moment partials, moment
+// totals and proposal components by the filter's own kernels / function, then all horizons in one launch
+int ssme_lw_sim_future_obs(ssme_lw_handle h, int32_t num_steps, const double* last_obs, double* y_out, double* x_out,
+                           uint32_t* start_out, double* prop_out) {
+    if (!h || !y_out || !last_obs || num_steps < 1 || num_steps > kFcMaxSteps) return SSME_ERR_INVALID_ARG;
+    if (h->shard_world > 0) { h->err = "forecasts of particle-sharded filters are not implemented"; return SSME_ERR_UNSUPPORTED; }
+    if (h->t < 1) { h->err = "sim_future_obs before the first step"; return SSME_ERR_STATE; }
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const int H = num_steps, R = h->R, N = h->N;
+    const int Ns = (N + 1) & ~1;
+    const size_t nb = (size_t)R * h->Bs, np = (size_t)R * h->Npad, ns = (size_t)R * H * Ns;
+    if (!h->fc_T) {
+        HIPCHK(own_alloc(h, h->fc_T, sizeof(double) * nb));
+        HIPCHK(own_alloc(h, h->fc_R, sizeof(double) * nb));
+        HIPCHK(own_alloc(h, h->fc_scal, sizeof(FilterScalars) * R, Mem::zeroed));
+        HIPCHK(own_alloc(h, h->fc_last, sizeof(double) * R));
+        HIPCHK(own_alloc(h, h->fc_x0, sizeof(double) * np));
+        HIPCHK(own_alloc(h, h->fc_th0, sizeof(double) * np * kDP));
+        HIPCHK(own_alloc(h, h->fc_start, sizeof(uint32_t) * np));
+        HIPCHK(own_alloc(h, h->fc_mom, sizeof(double) * (size_t)R * h->B * 16));
+        HIPCHK(own_alloc(h, h->fc_momtot, sizeof(double) * (size_t)R * 16, Mem::zeroed));
+        HIPCHK(own_alloc(h, h->fc_prop, sizeof(double) * (size_t)R * 16, Mem::zeroed));
+        for (hipEvent_t& e : h->fc_ev) HIPCHK(hipEventCreate(&e));
+    }
+    if (ns > h->fc_cap_y) { h->fc_cap_y = 0; HIPCHK(own_alloc(h, h->fc_y, sizeof(double) * ns)); h->fc_cap_y = ns; }
+    if (x_out && ns > h->fc_cap_x) { h->fc_cap_x = 0; HIPCHK(own_alloc(h, h->fc_x, sizeof(double) * ns)); h->fc_cap_x = ns; }
+    h->h_last_obs.assign(last_obs, last_obs + R);
+    HIPCHK(hipEventRecord(h->fc_ev[0], h->stream));
+    HIPCHK(hipMemcpyAsync(h->fc_last, h->h_last_obs.data(), sizeof(double) * R, hipMemcpyHostToDevice, h->stream));
+    {
+        // level-2 of the second-stage weights of the last step (the weights ssme_lw_get_expectations uses) into the forecast's own tables
+        StepArgs p{};
+        p.tsum_in = h->tsumB; p.tmax_in = h->tmaxB; p.l2_T = h->fc_T; p.l2_R = h->fc_R; p.scal = h->fc_scal;
+        p.B = h->B; p.Bs = h->Bs; p.Bpow2 = h->Bpow2; p.rshift = h->rshift; p.R = R; p.N = N; p.tile = kTile;
+        p.resampler = RESAMP_MULTINOMIAL; p.resamp_sched = 1; p.t = h->t;
+        hipLaunchKernelGGL(k_level2_plan, dim3(R), dim3(1024), h->lds_bytes_plan, h->stream, p, 0);
+    }
+    FcLwArgs a{};
+    a.x = h->xB; a.th = h->thB; a.cdf = h->cdfB; a.l2_T = h->fc_T; a.l2_R = h->fc_R; a.scal = h->fc_scal; a.last_obs = h->fc_last;
+    a.x0 = h->fc_x0; a.th0 = h->fc_th0; a.start = h->fc_start; a.mom = h->fc_mom; a.prop = h->fc_prop;
+    a.y_out = h->fc_y; a.x_out = x_out ? h->fc_x : nullptr;
+    a.keyp = h->keybuf; a.first_filter = h->cfg.first_filter_id;
+    a.N = N; a.Npad = h->Npad; a.Ns = Ns; a.B = h->B; a.Bs = h->Bs; a.Bpow2 = h->Bpow2; a.t0 = h->t; a.H = H;
+    a.a_shrink = (3.0 * h->cfg.delta - 1.0) / (2.0 * h->cfg.delta);
+    for (int d = 0; d < kDP; ++d) a.trans[d] = h->cfg.transforms[d];
+    hipLaunchKernelGGL(k_fc_lw_start, dim3(h->B, R), dim3(kLwNT), 0, h->stream, a);
+    {
+        LwArgs m{};                                   // the filter's own totals kernel on the forecast's partials
+        m.B = h->B; m.mom = h->fc_mom; m.momtot = h->fc_momtot;
+        hipLaunchKernelGGL(k_lw_mom_totals, dim3(kNMom, R), dim3(64), 0, h->stream, m);
+    }
+    hipLaunchKernelGGL(k_fc_lw_prop, dim3(R), dim3(64), 0, h->stream, (const double*)h->fc_momtot, N, a.a_shrink, h->fc_prop);
+    HIPCHK(hipEventRecord(h->fc_ev[1], h->stream));
+    hipLaunchKernelGGL(k_fc_lw_horizon, dim3((Ns / 2 + kFcNT - 1) / kFcNT, R), dim3(kFcNT), 0, h->stream, a);
+    HIPCHK(hipEventRecord(h->fc_ev[2], h->stream));
+    HIPCHK(hipGetLastError());
+    const size_t rows = (size_t)R * H;
+    HIPCHK(hipMemcpy2DAsync(y_out, sizeof(double) * N, h->fc_y, sizeof(double) * Ns, sizeof(double) * N, rows, hipMemcpyDeviceToHost, h->stream));
+    if (x_out) HIPCHK(hipMemcpy2DAsync(x_out, sizeof(double) * N, h->fc_x, sizeof(double) * Ns, sizeof(double) * N, rows, hipMemcpyDeviceToHost, h->stream));
+    if (start_out) HIPCHK(hipMemcpy2DAsync(start_out, sizeof(uint32_t) * N, h->fc_start, sizeof(uint32_t) * h->Npad, sizeof(uint32_t) * N, R, hipMemcpyDeviceToHost, h->stream));
+    if (prop_out) HIPCHK(hipMemcpyAsync(prop_out, h->fc_prop, sizeof(double) * (size_t)R * 16, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipEventElapsedTime(&h->fc_ms_horizon, h->fc_ev[1], h->fc_ev[2]));
+    HIPCHK(hipEventElapsedTime(&h->fc_ms_call, h->fc_ev[0], h->fc_ev[2]));
+    return SSME_OK;
+}
+
+int ssme_lw_forecast_elapsed_ms(ssme_lw_handle h, float* horizon_kernel_ms, float* call_ms) {
+    if (!h) return SSME_ERR_INVALID_ARG;
+    if (horizon_kernel_ms) *horizon_kernel_ms = h->fc_ms_horizon;
+    if (call_ms) *call_ms = h->fc_ms_call;
     return SSME_OK;
 }
 

@@ -176,6 +176,26 @@ class ParticleFilterBank:
         self._chk(capi.lib().ssme_pf_swarm_aggregate_user(self._h, int(num_threads), capi.dptr(ll), capi.dptr(ex)))
         return float(ll[0]), ex
 
+    def sim_future_obs(self, H, last_obs=None, states=False, start=False):
+        """Simulated future observations y[R, H, N] of every filter, on the device (ssme_pf_sim_future_obs: sim_future_obs of the
+        reference's *FutureSimulator add-ons; layout "param, time, then state particle", pswarm_filter.h:49-50).  last_obs: the
+        last observation, a scalar or one value per filter (read by the leverage model only).  states / start: also return the
+        simulated states x[R, H, N] / the ancestors [R, N] of the start draw: y, or (y[, x][, start])."""
+        H = int(H)
+        lo = None if last_obs is None else np.ascontiguousarray(np.broadcast_to(np.asarray(last_obs, dtype=np.float64), (self.r,)))
+        y = np.empty((self.r, max(H, 0), self.n))
+        x = np.empty_like(y) if states else None
+        st = np.empty((self.r, self.n), dtype=np.uint32) if start else None
+        self._chk(capi.lib().ssme_pf_sim_future_obs(self._h, H, capi.dptr(lo), capi.dptr(y), capi.dptr(x), capi.u32ptr(st)))
+        out = (y,) + ((x,) if states else ()) + ((st,) if start else ())
+        return y if len(out) == 1 else out
+
+    def forecast_elapsed_ms(self):
+        """HIP-event times (ms) of the last sim_future_obs: (horizon kernel alone, whole call without the download)."""
+        a, b = C.c_float(), C.c_float()
+        self._chk(capi.lib().ssme_pf_forecast_elapsed_ms(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def weights(self, f=0):
         """(x, w) of filter f after the last step for host-side functionals: w = exp(logw - max logw); x: [dim_x, N] for a vector model."""
         dx = self._dims()[0]
@@ -249,6 +269,11 @@ class _SingleFilter:
             else:
                 out.append(float(next(dev)))
         return out
+
+    def sim_future_obs(self, H, last_obs=None, states=False, start=False):
+        """sim_future_obs(num_future_steps) of the model object: y[H, N] (ParticleFilterBank.sim_future_obs of the one filter)."""
+        out = self._bank.sim_future_obs(H, last_obs, states, start)
+        return out[0] if not isinstance(out, tuple) else tuple(o[0] for o in out)
 
     @property
     def bank(self):
@@ -347,6 +372,13 @@ class SwarmWithCovs:
 
     def getExpectations(self):
         return list(self._exp)
+
+    def simFutureObs(self, num_future_steps, last_obs=None, states=False, start=False):
+        """Swarm::simFutureObs / SwarmWithCovs::simFutureObs (pswarm_filter.h:247-253, 547-553): sim_future_obs of every member,
+        here ONE device call for all of them; y[member, time, state particle].  last_obs: the last observation (leverage members)."""
+        if self._bank is None:
+            self._finish_construction()
+        return self._bank.sim_future_obs(num_future_steps, last_obs, states, start)
 
     def close(self):
         if self._bank is not None:
@@ -508,6 +540,27 @@ class svol_lw_1_par:
 
     def getParamSamples(self, f=0):
         return self.state(f)["theta"]
+
+    def sim_future_obs(self, H, last_obs, states=False, start=False, prop=False):
+        """sim_future_obs(num_future_steps) of the *FutureSimulator add-ons (liu_west_filter.h:1315-1363), on the device
+        (ssme_lw_sim_future_obs): y[R, H, N].  last_obs: the last observation, a scalar or one value per filter.  states / start /
+        prop: also return the simulated states x[R, H, N] / the ancestors [R, N] of the start draw / [R, 16] = theta-bar[4] and
+        the Cholesky factor L[10] (lower triangle by rows) of the start population as used."""
+        H = int(H)
+        lo = np.ascontiguousarray(np.broadcast_to(np.asarray(last_obs, dtype=np.float64), (self.r,)))
+        y = np.empty((self.r, max(H, 0), self.n))
+        x = np.empty_like(y) if states else None
+        st = np.empty((self.r, self.n), dtype=np.uint32) if start else None
+        pr = np.empty((self.r, 16)) if prop else None
+        self._chk(capi.lib().ssme_lw_sim_future_obs(self._h, H, capi.dptr(lo), capi.dptr(y), capi.dptr(x), capi.u32ptr(st), capi.dptr(pr)))
+        out = (y,) + ((x,) if states else ()) + ((st,) if start else ()) + ((pr,) if prop else ())
+        return y if len(out) == 1 else out
+
+    def forecast_elapsed_ms(self):
+        """HIP-event times (ms) of the last sim_future_obs: (horizon kernel alone, whole call without the download)."""
+        a, b = C.c_float(), C.c_float()
+        self._chk(capi.lib().ssme_lw_forecast_elapsed_ms(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def last_elapsed_ms(self):
         ms = C.c_float()
