@@ -97,7 +97,12 @@ static hipError_t own_alloc(HandleCore* h, T*& p, size_t bytes, Mem kind = Mem::
     if (e != hipSuccess) return e;
     h->owned.emplace_back(q, kind == Mem::pinned);
     p = static_cast<T*>(q);
-    return kind == Mem::zeroed ? hipMemset(q, 0, bytes) : hipSuccess;
+    if (kind != Mem::zeroed) return hipSuccess;
+    // hipMemset of device memory may return before the fill has run, and the handle's stream is non-blocking: it does not wait for
+    // the null stream.  Wait here, so that the fill cannot land after a kernel queued on the handle's stream next (the first
+    // forecast of a handle: S' of k_level2_plan was zeroed again between k_fc_start and k_fc_horizon, which then wrote NaN).
+    e = hipMemset(q, 0, bytes);
+    return e != hipSuccess ? e : hipStreamSynchronize(nullptr);
 }
 
 static int create_stream(HandleCore* h) {
