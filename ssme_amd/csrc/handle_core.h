@@ -1,10 +1,13 @@
 // handle_core.h -- host state and plumbing that the two filter handles of pf_api.hip share (the bootstrap handle ssme_pf_s and
 // the Liu-West handle ssme_lw_s both derive from HandleCore): tile layout, stream and events, device buffers owned by the
-// handle, error reporting, and the entry points that both C ABIs offer under their own names.
+// handle, the dynamic-LDS grants of the kernels (grant_lds), error reporting, the launches and shard bookkeeping that both filters
+// repeat, and the entry points that both C ABIs offer under their own names.
 #pragma once
 #include "../../include/ssme_pf.h"
 #include "pf_kernels.h"
 
+#include <map>
+#include <mutex>
 #include <string>
 #include <type_traits>
 #include <utility>
@@ -105,6 +108,26 @@ static hipError_t own_alloc(HandleCore* h, T*& p, size_t bytes, Mem kind = Mem::
     return e != hipSuccess ? e : hipStreamSynchronize(nullptr);
 }
 
+// The dynamic-LDS ceiling of a kernel is state of the (kernel, device) pair, shared by every handle of the process: it is only
+// ever raised (a handle with few tiles must not lower what a handle with many tiles was granted).  Every grant of the library
+// goes through here, at handle creation (not inside a stream capture), with `device` current; handles are created from several
+// threads (the swarm adaptor's pool), hence the lock.
+static hipError_t grant_lds(const void* kernel, size_t bytes, int device) {
+    static std::mutex mu;
+    static std::map<std::pair<const void*, int>, size_t> granted;
+    std::lock_guard<std::mutex> lock(mu);
+    size_t& have = granted[{kernel, device}];
+    if (bytes <= have) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e == hipSuccess) have = bytes;
+    return e;
+}
+// the two split level-2 kernels that take a handle's lds_bytes_plan
+static hipError_t grant_plan_lds(const HandleCore* h, int device) {
+    const hipError_t e = grant_lds(reinterpret_cast<const void*>(&k_level2_plan), h->lds_bytes_plan, device);
+    return e != hipSuccess ? e : grant_lds(reinterpret_cast<const void*>(&k_l2_ranges), h->lds_bytes_plan, device);
+}
+
 static int create_stream(HandleCore* h) {
     HIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     h->own_stream = h->stream;
@@ -153,6 +176,34 @@ static size_t own_particles(const HandleCore* h) {
     return (size_t)h->N - first < own ? (size_t)h->N - first : own;
 }
 
+// what the two *_shard_create functions check before the handle exists: one filter of n_particles over `world` ranks
+static int shard_create_check(int n_particles, int n_filters, int rank, int world) {
+    if (world < 1 || world > 64 || rank < 0 || rank >= world) return SSME_ERR_INVALID_ARG;
+    if (n_filters != 1 || n_particles < 1) return SSME_ERR_UNSUPPORTED;
+    Layout l;
+    return set_layout(&l, n_particles, 1, kTile, rank, world) ? SSME_OK : SSME_ERR_UNSUPPORTED;   // every rank must own a tile
+}
+
+// flag and widest reaches of the last native series (`ran`: the driver has allocated its buffers)
+static int shard_stats(const HandleCore* h, bool ran, int32_t* out4) {
+    if (!h || !out4) return SSME_ERR_INVALID_ARG;
+    if (h->shard_world < 1 || !ran) return SSME_ERR_STATE;
+    out4[0] = h->sh_stats[3]; out4[1] = h->sh_stats[0]; out4[2] = h->sh_stats[1]; out4[3] = h->sh_stats[2];
+    return SSME_OK;
+}
+
+// split level-2 of a sharded filter: every tile's source range is in l2_lo / l2_hi; a rank's window is [lo of its first tile,
+// hi of its last].  Queues the 2 x world downloads into `stage` ([world][2], pinned).
+static int enqueue_window_download(HandleCore* h, const int32_t* l2_lo, const int32_t* l2_hi, int32_t* stage) {
+    const size_t Bl = h->sh_Bl;
+    for (int d = 0; d < h->shard_world; ++d) {
+        const size_t last = (d + 1) * Bl - 1 < (size_t)h->B - 1 ? (d + 1) * Bl - 1 : (size_t)h->B - 1;     // the last rank may own fewer tiles
+        HIPCHK(hipMemcpyAsync(stage + 2 * d, l2_lo + d * Bl, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipMemcpyAsync(stage + 2 * d + 1, l2_hi + last, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    }
+    return SSME_OK;
+}
+
 static int shard_layout(const HandleCore* h, int32_t* out4) {
     if (!h || !out4) return SSME_ERR_INVALID_ARG;
     if (h->shard_world < 1) return SSME_ERR_STATE;
@@ -199,6 +250,21 @@ static int step_gamma_row(H* h, void (*draw)(H* h, int t0, int nT)) {
         h->gamma_t0 = h->t; h->gamma_rows = kStepGammaChunk;
     }
     return h->t - h->gamma_t0;
+}
+
+
+// Gamma tables of one multinomial draw for time indices t0 .. t0+nT-1 into table rows 0 .. nT-1: the draws (Philox stream
+// `draw_stream`), then their prefix sums and totals (`extra_stream`)
+static void launch_gamma_tables(HandleCore* h, double* gam, double* pgam, double* gtot, uint32_t draw_stream, uint32_t extra_stream,
+                                int tile, uint32_t first_filter, int t0, int nT) {
+    hipLaunchKernelGGL(k_gamma_draw, dim3((h->B + kThreads - 1) / kThreads, nT, h->R), dim3(kThreads), 0, h->stream,
+                       gam, h->N, h->B, h->R, t0, (const uint32_t*)h->keybuf, first_filter, draw_stream, tile);
+    if (h->B <= 64)           // short rows: one thread per row; else one workgroup per row
+        hipLaunchKernelGGL(k_gamma_prefix_rows, dim3((nT * h->R + kThreads - 1) / kThreads), dim3(kThreads), 0, h->stream,
+                           (const double*)gam, pgam, gtot, h->B, h->R, nT, t0, (const uint32_t*)h->keybuf, first_filter, extra_stream);
+    else
+        hipLaunchKernelGGL(k_gamma_prefix, dim3(nT * h->R), dim3(kThreads), 0, h->stream,
+                           (const double*)gam, pgam, gtot, h->B, h->R, nT, t0, (const uint32_t*)h->keybuf, first_filter, extra_stream);
 }
 
 }  // namespace ssme

@@ -10,7 +10,6 @@
 #include "handle_core.h"
 #include "shard_driver.h"
 
-#include <atomic>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -22,8 +21,13 @@
 
 using namespace ssme;
 
+// k_filter_step of one (model, tile): fn[BIG][WL2][RS + 1] at the tile's own workgroup size nt (no BIG + WL2 kernel), and the
+// general 2048-particle kernel at 256 / 1024 threads (ssme_pf_set_tuning)
+struct StepKernels { const void* fn[2][2][3]; const void* wide[2]; int nt; };
+
 struct ssme_pf_s : HandleCore {
     ssme_pf_config cfg;
+    StepKernels kern;        // resolved at creation: what the handle launches and what it is granted
     bool params_set;
     int debug_anc, keep_logw;
     int graph_mode;
@@ -238,99 +242,79 @@ static int default_tile(int n_particles, int n_filters) {
     return kTile;
 }
 
-// One launcher per instantiation of the step kernel.  The dynamic-LDS ceiling of a kernel is process-wide state: it is
-// only ever raised (a handle with few tiles must not lower what a handle with many tiles was granted).
-static thread_local int g_grant_only = 0;      // != 0: launch_k only raises the LDS ceiling (handle creation); 1 general kernel, 2 / 3 the RS = 0 / 1 variants
-template <int MODEL, int NT, bool BIG, int TILE, int RS, bool WL2 = false>
-static void launch_k(ssme_pf_handle h, const StepArgs& a, dim3 grid, size_t lds) {
-    static std::atomic<size_t> granted{0};
-    auto kern = &k_filter_step<MODEL, NT, BIG, TILE, RS, WL2>;
-    if (lds > granted.load(std::memory_order_relaxed)) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        granted.store(lds, std::memory_order_relaxed);
+// cfg.model as a compile-time model id: f(std::integral_constant<int, MODEL_...>) for the handle's model
+template <class F>
+static void with_model(int model, F&& f) {
+    switch (model) {
+        case SSME_MODEL_SVOL: f(std::integral_constant<int, MODEL_SVOL>{}); break;
+        case SSME_MODEL_SVOL_LEVERAGE: f(std::integral_constant<int, MODEL_SVOL_LEVERAGE>{}); break;
+#if SSME_HAS_USER_MODEL
+        case SSME_MODEL_USER0: f(std::integral_constant<int, MODEL_USER0>{}); break;
+#endif
+        default: f(std::integral_constant<int, MODEL_LIN_GAUSS>{}); break;
     }
-    if (g_grant_only) return;
-    hipLaunchKernelGGL(kern, grid, dim3(NT), lds, h->stream, a);
 }
 
-// RS: the common configurations (multinomial -- the reference's -- or systematic resampling, every step, t > 0, no debug
-// outputs) have their own instantiations; returns the RS template argument or -1 for the general kernel
-static int hot_config(ssme_pf_handle h, const StepArgs& a) {
-    if (g_grant_only) return g_grant_only - 2;                       // 1 -> -1 (general), 2 -> 0, 3 -> 1
-    if (h->cfg.resamp_sched != 1 || a.t <= 0 || a.anc || a.logw || a.ticket) return -1;
-    return h->cfg.resampler == SSME_RESAMP_MULTINOMIAL ? 0 : (h->cfg.resampler == SSME_RESAMP_SYSTEMATIC ? 1 : -1);
+// The instantiations of k_filter_step one (model, tile) has.  RS: the common configurations (multinomial -- the reference's --
+// or systematic resampling, every step, t > 0, no debug outputs) have their own instantiations, -1 is the general kernel.
+// WL2: filters of at most 128 tiles take the level-2 wave by wave; BIG (split level-2) has no such variant.
+template <int MODEL, int NT, int TILE, bool BIG, bool WL2>
+static void fill_rs(const void* (&fn)[3]) {
+    fn[0] = reinterpret_cast<const void*>(&k_filter_step<MODEL, NT, BIG, TILE, -1, WL2>);
+    fn[1] = reinterpret_cast<const void*>(&k_filter_step<MODEL, NT, BIG, TILE, 0, WL2>);
+    fn[2] = reinterpret_cast<const void*>(&k_filter_step<MODEL, NT, BIG, TILE, 1, WL2>);
 }
-
-template <int MODEL, int NT, bool BIG, int TILE, bool WL2>
-static void launch_rs_w(ssme_pf_handle h, const StepArgs& a, dim3 grid, size_t lds, int rs) {
-    if (rs == 0) launch_k<MODEL, NT, BIG, TILE, 0, WL2>(h, a, grid, lds);
-    else if (rs == 1) launch_k<MODEL, NT, BIG, TILE, 1, WL2>(h, a, grid, lds);
-    else launch_k<MODEL, NT, BIG, TILE, -1, WL2>(h, a, grid, lds);
+template <int MODEL, int NT, int TILE>
+static void fill_step_kernels(StepKernels& k) {
+    k.nt = NT;
+    fill_rs<MODEL, NT, TILE, false, false>(k.fn[0][0]);
+    fill_rs<MODEL, NT, TILE, false, true>(k.fn[0][1]);
+    fill_rs<MODEL, NT, TILE, true, false>(k.fn[1][0]);
 }
-// WL2: filters of at most 128 tiles take the level-2 wave by wave (k_filter_step); its own instantiations
-template <int MODEL, int NT, bool BIG, int TILE>
-static void launch_rs(ssme_pf_handle h, const StepArgs& a, dim3 grid, size_t lds, int rs) {
-    if (BIG) { launch_rs_w<MODEL, NT, BIG, TILE, false>(h, a, grid, lds, rs); return; }
-    if (g_grant_only || a.B <= 128) launch_rs_w<MODEL, NT, false, TILE, true>(h, a, grid, lds, rs);
-    if (g_grant_only || a.B > 128) launch_rs_w<MODEL, NT, false, TILE, false>(h, a, grid, lds, rs);
-}
-
 template <int MODEL>
-static void launch_step_grid(ssme_pf_handle h, const StepArgs& a, dim3 grid) {
-    const int rs = hot_config(h, a);
-    if (h->tile == kTileSmall) {
-        if (h->split_l2) launch_rs<MODEL, 256, true, kTileSmall>(h, a, grid, h->lds_bytes_big, rs);
-        else launch_rs<MODEL, 256, false, kTileSmall>(h, a, grid, h->lds_bytes, rs);
-        return;
+static StepKernels step_kernels(int tile) {
+    StepKernels k{};
+    if (tile == kTileSmall) fill_step_kernels<MODEL, 256, kTileSmall>(k);
+    else if (tile == kTileMid) fill_step_kernels<MODEL, 512, kTileMid>(k);      // 1024-particle tiles: 512 threads, one particle pair each
+    else {
+        fill_step_kernels<MODEL, 512, kTile>(k);
+        k.wide[0] = reinterpret_cast<const void*>(&k_filter_step<MODEL, 256, false, kTile, -1>);
+        k.wide[1] = reinterpret_cast<const void*>(&k_filter_step<MODEL, 1024, false, kTile, -1>);
     }
-    if (h->tile == kTileMid) {      // 1024-particle tiles: 512 threads, one particle pair each
-        if (h->split_l2) launch_rs<MODEL, 512, true, kTileMid>(h, a, grid, h->lds_bytes_big, rs);
-        else launch_rs<MODEL, 512, false, kTileMid>(h, a, grid, h->lds_bytes, rs);
-        return;
-    }
-    if (h->split_l2) { launch_rs<MODEL, 512, true, kTile>(h, a, grid, h->lds_bytes_big, rs); return; }
-    switch (h->nt) {
-        case 256: launch_k<MODEL, 256, false, kTile, -1>(h, a, grid, h->lds_bytes); break;
-        case 512: launch_rs<MODEL, 512, false, kTile>(h, a, grid, h->lds_bytes, rs); break;
-        default: launch_k<MODEL, 1024, false, kTile, -1>(h, a, grid, h->lds_bytes); break;
-    }
+    return k;
+}
+// every kernel of the handle's table gets its LDS ceiling (handle creation)
+static hipError_t grant_step_lds(const ssme_pf_s* h) {
+    hipError_t e = hipSuccess;
+    for (int big = 0; big < 2; ++big)
+        for (int wl2 = 0; wl2 < 2; ++wl2)
+            for (const void* fn : h->kern.fn[big][wl2])
+                if (fn && e == hipSuccess) e = grant_lds(fn, big ? h->lds_bytes_big : h->lds_bytes, h->cfg.device);
+    for (const void* fn : h->kern.wide)
+        if (fn && e == hipSuccess) e = grant_lds(fn, h->lds_bytes, h->cfg.device);
+    return e;
+}
+
+// the kernel of the handle's table that runs the step `a` describes, its workgroup size and dynamic LDS
+struct StepLaunch { const void* fn; int nt; size_t lds; };
+static StepLaunch select_step_kernel(const ssme_pf_s* h, const StepArgs& a) {
+    int rs = -1;
+    if (h->cfg.resamp_sched == 1 && a.t > 0 && !a.anc && !a.logw && !a.ticket)
+        rs = h->cfg.resampler == SSME_RESAMP_MULTINOMIAL ? 0 : (h->cfg.resampler == SSME_RESAMP_SYSTEMATIC ? 1 : -1);
+    if (h->split_l2) return {h->kern.fn[1][0][rs + 1], h->kern.nt, h->lds_bytes_big};
+    if (h->tile == kTile && h->nt != 512) return {h->kern.wide[h->nt == 1024], h->nt, h->lds_bytes};      // ssme_pf_set_tuning
+    return {h->kern.fn[0][a.B <= 128 ? 1 : 0][rs + 1], h->kern.nt, h->lds_bytes};
 }
 static void launch_step_on(ssme_pf_handle h, const StepArgs& a, dim3 grid) {
-    switch (h->cfg.model) {
-        case SSME_MODEL_SVOL: launch_step_grid<MODEL_SVOL>(h, a, grid); break;
-        case SSME_MODEL_SVOL_LEVERAGE: launch_step_grid<MODEL_SVOL_LEVERAGE>(h, a, grid); break;
-#if SSME_HAS_USER_MODEL
-        case SSME_MODEL_USER0: launch_step_grid<MODEL_USER0>(h, a, grid); break;
-#endif
-        default: launch_step_grid<MODEL_LIN_GAUSS>(h, a, grid); break;
-    }
+    const StepLaunch k = select_step_kernel(h, a);
+    void* args[] = {const_cast<StepArgs*>(&a)};
+    hipLaunchKernel(k.fn, grid, dim3(k.nt), args, k.lds, h->stream);
 }
 static void launch_step(ssme_pf_handle h, const StepArgs& a) { launch_step_on(h, a, dim3(h->B, h->R)); }
-// every instantiation this handle can launch gets its LDS ceiling now (not inside a stream capture)
-static void grant_step_lds(ssme_pf_handle h) {
-    const int nt0 = h->nt, sp0 = h->split_l2;
-    StepArgs a{};
-    for (int hot = 1; hot <= 3; ++hot)
-        for (int sp = 0; sp < 2; ++sp)
-            for (int nt : {256, 512, 1024}) {
-                g_grant_only = hot; h->split_l2 = sp; h->nt = nt;
-                launch_step_on(h, a, dim3(1, 1));
-            }
-    g_grant_only = 0; h->nt = nt0; h->split_l2 = sp0;
-}
 // Gamma tables for time indices t0 .. t0+nT-1 into table rows 0 .. nT-1
 static void launch_gamma(ssme_pf_handle h, int t0, int nT) {
     if (h->cfg.resampler != SSME_RESAMP_MULTINOMIAL) return;
-    hipLaunchKernelGGL(k_gamma_draw, dim3((h->B + kThreads - 1) / kThreads, nT, h->R), dim3(kThreads), 0, h->stream,
-                       h->gam, h->N, h->B, h->R, t0, (const uint32_t*)h->keybuf, h->cfg.first_filter_id, (uint32_t)STREAM_GAMMA, h->tile);
-    if (h->B <= 64)
-        hipLaunchKernelGGL(k_gamma_prefix_rows, dim3((nT * h->R + kThreads - 1) / kThreads), dim3(kThreads), 0, h->stream,
-                           h->gam, h->pgam, h->gtot, h->B, h->R, nT, t0, (const uint32_t*)h->keybuf, h->cfg.first_filter_id,
-                           (uint32_t)STREAM_RESAMP_EXTRA);
-    else
-        hipLaunchKernelGGL(k_gamma_prefix, dim3(nT * h->R), dim3(kThreads), 0, h->stream,
-                           h->gam, h->pgam, h->gtot, h->B, h->R, nT, t0, (const uint32_t*)h->keybuf, h->cfg.first_filter_id,
-                           (uint32_t)STREAM_RESAMP_EXTRA);
+    launch_gamma_tables(h, h->gam, h->pgam, h->gtot, STREAM_GAMMA, STREAM_RESAMP_EXTRA, h->tile, h->cfg.first_filter_id, t0, nT);
 }
 // the split level-2 of one draw: one workgroup per filter up to 1024 tiles, several above (k_l2_scan_blocks + k_l2_ranges)
 static void launch_level2(hipStream_t st, const StepArgs& a, int n_filters, size_t lds, int ranges) {
@@ -400,14 +384,7 @@ static void enqueue_series_small(ssme_pf_handle h, int T, bool has_z) {
     a.z = has_z ? h->zbuf : nullptr;
     a.per_step = h->per_step;
     a.small_ms = h->small_ms;
-    switch (h->cfg.model) {
-        case SSME_MODEL_SVOL: launch_small_m<MODEL_SVOL>(h, a, T); break;
-        case SSME_MODEL_SVOL_LEVERAGE: launch_small_m<MODEL_SVOL_LEVERAGE>(h, a, T); break;
-#if SSME_HAS_USER_MODEL
-        case SSME_MODEL_USER0: launch_small_m<MODEL_USER0>(h, a, T); break;
-#endif
-        default: launch_small_m<MODEL_LIN_GAUSS>(h, a, T); break;
-    }
+    with_model(h->cfg.model, [&](auto m) { launch_small_m<decltype(m)::value>(h, a, T); });
     h->cur = 1;
 }
 
@@ -499,10 +476,11 @@ static int user_expectations_checked(ssme_pf_handle h) {
 #endif
 }
 
-// the horizon kernel of a forecast (forecast.h), one instantiation per built-in model
+// the horizon kernel of a forecast (forecast.h), one instantiation per built-in model (user models declare no observation draw)
 template <int MODEL>
 static void launch_fc_horizon(ssme_pf_handle h, const FcArgs& a) {
-    hipLaunchKernelGGL((k_fc_horizon<MODEL>), dim3((a.Ns / 2 + kFcNT - 1) / kFcNT, h->R), dim3(kFcNT), 0, h->stream, a);
+    if constexpr (MODEL != MODEL_USER0)
+        hipLaunchKernelGGL((k_fc_horizon<MODEL>), dim3((a.Ns / 2 + kFcNT - 1) / kFcNT, h->R), dim3(kFcNT), 0, h->stream, a);
 }
 
 extern "C" {
@@ -550,7 +528,8 @@ static int create_impl(const ssme_pf_config* cfg, int shard_rank, int shard_worl
     h->small_series = 1;
     dims_of(cfg->model, &h->dx, &h->dy);
     if (h->dx > 1 || h->dy > 1) h->small_series = 0;             // vector models run the tiled step kernel at every N
-    h->nt = tile == kTileSmall ? 256 : 512;
+    with_model(cfg->model, [&](auto m) { h->kern = step_kernels<decltype(m)::value>(tile); });
+    h->nt = h->kern.nt;
     hipError_t e = hipSetDevice(cfg->device);
     if (e != hipSuccess) { delete h; return SSME_ERR_HIP; }
     {
@@ -568,12 +547,8 @@ static int create_impl(const ssme_pf_config* cfg, int shard_rank, int shard_worl
             HIPCHK(own_alloc(h, h->tsum[i], sizeof(double) * nb, Mem::zeroed));
             HIPCHK(own_alloc(h, h->tmax[i], sizeof(double) * nb, Mem::zeroed));
         }
-        grant_step_lds(h);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_level2_plan), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)h->lds_bytes_plan));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_l2_ranges), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)h->lds_bytes_plan));
+        HIPCHK(grant_step_lds(h));
+        HIPCHK(grant_plan_lds(h, cfg->device));
         HIPCHK(own_alloc(h, h->l2_work, sizeof(double) * (nb + (size_t)h->R * kL2Scratch + 32), Mem::zeroed));
         HIPCHK(own_alloc(h, h->l2_T, sizeof(double) * nb));
         HIPCHK(own_alloc(h, h->l2_R, sizeof(double) * nb));
@@ -645,11 +620,9 @@ int ssme_pf_default_tile(int32_t n_particles, int32_t bank_filters) { return def
 // are the caller's (device pointers), so that the host side can hand the same memory to its collective library.
 int ssme_pf_shard_create(const ssme_pf_config* cfg, int32_t rank, int32_t world, ssme_pf_handle* out) {
     if (!cfg || !out) return SSME_ERR_INVALID_ARG;
-    if (world < 1 || world > 64 || rank < 0 || rank >= world) return SSME_ERR_INVALID_ARG;
-    if (cfg->n_filters != 1 || cfg->resamp_sched < 1) return SSME_ERR_UNSUPPORTED;
-    if (cfg->n_particles < 1) return SSME_ERR_UNSUPPORTED;
-    Layout l;
-    if (!set_layout(&l, cfg->n_particles, 1, kTile, rank, world)) return SSME_ERR_UNSUPPORTED;   // every rank must own a tile
+    const int rc = shard_create_check(cfg->n_particles, cfg->n_filters, rank, world);
+    if (rc != SSME_OK) return rc;
+    if (cfg->resamp_sched < 1) return SSME_ERR_UNSUPPORTED;
     return create_impl(cfg, rank, world, out);
 }
 
@@ -712,18 +685,12 @@ int ssme_pf_shard_plan(ssme_pf_handle h, const double* tsum_all, const double* t
     shard_plan_device(h, t, tsum_all, tmax_all);
     HIPCHK(hipGetLastError());
     int32_t* stage = reinterpret_cast<int32_t*>(h->pin + 2 + h->R);            // pinned
-    if (h->split_l2) {
-        // more than 1024 tiles in total: the split level-2 plans every tile; a rank's window is [lo of its first tile, hi of its last]
-        const int Bl = h->sh_Bl;
-        const bool sorted = h->cfg.resampler != SSME_RESAMP_MULTINOMIAL_IID;
-        for (int d = 0; d < h->shard_world; ++d) {
-            stage[2 * d] = 0; stage[2 * d + 1] = h->B - 1;
-            if (sorted) {
-                HIPCHK(hipMemcpyAsync(stage + 2 * d, h->l2_lo + (size_t)d * Bl, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-                const size_t last = (size_t)(d + 1) * Bl - 1 < (size_t)h->B - 1 ? (size_t)(d + 1) * Bl - 1 : (size_t)h->B - 1;     // the last rank may own fewer tiles
-                HIPCHK(hipMemcpyAsync(stage + 2 * d + 1, h->l2_hi + last, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-            }
-        }
+    if (h->split_l2 && h->cfg.resampler == SSME_RESAMP_MULTINOMIAL_IID) {
+        for (int d = 0; d < h->shard_world; ++d) { stage[2 * d] = 0; stage[2 * d + 1] = h->B - 1; }      // unsorted targets need every tile
+    } else if (h->split_l2) {
+        // more than 1024 tiles in total: the split level-2 plans every tile
+        const int rc = enqueue_window_download(h, h->l2_lo, h->l2_hi, stage);
+        if (rc != SSME_OK) return rc;
     } else {
         HIPCHK(hipMemcpyAsync(stage, h->plan_dev, sizeof(int32_t) * 2 * h->shard_world, hipMemcpyDeviceToHost, h->stream));
     }
@@ -932,12 +899,7 @@ int ssme_pf_shard_download(ssme_pf_handle h, double* x_local, uint64_t* cdf_loca
     return SSME_OK;
 }
 
-int ssme_pf_shard_stats(ssme_pf_handle h, int32_t* out4) {
-    if (!h || !out4) return SSME_ERR_INVALID_ARG;
-    if (h->shard_world < 1 || !h->sh_x[0]) return SSME_ERR_STATE;
-    out4[0] = h->sh_stats[3]; out4[1] = h->sh_stats[0]; out4[2] = h->sh_stats[1]; out4[3] = h->sh_stats[2];
-    return SSME_OK;
-}
+int ssme_pf_shard_stats(ssme_pf_handle h, int32_t* out4) { return shard_stats(h, h && h->sh_x[0], out4); }
 
 int ssme_pf_set_params(ssme_pf_handle h, const double* theta, int32_t n_theta, int32_t n_rows) {
     if (!h || !theta) return SSME_ERR_INVALID_ARG;
@@ -1364,11 +1326,7 @@ int ssme_pf_sim_future_obs(ssme_pf_handle h, int32_t num_steps, const double* la
     a.N = N; a.Npad = h->Npad; a.Ns = Ns; a.B = h->B; a.Bs = h->Bs; a.Bpow2 = h->Bpow2; a.tile = h->tile; a.t0 = h->t; a.H = H;
     hipLaunchKernelGGL(k_fc_start, dim3(h->B, R), dim3(kFcNT), 0, h->stream, a);
     HIPCHK(hipEventRecord(h->fc_ev[1], h->stream));
-    switch (h->cfg.model) {
-        case SSME_MODEL_SVOL: launch_fc_horizon<MODEL_SVOL>(h, a); break;
-        case SSME_MODEL_SVOL_LEVERAGE: launch_fc_horizon<MODEL_SVOL_LEVERAGE>(h, a); break;
-        default: launch_fc_horizon<MODEL_LIN_GAUSS>(h, a); break;
-    }
+    with_model(h->cfg.model, [&](auto m) { launch_fc_horizon<decltype(m)::value>(h, a); });
     HIPCHK(hipEventRecord(h->fc_ev[2], h->stream));
     HIPCHK(hipGetLastError());
     const size_t rows = (size_t)R * H;
@@ -1697,37 +1655,28 @@ static int lw_ensure_capacity(ssme_lw_handle h, int T) {
 
 // Gamma tables of both draws for time indices t0 .. t0+nT-1 into rows 0 .. nT-1
 static void lw_launch_gamma(ssme_lw_handle h, int t0, int nT) {
-    const uint32_t* kp = h->keybuf;
-    const dim3 g1((h->B + kThreads - 1) / kThreads, nT, h->R);
-    const bool rows = h->B <= 64;                    // short rows: one thread per row; else one workgroup per row
-    const dim3 g2(rows ? (nT * h->R + kThreads - 1) / kThreads : nT * h->R);
-    auto prefix = [&](double* gam, double* pgam, double* gtot, uint32_t extra) {
-        if (rows) hipLaunchKernelGGL(k_gamma_prefix_rows, g2, dim3(kThreads), 0, h->stream, gam, pgam, gtot, h->B, h->R, nT, t0, kp,
-                                     h->cfg.first_filter_id, extra);
-        else hipLaunchKernelGGL(k_gamma_prefix, g2, dim3(kThreads), 0, h->stream, gam, pgam, gtot, h->B, h->R, nT, t0, kp,
-                                h->cfg.first_filter_id, extra);
-    };
-    hipLaunchKernelGGL(k_gamma_draw, g1, dim3(kThreads), 0, h->stream, h->gamB, h->N, h->B, h->R, t0, kp,
-                       h->cfg.first_filter_id, (uint32_t)STREAM_GAMMA, kTile);
-    prefix(h->gamB, h->pgamB, h->gtotB, (uint32_t)STREAM_RESAMP_EXTRA);
-    hipLaunchKernelGGL(k_gamma_draw, g1, dim3(kThreads), 0, h->stream, h->gamA, h->N, h->B, h->R, t0, kp,
-                       h->cfg.first_filter_id, (uint32_t)STREAM_GAMMA_K, kTile);
-    prefix(h->gamA, h->pgamA, h->gtotA, (uint32_t)STREAM_LW_K_EXTRA);
+    launch_gamma_tables(h, h->gamB, h->pgamB, h->gtotB, STREAM_GAMMA, STREAM_RESAMP_EXTRA, kTile, h->cfg.first_filter_id, t0, nT);
+    launch_gamma_tables(h, h->gamA, h->pgamA, h->gtotA, STREAM_GAMMA_K, STREAM_LW_K_EXTRA, kTile, h->cfg.first_filter_id, t0, nT);
 }
 
-// the stage kernels, with the reference test models' transform set compiled in when the handle has it
-template <bool BIG>
-static void lw_launch_stage1(ssme_lw_handle h, dim3 grid, size_t lds, const LwArgs& a) {
-    if (h->fixed_trans) hipLaunchKernelGGL((k_lw_stage1<BIG, true>), grid, dim3(kLwNT), lds, h->stream, a);
-    else hipLaunchKernelGGL((k_lw_stage1<BIG, false>), grid, dim3(kLwNT), lds, h->stream, a);
+// the stage kernels: stage 1 / 2, BIG (split level-2), FT (the reference test models' transform set compiled in)
+static const void* lw_stage_kernel(int stage, bool big, bool ft) {
+    static const void* const tab[2][2][2] = {
+        {{reinterpret_cast<const void*>(&k_lw_stage1<false, false>), reinterpret_cast<const void*>(&k_lw_stage1<false, true>)},
+         {reinterpret_cast<const void*>(&k_lw_stage1<true, false>), reinterpret_cast<const void*>(&k_lw_stage1<true, true>)}},
+        {{reinterpret_cast<const void*>(&k_lw_stage2<false, false>), reinterpret_cast<const void*>(&k_lw_stage2<false, true>)},
+         {reinterpret_cast<const void*>(&k_lw_stage2<true, false>), reinterpret_cast<const void*>(&k_lw_stage2<true, true>)}}};
+    return tab[stage - 1][big][ft];
 }
-template <bool BIG>
-static void lw_launch_stage2(ssme_lw_handle h, dim3 grid, size_t lds, const LwArgs& a) {
-    if (h->fixed_trans) hipLaunchKernelGGL((k_lw_stage2<BIG, true>), grid, dim3(kLwNT), lds, h->stream, a);
-    else hipLaunchKernelGGL((k_lw_stage2<BIG, false>), grid, dim3(kLwNT), lds, h->stream, a);
+static void lw_launch_stage(ssme_lw_handle h, int stage, dim3 grid, const LwArgs& a) {
+    void* args[] = {const_cast<LwArgs*>(&a)};
+    hipLaunchKernel(lw_stage_kernel(stage, h->split_l2, h->fixed_trans), grid, dim3(kLwNT), args,
+                    h->split_l2 ? h->lds_bytes_big : h->lds_bytes, h->stream);
 }
 
-static void lw_launch_plan(ssme_lw_handle h, int draw, int t, int gi, const double* tsum, const double* tmax, bool ranges) {
+// the StepArgs of a level-2 of draw 0 (resampling, second-stage weights, Gamma tables B) or 1 (k draw, first-stage weights, tables A)
+// from the given tile sums / maxima: what k_level2_plan / k_l2_scan_blocks / k_l2_ranges and k_shard_plan read
+static StepArgs lw_plan_args(ssme_lw_handle h, int draw, int t, int gi, const double* tsum, const double* tmax) {
     StepArgs a{};
     a.tsum_in = tsum; a.tmax_in = tmax;
     a.l2_T = h->l2T[draw]; a.l2_R = h->l2R[draw]; a.l2_lo = h->l2lo[draw]; a.l2_hi = h->l2hi[draw];
@@ -1738,7 +1687,21 @@ static void lw_launch_plan(ssme_lw_handle h, int draw, int t, int gi, const doub
     a.pgam = draw ? h->pgamA : h->pgamB; a.gtot = draw ? h->gtotA : h->gtotB;
     a.keyp = h->keybuf; a.first_filter = h->cfg.first_filter_id;
     a.l2_work = h->l2_work;
-    launch_level2(h->stream, a, h->shard_world > 0 ? 1 : h->R, h->lds_bytes_plan, ranges ? 1 : 0);
+    return a;
+}
+static void lw_launch_plan(ssme_lw_handle h, int draw, int t, int gi, const double* tsum, const double* tmax, bool ranges) {
+    launch_level2(h->stream, lw_plan_args(h, draw, t, gi, tsum, tmax), h->shard_world > 0 ? 1 : h->R, h->lds_bytes_plan, ranges ? 1 : 0);
+}
+
+// between the stages: theta-bar and the Cholesky factor of n_filters filters by one workgroup each (k_lw_mid); `totals`: the
+// moment totals by one wave per moment first
+static void lw_launch_mid(ssme_lw_handle h, LwArgs& a, int n_filters, bool totals) {
+    if (totals) {
+        a.momtot = h->momtot;
+        hipLaunchKernelGGL(k_lw_mom_totals, dim3(kNMom, n_filters), dim3(64), 0, h->stream, a);
+    }
+    if (h->split_l2) hipLaunchKernelGGL(k_lw_mid<true>, dim3(n_filters), dim3(kThreads), 0, h->stream, a);
+    else hipLaunchKernelGGL(k_lw_mid<false>, dim3(n_filters), dim3(kThreads), 0, h->stream, a);
 }
 
 static void lw_enqueue_step(ssme_lw_handle h, int t, int yi, int gi, bool record, bool finalize_prev, const double* yz_now = nullptr) {
@@ -1747,31 +1710,24 @@ static void lw_enqueue_step(ssme_lw_handle h, int t, int yi, int gi, bool record
     a.t = t; a.yi = yi; a.gi = gi; a.finalize_prev = finalize_prev ? 1 : 0;
     a.per_step = record ? h->per_step : nullptr;
     const dim3 grid(h->B, h->R);
-    const bool resampled = (t % h->rs) == 0;           // a resampling draw closes step t-1 (lazily: it runs at the start of step t)
     if (t == 0) {
         hipLaunchKernelGGL(k_lw_init, grid, dim3(kLwNT), 0, h->stream, a);
-    } else if (h->split_l2) {
-        lw_launch_plan(h, 0, t, gi, h->tsumB, h->tmaxB, resampled);
-        lw_launch_stage1<true>(h, grid, h->lds_bytes_big, a);
-        if (h->form == 0) lw_launch_plan(h, 1, t, gi, h->tsumA, h->tmaxA, true);
-        a.momtot = h->momtot;
-        hipLaunchKernelGGL(k_lw_mom_totals, dim3(kNMom, h->R), dim3(64), 0, h->stream, a);
-        hipLaunchKernelGGL(k_lw_mid<true>, dim3(h->R), dim3(kThreads), 0, h->stream, a);
-        lw_launch_stage2<true>(h, grid, h->lds_bytes_big, a);
-        if (a.compose) { std::swap(h->xB, h->xr); std::swap(h->thB, h->thr); }      // the new population is where stage 2 wrote it
+        return;
+    }
+    if (h->split_l2) {
+        // a resampling draw closes step t-1 only if t % rs == 0 (lazily: it runs at the start of step t)
+        lw_launch_plan(h, 0, t, gi, h->tsumB, h->tmaxB, (t % h->rs) == 0);
     } else {
         // two launches when the tile partials ([B][14] doubles) fit the window area of stage 2's LDS: every workgroup of stage 2
-        // then takes theta-bar and the Cholesky factor from them itself
+        // then takes theta-bar and the Cholesky factor from them itself.  Otherwise (586 .. 1024 tiles, and the split level-2):
+        // the totals by one wave per moment, then the one-workgroup rest
         a.fuse_mid = ((size_t)h->B * kNMom * sizeof(double) <= h->lds_bytes) ? 1 : 0;
-        lw_launch_stage1<false>(h, grid, h->lds_bytes, a);
-        if (!a.fuse_mid) {
-            a.momtot = h->momtot;                // 586 .. 1024 tiles: the totals by one wave per moment, then the one-workgroup rest
-            hipLaunchKernelGGL(k_lw_mom_totals, dim3(kNMom, h->R), dim3(64), 0, h->stream, a);
-            hipLaunchKernelGGL(k_lw_mid<false>, dim3(h->R), dim3(kThreads), 0, h->stream, a);
-        }
-        lw_launch_stage2<false>(h, grid, h->lds_bytes, a);
-        if (a.compose) { std::swap(h->xB, h->xr); std::swap(h->thB, h->thr); }
     }
+    lw_launch_stage(h, 1, grid, a);
+    if (h->split_l2 && h->form == 0) lw_launch_plan(h, 1, t, gi, h->tsumA, h->tmaxA, true);
+    if (!a.fuse_mid) lw_launch_mid(h, a, h->R, true);
+    lw_launch_stage(h, 2, grid, a);
+    if (a.compose) { std::swap(h->xB, h->xr); std::swap(h->thB, h->thr); }      // the new population is where stage 2 wrote it
 }
 static void lw_enqueue_finalize(ssme_lw_handle h, int t, bool record, double* ll_host = nullptr) {
     LwArgs a = lw_args(h);
@@ -1836,10 +1792,11 @@ static int lw_create_impl(const ssme_lw_config* cfg, int shard_rank, int shard_w
             HIPCHK(own_alloc(h, h->l2hi[d], sizeof(int32_t) * nb, Mem::zeroed));
             HIPCHK(own_alloc(h, h->l2s[d], sizeof(FilterScalars) * (size_t)h->R, Mem::zeroed));
         }
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_level2_plan), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)h->lds_bytes_plan));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_l2_ranges), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)h->lds_bytes_plan));
+        HIPCHK(grant_plan_lds(h, cfg->device));
+        for (int stage = 1; stage <= 2; ++stage)
+            for (int big = 0; big < 2; ++big)
+                for (int ft = 0; ft < 2; ++ft)
+                    HIPCHK(grant_lds(lw_stage_kernel(stage, big, ft), big ? h->lds_bytes_big : h->lds_bytes, cfg->device));
         if (h->shard_world == 0) {               // a sharded handle works on the caller's buffers
             for (double** p : {&h->xB, &h->xr, &h->lw1, &h->cdfA, &h->cdfB}) HIPCHK(own_alloc(h, *p, sizeof(double) * np, Mem::zeroed));
             if (h->rs > 1) HIPCHK(own_alloc(h, h->lwB, sizeof(double) * np, Mem::zeroed));
@@ -1865,14 +1822,6 @@ static int lw_create_impl(const ssme_lw_config* cfg, int shard_rank, int shard_w
             const uint32_t k[2] = {(uint32_t)h->cfg.seed, (uint32_t)(h->cfg.seed >> 32)};
             HIPCHK(hipMemcpy(h->keybuf, k, sizeof(k), hipMemcpyHostToDevice));
         }
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lw_stage1<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lw_stage2<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lw_stage1<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes_big));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lw_stage2<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes_big));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lw_stage1<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lw_stage2<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lw_stage1<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes_big));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lw_stage2<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes_big));
         rc2 = lw_ensure_capacity(h, 1);
         if (rc2 != SSME_OK) return rc2;
         return lw_reset(h);
@@ -1890,12 +1839,8 @@ int ssme_lw_create(const ssme_lw_config* cfg, ssme_lw_handle* out) { return lw_c
 // in tile order by every rank (k_lw_mid), so theta-bar, the Cholesky factor and all draws equal the unsharded filter's.
 int ssme_lw_shard_create(const ssme_lw_config* cfg, int32_t rank, int32_t world, ssme_lw_handle* out) {
     if (!cfg || !out) return SSME_ERR_INVALID_ARG;
-    if (world < 1 || world > 64 || rank < 0 || rank >= world) return SSME_ERR_INVALID_ARG;
-    if (cfg->n_filters != 1) return SSME_ERR_UNSUPPORTED;
-    if (cfg->n_particles < 1) return SSME_ERR_UNSUPPORTED;
-    Layout l;
-    if (!set_layout(&l, cfg->n_particles, 1, kTile, rank, world)) return SSME_ERR_UNSUPPORTED;   // every rank must own a tile
-    return lw_create_impl(cfg, rank, world, out);
+    const int rc = shard_create_check(cfg->n_particles, cfg->n_filters, rank, world);
+    return rc != SSME_OK ? rc : lw_create_impl(cfg, rank, world, out);
 }
 
 int ssme_lw_shard_layout(ssme_lw_handle h, int32_t* out4) { return shard_layout(h, out4); }
@@ -1958,27 +1903,14 @@ int ssme_lw_shard_plan(ssme_lw_handle h, int32_t which, int32_t t, const double*
     if (h->split_l2) {
         lw_launch_plan(h, which, t, t, tsum_all, tmax_all, true);
         HIPCHK(hipGetLastError());
-        const int Bl = h->sh_Bl;
-        for (int d = 0; d < h->shard_world; ++d) {
-            const size_t last = (size_t)(d + 1) * Bl - 1 < (size_t)h->B - 1 ? (size_t)(d + 1) * Bl - 1 : (size_t)h->B - 1;
-            HIPCHK(hipMemcpyAsync(h->plan_pin + 2 * d, h->l2lo[which] + (size_t)d * Bl, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(hipMemcpyAsync(h->plan_pin + 2 * d + 1, h->l2hi[which] + last, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-        }
-        HIPCHK(wait_stream_low_latency(h->stream));
-        for (int d = 0; d < 2 * h->shard_world; ++d) lo_hi[d] = h->plan_pin[d];
-        return SSME_OK;
+        const int rc = enqueue_window_download(h, h->l2lo[which], h->l2hi[which], h->plan_pin);
+        if (rc != SSME_OK) return rc;
+    } else {
+        hipLaunchKernelGGL(k_shard_plan, dim3(1), dim3(512), sizeof(double) * (h->Bpow2 < 2 ? 2 : h->Bpow2), h->stream,
+                           lw_plan_args(h, which, t, t, tsum_all, tmax_all), h->shard_world, h->sh_Bl, h->plan_dev);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(h->plan_pin, h->plan_dev, sizeof(int32_t) * 2 * h->shard_world, hipMemcpyDeviceToHost, h->stream));
     }
-    StepArgs a{};                                   // the fields k_shard_plan reads
-    a.tsum_in = tsum_all; a.tmax_in = tmax_all;
-    a.B = h->B; a.Bs = h->Bs; a.Bpow2 = h->Bpow2; a.rshift = h->rshift; a.R = 1; a.N = h->N; a.tile = kTile;
-    a.resampler = RESAMP_MULTINOMIAL; a.resamp_sched = 1;
-    a.t = t; a.gi = t;
-    a.pgam = which ? h->pgamA : h->pgamB; a.gtot = which ? h->gtotA : h->gtotB;
-    a.keyp = h->keybuf; a.first_filter = h->cfg.first_filter_id;
-    hipLaunchKernelGGL(k_shard_plan, dim3(1), dim3(512), sizeof(double) * (h->Bpow2 < 2 ? 2 : h->Bpow2), h->stream, a,
-                       h->shard_world, h->sh_Bl, h->plan_dev);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(h->plan_pin, h->plan_dev, sizeof(int32_t) * 2 * h->shard_world, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(wait_stream_low_latency(h->stream));
     for (int d = 0; d < 2 * h->shard_world; ++d) lo_hi[d] = h->plan_pin[d];
     return SSME_OK;
@@ -1999,8 +1931,7 @@ int ssme_lw_shard_stage1(ssme_lw_handle h, int32_t t, int32_t win_tile0, int32_t
     a.win_tile0 = win_tile0; (void)win_tiles;
     a.xr = xr; a.thr = thr; a.lw1 = lw1; a.cdfA = cdfA; a.tsumA = tsumA; a.tmaxA = tmaxA; a.mom = mom;
     a.anc = anc;
-    if (h->split_l2) lw_launch_stage1<true>(h, dim3(h->sh_Bown, 1), h->lds_bytes_big, a);
-    else lw_launch_stage1<false>(h, dim3(h->sh_Bown, 1), h->lds_bytes, a);
+    lw_launch_stage(h, 1, dim3(h->sh_Bown, 1), a);
     HIPCHK(hipGetLastError());
     return SSME_OK;
 }
@@ -2012,16 +1943,7 @@ int ssme_lw_shard_mid(ssme_lw_handle h, int32_t t, const double* tsumA_all, cons
     LwArgs a = lw_shard_args(h, t);
     a.tsumA = const_cast<double*>(tsumA_all); a.tmaxA = const_cast<double*>(tmaxA_all); a.mom = const_cast<double*>(mom_all);
     // split level-2: the plan of the k draw (ssme_lw_shard_plan(which = 1)) must precede this call -- it provides m and S
-    if (h->split_l2) {
-        a.momtot = h->momtot;
-        hipLaunchKernelGGL(k_lw_mom_totals, dim3(kNMom, 1), dim3(64), 0, h->stream, a);
-        hipLaunchKernelGGL(k_lw_mid<true>, dim3(1), dim3(kThreads), 0, h->stream, a);
-    }
-    else if (h->B > 256) {
-        a.momtot = h->momtot;
-        hipLaunchKernelGGL(k_lw_mom_totals, dim3(kNMom, 1), dim3(64), 0, h->stream, a);
-        hipLaunchKernelGGL(k_lw_mid<false>, dim3(1), dim3(kThreads), 0, h->stream, a);
-    } else hipLaunchKernelGGL(k_lw_mid<false>, dim3(1), dim3(kThreads), 0, h->stream, a);
+    lw_launch_mid(h, a, 1, h->split_l2 || h->B > 256);
     HIPCHK(hipGetLastError());
     return SSME_OK;
 }
@@ -2040,8 +1962,7 @@ int ssme_lw_shard_stage2(ssme_lw_handle h, int32_t t, int32_t win_tile0, int32_t
     a.win_tile0 = win_tile0; (void)win_tiles;
     a.xB = xB; a.thB = thB; a.cdfB = cdfB; a.tsumB = tsumB; a.tmaxB = tmaxB;
     a.kidx = kidx;
-    if (h->split_l2) lw_launch_stage2<true>(h, dim3(h->sh_Bown, 1), h->lds_bytes_big, a);
-    else lw_launch_stage2<false>(h, dim3(h->sh_Bown, 1), h->lds_bytes, a);
+    lw_launch_stage(h, 2, dim3(h->sh_Bown, 1), a);
     HIPCHK(hipGetLastError());
     h->t = t + 1;
     return SSME_OK;
@@ -2171,12 +2092,7 @@ int ssme_lw_shard_download(ssme_lw_handle h, double* x_local, double* theta_loca
     return SSME_OK;
 }
 
-int ssme_lw_shard_stats(ssme_lw_handle h, int32_t* out4) {
-    if (!h || !out4) return SSME_ERR_INVALID_ARG;
-    if (h->shard_world < 1 || !h->sh_xB) return SSME_ERR_STATE;
-    out4[0] = h->sh_stats[3]; out4[1] = h->sh_stats[0]; out4[2] = h->sh_stats[1]; out4[3] = h->sh_stats[2];
-    return SSME_OK;
-}
+int ssme_lw_shard_stats(ssme_lw_handle h, int32_t* out4) { return shard_stats(h, h && h->sh_xB, out4); }
 
 int ssme_lw_get_loglik(ssme_lw_handle h, double* out) {
     if (!h || !out) return SSME_ERR_INVALID_ARG;
