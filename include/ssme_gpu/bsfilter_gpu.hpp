@@ -190,6 +190,16 @@ public:
         check(ssme_pf_get_user_expectations(h_.get(), out.data()), h_.get());
         return out;
     }
+    // sim_future_obs(num_future_steps) of the model's FutureSimulator add-on (test/test_pswarm.cpp:64-67, 112-116) after the last
+    // filter(), ON THE DEVICE, for a model whose header declares its observation draw (model_api.h: gsamp / gsamp_vec):
+    // y[time][component][particle], row-major (ssme_pf_sim_future_obs).  last_obs: the covariate of the first simulated step (the
+    // later ones read component 0 of the previous simulated observation).  Throws what check throws (std::runtime_error) when the
+    // linked library declares no draw (SSME_ERR_UNSUPPORTED of the call itself).
+    std::vector<double> sim_future_obs(unsigned num_steps, double last_obs = 0.0) {
+        std::vector<double> y((std::size_t)num_steps * dimy * nparts);
+        check(ssme_pf_sim_future_obs(h_.get(), (std::int32_t)num_steps, &last_obs, y.data(), nullptr, nullptr), h_.get());
+        return y;
+    }
     ssme_pf_handle native() const { return h_.get(); }
 
 private:

@@ -112,8 +112,13 @@ int ssme_pf_user_model_n_theta(void);
  * SSME_ERR_UNSUPPORTED and zeros without a user model.  With dim_y > 1 every y argument of this interface is dim_y values per time
  * step (run_series: y[t * dim_y + j]; step: dim_y values); with dim_x > 1 ssme_pf_download_state and ssme_pf_download_weights return
  * x[d * N + i] (dim_x planes; the weights are what a host-side functional h(x) of the whole state needs) and the device functionals
- * see component 0.  Vector models are unsharded, SSME_F64. */
+ * see component 0.  A forecast (ssme_pf_sim_future_obs, for a header that declares the observation draw) returns
+ * y_out[((r * num_steps + k) * dim_y + j) * N + i] and x_out[((r * num_steps + k) * dim_x + d) * N + i]; the covariate of a simulated
+ * step is component 0 of the previous simulated observation.  Vector models are unsharded, SSME_F64. */
 int ssme_pf_user_model_dims(int32_t* dim_x, int32_t* dim_y);
+/* 1 when the compiled-in user model declares its observation draw (gsamp, or gsamp_vec for a vector model: ssme_amd/csrc/model_api.h)
+ * and SSME_MODEL_USER0 handles can therefore be forecast; 0 for the stock library and for a header without the draw.  Needs no device. */
+int ssme_pf_user_model_has_gsamp(void);
 
 /* UNTRANSFORMED parameters, as the reference's model ctors receive them from
  * pack::get_untrans_params (univ_svol_bootstrap_filter.h:55-61).  theta is
@@ -230,10 +235,17 @@ int ssme_pf_last_elapsed_ms(ssme_pf_handle h, float* ms);
  * zero, -inf or NaN (e.g. `bad` parameters) gets NaN samples and the call returns SSME_OK.  The call changes nothing a later call on
  * the handle returns (buffers and Philox streams of its own: two forecasts from one origin return the same bits) and is ordered
  * behind steps queued with logcondlike_out = NULL.  SSME_F32 handles round last_obs on entry and every output to float.
- * Arguments are validated before any HIP call: NULL handle or y_out, num_steps < 1 or > 65535: SSME_ERR_INVALID_ARG; sharded handles
- * and SSME_MODEL_USER0 (user models declare no gSamp): SSME_ERR_UNSUPPORTED; before the first step: SSME_ERR_STATE. */
+ * SSME_MODEL_USER0 whose header declares the observation draw (ssme_pf_user_model_has_gsamp; gsamp / gsamp_vec of
+ * ssme_amd/csrc/model_api.h): the same start draw gathers all dim_x state planes, then  x <- prop / prop_vec(x, zs, zcov = y_prev[0]),
+ * y <- gsamp / gsamp_vec(x, zo),  y_prev <- y: the covariate of a simulated step is component 0 of the previous simulated
+ * observation (last_obs at the first horizon), the built-in leverage model's convention; a model with an exogenous covariate cannot
+ * be forecast.  Layouts: y_out[((r * num_steps + k) * dim_y + j) * N + i], x_out[((r * num_steps + k) * dim_x + d) * N + i],
+ * start_out[R][N]; with dim = 1 these are the layouts above, and a scalar user model consumes the random numbers a built-in one does.
+ * Arguments are validated before any HIP call: NULL handle or y_out, num_steps < 1 or > 65535: SSME_ERR_INVALID_ARG; sharded handles,
+ * and SSME_MODEL_USER0 when the compiled-in header declares no observation draw: SSME_ERR_UNSUPPORTED; before the first step:
+ * SSME_ERR_STATE. */
 int ssme_pf_sim_future_obs(ssme_pf_handle h, int32_t num_steps, const double* last_obs /*R or NULL*/,
-                           double* y_out /*[R][num_steps][N]*/, double* x_out /*same shape or NULL*/,
+                           double* y_out /*[R][num_steps][dim_y][N]*/, double* x_out /*[R][num_steps][dim_x][N] or NULL*/,
                            uint32_t* start_out /*[R][N] or NULL*/);
 /* HIP-event times (ms) of the last ssme_pf_sim_future_obs: the horizon kernel alone, and the whole call without the download. */
 int ssme_pf_forecast_elapsed_ms(ssme_pf_handle h, float* horizon_kernel_ms, float* call_ms);

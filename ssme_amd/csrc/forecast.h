@@ -14,6 +14,8 @@
 //                  the run-time loop over the horizon, one Philox call per particle and horizon (words 0-1 -> the pair
 //                  (z_state, z_obs) by pair_normals), one coalesced 16-byte store per lane and horizon into y[r][k][.]
 //                  (and x[r][k][.] when asked).  Tables of log / sincos / exp in LDS, as in the step kernels.
+// A user model that declares its observation draw (model_api.h: gsamp / gsamp_vec) runs the same pair on every state plane:
+//   k_fc_start_vec<DX>, k_fc_horizon_user<M, DX, DY> (below the built-in kernels).
 #pragma once
 #include "pf_kernels.h"
 #include "lw_kernels.h"
@@ -23,12 +25,13 @@ namespace ssme {
 // Counter streams of the forecast.  A counter is (particle, t0, filter id, stream + (k << 8)) with t0 = the origin (steps done
 // so far) and k = the horizon (0 for the start draw).  The filters' streams are all below 144 (ssme_math.h, lw_kernels.h,
 // model_api.h) and carry nothing above bit 7, so no forecast counter equals a filter counter; k < 2^16 keeps k << 8 inside the word.
-enum { STREAM_FC_START = 160, STREAM_FC_SIM = 161, STREAM_FC_LW_JIT = 162, STREAM_FC_LW_SIM = 163 };
+// STREAM_FC_SIM2: the second call of a user model with more than two state or observation components (k_fc_horizon_user).
+enum { STREAM_FC_START = 160, STREAM_FC_SIM = 161, STREAM_FC_LW_JIT = 162, STREAM_FC_LW_SIM = 163, STREAM_FC_SIM2 = 164 };
 constexpr int kFcMaxSteps = 65535;
 constexpr int kFcNT = 256;
 
 struct FcArgs {
-    const double* x;           // [R][Npad] particles of the last step (pre-resampling)
+    const double* x;           // [R][Npad] particles of the last step (pre-resampling); user models: [DX][R][Npad], as x0
     const double* cdf;         // [R][Npad] tile-local inclusive integer sums of their fixed-point weights
     const double* l2_T;        // [R][Bs] inclusive prefixes T'_b of the rescaled tile sums   (k_level2_plan, forecast's own buffers)
     const double* l2_R;        // [R][Bs] A_b / A'_b
@@ -38,8 +41,8 @@ struct FcArgs {
     const double* last_obs;    // [R] y_prev of the first horizon, or null (0)
     double* x0;                // [R][Npad] states of the start population
     uint32_t* start;           // [R][Npad] its ancestors
-    double* y_out;             // [R][H][Ns]
-    double* x_out;             // [R][H][Ns] or null
+    double* y_out;             // [R][H][Ns]; user models: [R][H][DY][Ns]
+    double* x_out;             // [R][H][Ns] or null; user models: [R][H][DX][Ns]
     const uint32_t* keyp;      // [2] Philox key
     uint32_t first_filter;
     int32_t N, Npad, Ns, B, Bs, Bpow2, tile, t0, H;
@@ -143,6 +146,115 @@ __global__ __launch_bounds__(kFcNT) void k_fc_horizon(const FcArgs a) {
         *reinterpret_cast<double2*>(yrow) = make_double2(yp[0], yp[1]);
         yrow += plane;
         if (xrow) { *reinterpret_cast<double2*>(xrow) = make_double2(x[0], x[1]); xrow += plane; }
+    }
+}
+
+// ---------------------------------------------------------------------------------------
+// User models with an observation draw (model_api.h: gsamp / gsamp_vec), scalar or with up to kMaxDim state / observation components.
+// The start population is k_fc_start's draw with one gather per state plane at the ancestor's index: x and x0 are [DX][R][Npad]
+// (xplane = R Npad doubles per plane), as the filter's own particles.  grid = (B, R), block = kFcNT.
+// ---------------------------------------------------------------------------------------
+template <int DX>
+__global__ __launch_bounds__(kFcNT) void k_fc_start_vec(const FcArgs a, const size_t xplane) {
+    const int r = blockIdx.y, b = blockIdx.x;
+    const uint32_t rep = a.first_filter + (uint32_t)r;
+    const uint32_t key0 = a.keyp[0], key1 = a.keyp[1];
+    const size_t rowoff = (size_t)r * a.Npad;
+    const double* T = a.l2_T + (size_t)r * a.Bs;
+    const double* Rr = a.l2_R + (size_t)r * a.Bs;
+    const double* cdf_r = a.cdf + rowoff;
+    const double S = a.scal[r].S;
+    const bool alive = S > 0.0;
+    for (int j0 = threadIdx.x; j0 < a.tile; j0 += kFcNT) {
+        const int i = b * a.tile + j0;                       // < Npad
+        uint32_t anc = 0u;
+        double xv[DX];
+#pragma unroll
+        for (int d = 0; d < DX; ++d) xv[d] = 0.0;
+        if (i < a.N) {
+            const int an = fc_draw_ancestor(T, Rr, cdf_r, S, a.B, a.Bpow2, a.tile, a.N, i, (uint32_t)a.t0, rep, key0, key1);
+            anc = (uint32_t)an;
+#pragma unroll
+            for (int d = 0; d < DX; ++d) xv[d] = alive ? a.x[(size_t)d * xplane + rowoff + an] : dnan();
+        }
+        a.start[rowoff + i] = anc;
+#pragma unroll
+        for (int d = 0; d < DX; ++d) a.x0[(size_t)d * xplane + rowoff + i] = xv[d];
+    }
+}
+
+// ---------------------------------------------------------------------------------------
+// All H horizons of lane pairs (2p, 2p + 1) of a user model.  Per horizon k and particle i, call c in {0, 1} is
+// Philox(i, t0, filter id, S_c + (k << 8)) with S_0 = STREAM_FC_SIM, S_1 = STREAM_FC_SIM2; words 0-1 of call c give
+// (zs[2c], zo[2c]) and words 2-3 (zs[2c + 1], zo[2c + 1]) by pair_normals.  Only what max(DX, DY) components need is evaluated;
+// members past DX (state) or DY (observation) are dropped, so a scalar model consumes what k_fc_horizon does.
+//   x <- prop_vec(x, zs, y_prev[0]);  y <- gsamp_vec(x, zo);  y_prev <- y.
+// Outputs: y[(r H + k) DY + j][Ns], x[(r H + k) DX + d][Ns], rows of Ns = N rounded up to even doubles, one aligned double2 store
+// per lane, component and horizon; the pad column of an odd N is computed from a zero state and never copied out.  State, y_prev,
+// the model constants and the key stay in registers across the run-time loop (constant indices only: nothing in scratch).
+// grid = (ceil(Ns / 2 / kFcNT), R), block = kFcNT.
+// ---------------------------------------------------------------------------------------
+template <class M, int DX, int DY>
+__global__ __launch_bounds__(kFcNT) void k_fc_horizon_user(const FcArgs a, const size_t xplane) {
+    constexpr int DM = DX > DY ? DX : DY;
+    __shared__ __attribute__((aligned(16))) DrawTabs lds_dtab;
+    __shared__ __attribute__((aligned(16))) ExpTabEntry lds_etab[SSME_EXP_TABLE_SIZE];
+    load_log_table<kFcNT>(&lds_dtab);
+    load_exp_table<kFcNT>(lds_etab);
+    __syncthreads();
+    const int r = blockIdx.y;
+    const int i0 = ((int)blockIdx.x * kFcNT + (int)threadIdx.x) * 2;
+    if (i0 >= a.Ns) return;
+    const uint32_t rep = a.first_filter + (uint32_t)r;
+    const uint32_t key0 = a.keyp[0], key1 = a.keyp[1];
+    const ModelConst mc = a.mc[r];
+    const bool alive = a.scal[r].S > 0.0;
+    double x[DX][2];
+#pragma unroll
+    for (int d = 0; d < DX; ++d) {
+        const double2 xs = *reinterpret_cast<const double2*>(a.x0 + (size_t)d * xplane + (size_t)r * a.Npad + i0);
+        x[d][0] = xs.x; x[d][1] = xs.y;
+    }
+    const double y0 = a.last_obs ? a.last_obs[r] : 0.0;
+    double yp[2] = {y0, y0};                                       // component 0 of the previous observation
+    const size_t plane = (size_t)a.Ns;
+    double* yrow = a.y_out + (size_t)r * a.H * DY * plane + i0;
+    double* xrow = a.x_out ? a.x_out + (size_t)r * a.H * DX * plane + i0 : nullptr;
+    for (int k = 0; k < a.H; ++k) {
+        const uint32_t kk = (uint32_t)k << 8;
+        double y[DY][2];
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            double zs[4], zo[4];
+            {
+                const u32x4 o = philox4x32_10((uint32_t)(i0 + c), (uint32_t)a.t0, rep, (uint32_t)STREAM_FC_SIM + kk, key0, key1);
+                pair_normals(o.v0, o.v1, &lds_dtab, &zs[0], &zo[0]);
+                if constexpr (DM > 1) pair_normals(o.v2, o.v3, &lds_dtab, &zs[1], &zo[1]);
+            }
+            if constexpr (DM > 2) {
+                const u32x4 o = philox4x32_10((uint32_t)(i0 + c), (uint32_t)a.t0, rep, (uint32_t)STREAM_FC_SIM2 + kk, key0, key1);
+                pair_normals(o.v0, o.v1, &lds_dtab, &zs[2], &zo[2]);
+                if constexpr (DM > 3) pair_normals(o.v2, o.v3, &lds_dtab, &zs[3], &zo[3]);
+            }
+            double xi[DX], xn[DX], yv[DY];
+#pragma unroll
+            for (int d = 0; d < DX; ++d) xi[d] = x[d][c];
+            user_calls<M>::prop_vec(mc, xi, zs, yp[c], xn, lds_etab);
+            user_calls<M>::gsamp_vec(mc, xn, zo, yv, lds_etab);
+#pragma unroll
+            for (int d = 0; d < DX; ++d) x[d][c] = xn[d];
+#pragma unroll
+            for (int j = 0; j < DY; ++j) y[j][c] = alive ? yv[j] : dnan();
+            yp[c] = y[0][c];
+        }
+#pragma unroll
+        for (int j = 0; j < DY; ++j) *reinterpret_cast<double2*>(yrow + (size_t)j * plane) = make_double2(y[j][0], y[j][1]);
+        yrow += (size_t)DY * plane;
+        if (xrow) {
+#pragma unroll
+            for (int d = 0; d < DX; ++d) *reinterpret_cast<double2*>(xrow + (size_t)d * plane) = make_double2(x[d][0], x[d][1]);
+            xrow += (size_t)DX * plane;
+        }
     }
 }
 

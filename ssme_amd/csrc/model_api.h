@@ -51,6 +51,21 @@
 // Callers: ssme_pf_user_model_n_h / ssme_pf_get_user_expectations / ssme_pf_swarm_aggregate_user (include/ssme_pf.h),
 // user_bs_gpu::getModelExpectations (bsfilter_gpu.hpp), ParticleFilterBank.user_expectations / swarm_aggregate_user.  A header
 // without n_h compiles and behaves as before (n_h reads 0).  tests/models/svol_two_factor_h.h declares seven of them.
+//
+// OBSERVATION DRAW (optional; gSamp of the reference's FutureSimulator add-on, test/test_pswarm.cpp:64-67, 112-116).  A header that
+// declares it can be forecast: ssme_pf_sim_future_obs simulates from the model on the device (forecast.h).
+//     static __device__ double gsamp(const ssme::ModelConst& c, double x, double zo, const ssme::ExpTabEntry* etab);     // scalar model
+//     static __device__ void gsamp_vec(const ssme::ModelConst& c, const double* x /*dim_x*/, const double* zo /*dim_y*/,
+//                                      double* y /*dim_y*/, const ssme::ExpTabEntry* etab);                              // vector model
+// y from the state and dim_y standard normals, under the rules of the other callbacks (+ - * fma, ssme_math.h; constant indices).
+// A plain `/` and ssme::dsqrt are within those rules in every callback: both are correctly rounded on the device under the library's
+// flags (-fno-fast-math), as on the host, so a restatement reproduces them (lin_gauss_4d_h.h's init_vec, lin_gauss_4d_g.h's gsamp_vec).
+// What is excluded is libm (exp, log, pow, sin ...), whose results differ between the two.
+// A simulated step is x <- prop / prop_vec(c, x, zs, zcov = y_prev[0]), y <- gsamp / gsamp_vec(c, x, zo): the covariate of a
+// simulated step is component 0 of the previous simulated observation (fSamp(x, y_prev) of the reference, the built-in leverage
+// model's convention).  A model whose covariate is exogenous cannot be forecast without future covariates; that is not offered.
+// A header without the draw compiles and behaves as before (ssme_pf_user_model_has_gsamp reads 0, a forecast is
+// SSME_ERR_UNSUPPORTED).  tests/models/svol_leverage_user.h, svol_two_factor_g.h, lin_gauss_3d_g.h, lin_gauss_4d_g.h declare it.
 #pragma once
 #include <type_traits>
 #include "ssme_math.h"
@@ -90,6 +105,19 @@ template <class M> struct user_nh<M, std::void_t<decltype(M::n_h)>> {
     static constexpr int n = M::n_h;
     static_assert(n >= 1 && n <= kMaxUserFunctionals, "n_h of a user model: 1 .. 16");
 };
+// does the header declare the observation draw, in the form its dimensions ask for (gsamp / gsamp_vec above)?
+template <class M, class = void> struct declares_gsamp : std::false_type {};
+template <class M> struct declares_gsamp<M, std::void_t<decltype(&M::gsamp)>> : std::true_type {};
+template <class M, class = void> struct declares_gsamp_vec : std::false_type {};
+template <class M> struct declares_gsamp_vec<M, std::void_t<decltype(&M::gsamp_vec)>> : std::true_type {};
+template <class M> struct user_gsamp {
+    static constexpr bool vec = user_dims<M>::dx > 1 || user_dims<M>::dy > 1;
+    static_assert(!(vec && declares_gsamp<M>::value && !declares_gsamp_vec<M>::value),
+                  "a vector user model (dim_x or dim_y > 1) declares its observation draw as gsamp_vec, not gsamp");
+    static_assert(!(!vec && declares_gsamp_vec<M>::value && !declares_gsamp<M>::value),
+                  "a scalar user model declares its observation draw as gsamp, not gsamp_vec");
+    static constexpr bool has = vec ? declares_gsamp_vec<M>::value : declares_gsamp<M>::value;
+};
 // what the kernels call: a scalar model through its prop / logg, a vector model through its *_vec functions (the other set is a
 // stub that no launch reaches: vector models never run the scalar kernels and the other way round)
 template <class M, bool VEC = (user_dims<M>::dx > 1 || user_dims<M>::dy > 1)> struct user_calls;
@@ -99,6 +127,7 @@ template <class M> struct user_calls<M, false> {
     static __device__ __forceinline__ void init_vec(const ModelConst& c, const double* zn, double* x0) { x0[0] = zn[0] * c.a2; }
     static __device__ __forceinline__ void prop_vec(const ModelConst& c, const double* x, const double* zn, double zcov, double* xn, const ExpTabEntry* etab) { xn[0] = M::prop(c, x[0], zn[0], zcov, etab); }
     static __device__ __forceinline__ double logg_vec(const ModelConst& c, const double* y, const double* x, const ExpTabEntry* etab) { return M::logg(c, y[0], x[0], etab); }
+    static __device__ __forceinline__ void gsamp_vec(const ModelConst& c, const double* x, const double* zo, double* y, const ExpTabEntry* etab) { y[0] = M::gsamp(c, x[0], zo[0], etab); }
 };
 template <class M> struct user_calls<M, true> {
     static __device__ __forceinline__ double prop(const ModelConst&, double, double, double, const ExpTabEntry*) { return 0.0; }
@@ -106,6 +135,7 @@ template <class M> struct user_calls<M, true> {
     static __device__ __forceinline__ void init_vec(const ModelConst& c, const double* zn, double* x0) { M::init_vec(c, zn, x0); }
     static __device__ __forceinline__ void prop_vec(const ModelConst& c, const double* x, const double* zn, double zcov, double* xn, const ExpTabEntry* etab) { M::prop_vec(c, x, zn, zcov, xn, etab); }
     static __device__ __forceinline__ double logg_vec(const ModelConst& c, const double* y, const double* x, const ExpTabEntry* etab) { return M::logg_vec(c, y, x, etab); }
+    static __device__ __forceinline__ void gsamp_vec(const ModelConst& c, const double* x, const double* zo, double* y, const ExpTabEntry* etab) { M::gsamp_vec(c, x, zo, y, etab); }
 };
 #if SSME_HAS_USER_MODEL
 template <int MODEL> constexpr int model_dx() { return MODEL == MODEL_USER0 ? user_dims<ssme_user_model0>::dx : 1; }

@@ -72,9 +72,9 @@ struct ssme_pf_s : HandleCore {
     double *fc_T, *fc_R;         // [R][Bs] level-2 tables of the start draw
     FilterScalars* fc_scal;      // [R] S' of the start draw
     double *fc_gscale, *fc_last; // [R]
-    double* fc_x0;               // [R][Npad] states of the start population
+    double* fc_x0;               // [dx][R][Npad] states of the start population
     uint32_t* fc_start;          // [R][Npad] its ancestors
-    double *fc_y, *fc_x;         // [R][H][Ns] samples, fc_cap doubles each
+    double *fc_y, *fc_x;         // [R][H][dy][Ns] / [R][H][dx][Ns] samples, fc_cap doubles each
     size_t fc_cap_y, fc_cap_x;
     hipEvent_t fc_ev[3];         // call start, horizon kernel start, horizon kernel end
     float fc_ms_horizon, fc_ms_call;
@@ -476,11 +476,33 @@ static int user_expectations_checked(ssme_pf_handle h) {
 #endif
 }
 
-// the horizon kernel of a forecast (forecast.h), one instantiation per built-in model (user models declare no observation draw)
+// the horizon kernel of a forecast (forecast.h), one instantiation per built-in model (user models: launch_fc_user below)
 template <int MODEL>
 static void launch_fc_horizon(ssme_pf_handle h, const FcArgs& a) {
     if constexpr (MODEL != MODEL_USER0)
         hipLaunchKernelGGL((k_fc_horizon<MODEL>), dim3((a.Ns / 2 + kFcNT - 1) / kFcNT, h->R), dim3(kFcNT), 0, h->stream, a);
+}
+
+// does the compiled-in user model declare its observation draw (model_api.h: gsamp / gsamp_vec)?
+#if SSME_HAS_USER_MODEL
+constexpr bool kUserHasGsamp = user_gsamp<ssme_user_model0>::has;
+#else
+constexpr bool kUserHasGsamp = false;
+#endif
+
+// the two kernels of a user model's forecast: every state plane gathered at the ancestor's index, then all horizons.  ev: the
+// event recorded between them (start of the horizon kernel).  A template, so that a header without the draw instantiates neither
+template <class M>
+static hipError_t launch_fc_user(ssme_pf_handle h, const FcArgs& a, hipEvent_t ev) {
+    if constexpr (user_gsamp<M>::has) {
+        constexpr int DX = user_dims<M>::dx, DY = user_dims<M>::dy;
+        const size_t xplane = (size_t)h->R * h->Npad;
+        hipLaunchKernelGGL((k_fc_start_vec<DX>), dim3(h->B, h->R), dim3(kFcNT), 0, h->stream, a, xplane);
+        const hipError_t e = hipEventRecord(ev, h->stream);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL((k_fc_horizon_user<M, DX, DY>), dim3((a.Ns / 2 + kFcNT - 1) / kFcNT, h->R), dim3(kFcNT), 0, h->stream, a, xplane);
+    }
+    return hipSuccess;
 }
 
 extern "C" {
@@ -613,6 +635,7 @@ int ssme_pf_user_model_n_h(void) {
     return 0;
 #endif
 }
+int ssme_pf_user_model_has_gsamp(void) { return kUserHasGsamp ? 1 : 0; }
 int ssme_pf_default_tile(int32_t n_particles, int32_t bank_filters) { return default_tile(n_particles, bank_filters < 1 ? 1 : bank_filters); }
 
 // ---- particle-sharded filter: one filter of cfg->n_particles particles over `world` GPUs ------------------------------
@@ -1287,24 +1310,27 @@ int ssme_pf_sim_future_obs(ssme_pf_handle h, int32_t num_steps, const double* la
                            uint32_t* start_out) {
     if (!h || !y_out || num_steps < 1 || num_steps > kFcMaxSteps) return SSME_ERR_INVALID_ARG;
     if (h->shard_world > 0) { h->err = "forecasts of particle-sharded filters are not implemented"; return SSME_ERR_UNSUPPORTED; }
-    if (h->cfg.model == SSME_MODEL_USER0) { h->err = "user models declare no observation draw (gSamp)"; return SSME_ERR_UNSUPPORTED; }
+    const bool user = h->cfg.model == SSME_MODEL_USER0;
+    if (user && !kUserHasGsamp) { h->err = "this user model declares no observation draw (gsamp / gsamp_vec, model_api.h)"; return SSME_ERR_UNSUPPORTED; }
     if (!h->params_set || h->t < 1) { h->err = "sim_future_obs before the first step"; return SSME_ERR_STATE; }
     HIPCHK(hipSetDevice(h->cfg.device));
     const int H = num_steps, R = h->R, N = h->N;
     const int Ns = (N + 1) & ~1;
-    const size_t nb = (size_t)R * h->Bs, np = (size_t)R * h->Npad, ns = (size_t)R * H * Ns;
+    const int dx = h->dx, dy = h->dy;                      // 1 unless this is a vector user model
+    const size_t nb = (size_t)R * h->Bs, np = (size_t)R * h->Npad, rows = (size_t)R * H;
+    const size_t nsy = rows * dy * Ns, nsx = rows * dx * Ns;
     if (!h->fc_T) {
         HIPCHK(own_alloc(h, h->fc_T, sizeof(double) * nb));
         HIPCHK(own_alloc(h, h->fc_R, sizeof(double) * nb));
         HIPCHK(own_alloc(h, h->fc_scal, sizeof(FilterScalars) * R, Mem::zeroed));
         HIPCHK(own_alloc(h, h->fc_gscale, sizeof(double) * R));
         HIPCHK(own_alloc(h, h->fc_last, sizeof(double) * R));
-        HIPCHK(own_alloc(h, h->fc_x0, sizeof(double) * np));
+        HIPCHK(own_alloc(h, h->fc_x0, sizeof(double) * np * dx));
         HIPCHK(own_alloc(h, h->fc_start, sizeof(uint32_t) * np));
         for (hipEvent_t& e : h->fc_ev) HIPCHK(hipEventCreate(&e));
     }
-    if (ns > h->fc_cap_y) { h->fc_cap_y = 0; HIPCHK(own_alloc(h, h->fc_y, sizeof(double) * ns)); h->fc_cap_y = ns; }
-    if (x_out && ns > h->fc_cap_x) { h->fc_cap_x = 0; HIPCHK(own_alloc(h, h->fc_x, sizeof(double) * ns)); h->fc_cap_x = ns; }
+    if (nsy > h->fc_cap_y) { h->fc_cap_y = 0; HIPCHK(own_alloc(h, h->fc_y, sizeof(double) * nsy)); h->fc_cap_y = nsy; }
+    if (x_out && nsx > h->fc_cap_x) { h->fc_cap_x = 0; HIPCHK(own_alloc(h, h->fc_x, sizeof(double) * nsx)); h->fc_cap_x = nsx; }
     h->h_last_obs.assign(R, 0.0);
     if (last_obs) for (int r = 0; r < R; ++r) h->h_last_obs[r] = h->cfg.dtype == SSME_F32 ? f32r(last_obs[r]) : last_obs[r];
     HIPCHK(hipEventRecord(h->fc_ev[0], h->stream));
@@ -1324,20 +1350,25 @@ int ssme_pf_sim_future_obs(ssme_pf_handle h, int32_t num_steps, const double* la
     a.y_out = h->fc_y; a.x_out = x_out ? h->fc_x : nullptr;
     a.keyp = h->keybuf; a.first_filter = h->cfg.first_filter_id;
     a.N = N; a.Npad = h->Npad; a.Ns = Ns; a.B = h->B; a.Bs = h->Bs; a.Bpow2 = h->Bpow2; a.tile = h->tile; a.t0 = h->t; a.H = H;
-    hipLaunchKernelGGL(k_fc_start, dim3(h->B, R), dim3(kFcNT), 0, h->stream, a);
-    HIPCHK(hipEventRecord(h->fc_ev[1], h->stream));
-    with_model(h->cfg.model, [&](auto m) { launch_fc_horizon<decltype(m)::value>(h, a); });
+    if (user) {
+#if SSME_HAS_USER_MODEL
+        HIPCHK(launch_fc_user<ssme_user_model0>(h, a, h->fc_ev[1]));
+#endif
+    } else {
+        hipLaunchKernelGGL(k_fc_start, dim3(h->B, R), dim3(kFcNT), 0, h->stream, a);
+        HIPCHK(hipEventRecord(h->fc_ev[1], h->stream));
+        with_model(h->cfg.model, [&](auto m) { launch_fc_horizon<decltype(m)::value>(h, a); });
+    }
     HIPCHK(hipEventRecord(h->fc_ev[2], h->stream));
     HIPCHK(hipGetLastError());
-    const size_t rows = (size_t)R * H;
-    HIPCHK(hipMemcpy2DAsync(y_out, sizeof(double) * N, h->fc_y, sizeof(double) * Ns, sizeof(double) * N, rows, hipMemcpyDeviceToHost, h->stream));
-    if (x_out) HIPCHK(hipMemcpy2DAsync(x_out, sizeof(double) * N, h->fc_x, sizeof(double) * Ns, sizeof(double) * N, rows, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpy2DAsync(y_out, sizeof(double) * N, h->fc_y, sizeof(double) * Ns, sizeof(double) * N, rows * dy, hipMemcpyDeviceToHost, h->stream));
+    if (x_out) HIPCHK(hipMemcpy2DAsync(x_out, sizeof(double) * N, h->fc_x, sizeof(double) * Ns, sizeof(double) * N, rows * dx, hipMemcpyDeviceToHost, h->stream));
     if (start_out) HIPCHK(hipMemcpy2DAsync(start_out, sizeof(uint32_t) * N, h->fc_start, sizeof(uint32_t) * h->Npad, sizeof(uint32_t) * N, R, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipEventElapsedTime(&h->fc_ms_horizon, h->fc_ev[1], h->fc_ev[2]));
     HIPCHK(hipEventElapsedTime(&h->fc_ms_call, h->fc_ev[0], h->fc_ev[2]));
-    round_out(h, y_out, rows * N);
-    round_out(h, x_out, rows * N);
+    round_out(h, y_out, rows * dy * N);
+    round_out(h, x_out, rows * dx * N);
     return SSME_OK;
 }
 

@@ -16,7 +16,7 @@ from . import _capi as capi
 from ._capi import (MODEL_LIN_GAUSS, MODEL_SVOL, MODEL_SVOL_LEVERAGE, MODEL_USER0, RESAMP_MULTINOMIAL, RESAMP_MULTINOMIAL_IID,
                     RESAMP_STRATIFIED, RESAMP_SYSTEMATIC, SsmeError)
 
-__all__ = ["default_tile", "ParticleFilterBank", "svol_bs", "svol_leverage", "lin_gauss_bs", "log_like_eval", "svol_lw_1_par", "svol_lw_2_par", "SwarmWithCovs", "Swarm", "svol_swarm_1",
+__all__ = ["default_tile", "user_model_has_gsamp", "ParticleFilterBank", "svol_bs", "svol_leverage", "lin_gauss_bs", "log_like_eval", "svol_lw_1_par", "svol_lw_2_par", "SwarmWithCovs", "Swarm", "svol_swarm_1",
            "TR_NULL", "TR_TWICE_FISHER", "TR_LOGIT", "TR_LOG",
            "MODEL_SVOL", "MODEL_SVOL_LEVERAGE", "MODEL_LIN_GAUSS", "MODEL_USER0", "RESAMP_MULTINOMIAL", "RESAMP_SYSTEMATIC",
            "RESAMP_STRATIFIED", "RESAMP_MULTINOMIAL_IID", "SsmeError"]
@@ -25,6 +25,12 @@ __all__ = ["default_tile", "ParticleFilterBank", "svol_bs", "svol_leverage", "li
 def default_tile(n_particles, bank_filters=1):
     """The tile size tile = 0 stands for (ssme_pf_default_tile): a function of N and the size of the whole bank of filters."""
     return int(capi.lib().ssme_pf_default_tile(int(n_particles), int(bank_filters)))
+
+
+def user_model_has_gsamp():
+    """Does the loaded library's user model declare its observation draw (csrc/model_api.h: gsamp / gsamp_vec), so that
+    MODEL_USER0 filters can be forecast (sim_future_obs)?  False for the stock library.  Needs no device."""
+    return bool(capi.lib().ssme_pf_user_model_has_gsamp())
 
 
 class ParticleFilterBank:
@@ -179,12 +185,15 @@ class ParticleFilterBank:
     def sim_future_obs(self, H, last_obs=None, states=False, start=False):
         """Simulated future observations y[R, H, N] of every filter, on the device (ssme_pf_sim_future_obs: sim_future_obs of the
         reference's *FutureSimulator add-ons; layout "param, time, then state particle", pswarm_filter.h:49-50).  last_obs: the
-        last observation, a scalar or one value per filter (read by the leverage model only).  states / start: also return the
-        simulated states x[R, H, N] / the ancestors [R, N] of the start draw: y, or (y[, x][, start])."""
+        last observation, a scalar or one value per filter (the covariate of the first simulated step: read by the leverage model
+        and by user models whose prop reads its covariate).  states / start: also return the simulated states x[R, H, N] / the
+        ancestors [R, N] of the start draw: y, or (y[, x][, start]).  A user model that declares its observation draw
+        (user_model_has_gsamp) with a vector observation / state returns y[R, H, dim_y, N] / x[R, H, dim_x, N]."""
         H = int(H)
+        dx, dy = self._dims()
         lo = None if last_obs is None else np.ascontiguousarray(np.broadcast_to(np.asarray(last_obs, dtype=np.float64), (self.r,)))
-        y = np.empty((self.r, max(H, 0), self.n))
-        x = np.empty_like(y) if states else None
+        y = np.empty((self.r, max(H, 0), self.n) if dy == 1 else (self.r, max(H, 0), dy, self.n))
+        x = (np.empty((self.r, max(H, 0), self.n) if dx == 1 else (self.r, max(H, 0), dx, self.n))) if states else None
         st = np.empty((self.r, self.n), dtype=np.uint32) if start else None
         self._chk(capi.lib().ssme_pf_sim_future_obs(self._h, H, capi.dptr(lo), capi.dptr(y), capi.dptr(x), capi.u32ptr(st)))
         out = (y,) + ((x,) if states else ()) + ((st,) if start else ())
@@ -271,7 +280,8 @@ class _SingleFilter:
         return out
 
     def sim_future_obs(self, H, last_obs=None, states=False, start=False):
-        """sim_future_obs(num_future_steps) of the model object: y[H, N] (ParticleFilterBank.sim_future_obs of the one filter)."""
+        """sim_future_obs(num_future_steps) of the model object: y[H, N], or y[H, dim_y, N] for a user model with a vector observation
+        (ParticleFilterBank.sim_future_obs of the one filter)."""
         out = self._bank.sim_future_obs(H, last_obs, states, start)
         return out[0] if not isinstance(out, tuple) else tuple(o[0] for o in out)
 
