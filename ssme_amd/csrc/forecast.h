@@ -7,15 +7,18 @@
 //
 // Two kernels per call (bootstrap models; the Liu-West pair below adds the parameter records and their moments), both on buffers of
 // the forecast's own (nothing a later filter step reads is written):
-//   k_fc_start     draws N ancestors per filter from the last step's weights -- an iid two-level search of the integer
+//   k_fc_start_vec<DX>  draws N ancestors per filter from the last step's weights -- an iid two-level search of the integer
 //                  weight cdf, the search of k_filter_step's general path, on the level-2 tables k_level2_plan leaves
-//                  (T'_b, A_b / A'_b, S') -- and gathers their states.  grid = (tiles, R).
+//                  (T'_b, A_b / A'_b, S') -- and gathers their states, one gather per state plane (DX = 1: the built-in models).
+//                  grid = (tiles, R).
 //   k_fc_horizon   all H horizons in ONE launch: two particles per lane, state / y_prev / model constants in registers across
 //                  the run-time loop over the horizon, one Philox call per particle and horizon (words 0-1 -> the pair
 //                  (z_state, z_obs) by pair_normals), one coalesced 16-byte store per lane and horizon into y[r][k][.]
 //                  (and x[r][k][.] when asked).  Tables of log / sincos / exp in LDS, as in the step kernels.
 // A user model that declares its observation draw (model_api.h: gsamp / gsamp_vec) runs the same pair on every state plane:
 //   k_fc_start_vec<DX>, k_fc_horizon_user<M, DX, DY> (below the built-in kernels).
+// What the three horizon kernels (k_fc_horizon, k_fc_horizon_user, k_fc_lw_horizon) share is in fc_load_tables, fc_lane and
+// fc_store_row; what the two argument structs share is FcCommon.
 #pragma once
 #include "pf_kernels.h"
 #include "lw_kernels.h"
@@ -30,14 +33,13 @@ enum { STREAM_FC_START = 160, STREAM_FC_SIM = 161, STREAM_FC_LW_JIT = 162, STREA
 constexpr int kFcMaxSteps = 65535;
 constexpr int kFcNT = 256;
 
-struct FcArgs {
+// what the bootstrap and the Liu-West forecast both pass to their kernels
+struct FcCommon {
     const double* x;           // [R][Npad] particles of the last step (pre-resampling); user models: [DX][R][Npad], as x0
-    const double* cdf;         // [R][Npad] tile-local inclusive integer sums of their fixed-point weights
+    const double* cdf;         // [R][Npad] tile-local inclusive integer sums of their fixed-point weights (Liu-West: second stage)
     const double* l2_T;        // [R][Bs] inclusive prefixes T'_b of the rescaled tile sums   (k_level2_plan, forecast's own buffers)
     const double* l2_R;        // [R][Bs] A_b / A'_b
     const FilterScalars* scal; // [R] S' (forecast's own copy)
-    const ModelConst* mc;      // [R]
-    const double* gscale;      // [R] scale of the observation draw: beta (SVOL), 1 (leverage), tau (linear Gaussian)
     const double* last_obs;    // [R] y_prev of the first horizon, or null (0)
     double* x0;                // [R][Npad] states of the start population
     uint32_t* start;           // [R][Npad] its ancestors
@@ -45,7 +47,13 @@ struct FcArgs {
     double* x_out;             // [R][H][Ns] or null; user models: [R][H][DX][Ns]
     const uint32_t* keyp;      // [2] Philox key
     uint32_t first_filter;
-    int32_t N, Npad, Ns, B, Bs, Bpow2, tile, t0, H;
+    int32_t N, Npad, Ns, B, Bs, Bpow2, t0, H;
+};
+
+struct FcArgs : FcCommon {
+    const ModelConst* mc;      // [R]
+    const double* gscale;      // [R] scale of the observation draw: beta (SVOL), 1 (leverage), tau (linear Gaussian)
+    int32_t tile;
 };
 
 // The start draw of particle i: u = u01_mid40 of words 0-1 of Philox(i, t0, filter id, STREAM_FC_START), target = ceil(u S'),
@@ -67,92 +75,10 @@ __device__ __forceinline__ int fc_draw_ancestor(const double* T, const double* R
 }
 
 // ---------------------------------------------------------------------------------------
-// Start population of the bootstrap models: every particle's ancestor by fc_draw_ancestor and its state.  A filter without weight
-// (S' not > 0: all weights zero, -inf or NaN) gets NaN states.  grid = (B, R), block = kFcNT.
-// ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kFcNT) void k_fc_start(const FcArgs a) {
-    const int r = blockIdx.y, b = blockIdx.x;
-    const uint32_t rep = a.first_filter + (uint32_t)r;
-    const uint32_t key0 = a.keyp[0], key1 = a.keyp[1];
-    const size_t rowoff = (size_t)r * a.Npad;
-    const double* T = a.l2_T + (size_t)r * a.Bs;
-    const double* Rr = a.l2_R + (size_t)r * a.Bs;
-    const double* cdf_r = a.cdf + rowoff;
-    const double S = a.scal[r].S;
-    const bool alive = S > 0.0;
-    for (int j0 = threadIdx.x; j0 < a.tile; j0 += kFcNT) {
-        const int i = b * a.tile + j0;                       // < Npad
-        uint32_t anc = 0u;
-        double xv = 0.0;
-        if (i < a.N) {
-            const int an = fc_draw_ancestor(T, Rr, cdf_r, S, a.B, a.Bpow2, a.tile, a.N, i, (uint32_t)a.t0, rep, key0, key1);
-            anc = (uint32_t)an;
-            xv = alive ? a.x[rowoff + an] : dnan();
-        }
-        a.start[rowoff + i] = anc;
-        a.x0[rowoff + i] = xv;
-    }
-}
-
-// observation draw gSamp(x, z): SVOL beta exp(x/2) z, leverage exp(x/2) z (test/test_pswarm.cpp:112-116), linear Gaussian x + tau z
-template <int MODEL>
-__device__ __forceinline__ double model_gsamp(double gs, double x, double z, const ExpTabEntry* etab) {
-    if (MODEL == MODEL_LIN_GAUSS) return x + gs * z;
-    const double e = dexp_scaled_t(0.5 * x, 0, etab);
-    if (MODEL == MODEL_SVOL) return (gs * e) * z;
-    return e * z;
-}
-
-// ---------------------------------------------------------------------------------------
-// All H horizons of lane pairs (2p, 2p + 1).  Per horizon k and particle i: (z_s, z_o) = pair_normals of words 0-1 of
-// Philox(i, t0, filter id, STREAM_FC_SIM + (k << 8)); x <- model_prop(x, z_s, y_prev); y <- gSamp(x, z_o); y_prev <- y
-// (propagate, then observe: liu_west_filter.h:1338-1356).  Rows of the outputs are Ns = N rounded up to even doubles long, so
-// every store is an aligned double2; the pad column of an odd N is computed from a zero state and never copied out.
-// grid = (ceil(Ns / 2 / kFcNT), R), block = kFcNT.
-// ---------------------------------------------------------------------------------------
-template <int MODEL>
-__global__ __launch_bounds__(kFcNT) void k_fc_horizon(const FcArgs a) {
-    __shared__ __attribute__((aligned(16))) DrawTabs lds_dtab;
-    __shared__ __attribute__((aligned(16))) ExpTabEntry lds_etab[SSME_EXP_TABLE_SIZE];
-    load_log_table<kFcNT>(&lds_dtab);
-    load_exp_table<kFcNT>(lds_etab);
-    __syncthreads();
-    const int r = blockIdx.y;
-    const int i0 = ((int)blockIdx.x * kFcNT + (int)threadIdx.x) * 2;
-    if (i0 >= a.Ns) return;
-    const uint32_t rep = a.first_filter + (uint32_t)r;
-    const uint32_t key0 = a.keyp[0], key1 = a.keyp[1];
-    const ModelConst mc = a.mc[r];
-    const double gs = a.gscale[r];
-    const bool alive = a.scal[r].S > 0.0;
-    const double2 xs = *reinterpret_cast<const double2*>(a.x0 + (size_t)r * a.Npad + i0);
-    double x[2] = {xs.x, xs.y};
-    const double y0 = a.last_obs ? a.last_obs[r] : 0.0;
-    double yp[2] = {y0, y0};
-    const size_t plane = (size_t)a.Ns;
-    double* yrow = a.y_out + (size_t)r * a.H * plane + i0;
-    double* xrow = a.x_out ? a.x_out + (size_t)r * a.H * plane + i0 : nullptr;
-    for (int k = 0; k < a.H; ++k) {
-        const uint32_t c3 = (uint32_t)STREAM_FC_SIM + ((uint32_t)k << 8);
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            const u32x4 o = philox4x32_10((uint32_t)(i0 + c), (uint32_t)a.t0, rep, c3, key0, key1);
-            double zs, zo;
-            pair_normals(o.v0, o.v1, &lds_dtab, &zs, &zo);
-            x[c] = model_prop<MODEL>(mc, x[c], zs, yp[c], lds_etab);
-            const double yv = model_gsamp<MODEL>(gs, x[c], zo, lds_etab);
-            yp[c] = alive ? yv : dnan();
-        }
-        *reinterpret_cast<double2*>(yrow) = make_double2(yp[0], yp[1]);
-        yrow += plane;
-        if (xrow) { *reinterpret_cast<double2*>(xrow) = make_double2(x[0], x[1]); xrow += plane; }
-    }
-}
-
-// ---------------------------------------------------------------------------------------
-// User models with an observation draw (model_api.h: gsamp / gsamp_vec), scalar or with up to kMaxDim state / observation components.
-// The start population is k_fc_start's draw with one gather per state plane at the ancestor's index: x and x0 are [DX][R][Npad]
-// (xplane = R Npad doubles per plane), as the filter's own particles.  grid = (B, R), block = kFcNT.
+// Start population of the bootstrap models: every particle's ancestor by fc_draw_ancestor and its state, one gather per state plane
+// at the ancestor's index: x and x0 are [DX][R][Npad] (xplane = R Npad doubles per plane), as the filter's own particles.  The
+// built-in models and scalar user models are DX = 1.  A filter without weight (S' not > 0: all weights zero, -inf or NaN) gets NaN
+// states.  grid = (B, R), block = kFcNT.
 // ---------------------------------------------------------------------------------------
 template <int DX>
 __global__ __launch_bounds__(kFcNT) void k_fc_start_vec(const FcArgs a, const size_t xplane) {
@@ -183,6 +109,92 @@ __global__ __launch_bounds__(kFcNT) void k_fc_start_vec(const FcArgs a, const si
     }
 }
 
+// observation draw gSamp(x, z): SVOL beta exp(x/2) z, leverage exp(x/2) z (test/test_pswarm.cpp:112-116), linear Gaussian x + tau z
+template <int MODEL>
+__device__ __forceinline__ double model_gsamp(double gs, double x, double z, const ExpTabEntry* etab) {
+    if (MODEL == MODEL_LIN_GAUSS) return x + gs * z;
+    const double e = dexp_scaled_t(0.5 * x, 0, etab);
+    if (MODEL == MODEL_SVOL) return (gs * e) * z;
+    return e * z;
+}
+
+// ---------------------------------------------------------------------------------------
+// What the three horizon kernels share.  fc_load_tables: the draw and exp tables into LDS, then the barrier.
+// ---------------------------------------------------------------------------------------
+__device__ __forceinline__ void fc_load_tables(DrawTabs* dtab, ExpTabEntry* etab) {
+    load_log_table<kFcNT>(dtab);
+    load_exp_table<kFcNT>(etab);
+    __syncthreads();
+}
+
+// A lane's share of a horizon kernel: particles i0 and i0 + 1 of filter r (Philox filter id rep), the key, whether the filter has
+// weight, y_prev of the first horizon, the doubles per output plane and where the lane's first double2 of y / x (null: not asked
+// for) goes; a horizon is ny / nx planes of y / x.  False: the lane is past the row and has nothing to do.
+struct FcLane {
+    int r, i0;
+    uint32_t rep, key0, key1;
+    bool alive;
+    double y0;
+    size_t plane;
+    double *yrow, *xrow;
+};
+__device__ __forceinline__ bool fc_lane(const FcCommon& a, int ny, int nx, FcLane* l) {
+    l->r = blockIdx.y;
+    l->i0 = ((int)blockIdx.x * kFcNT + (int)threadIdx.x) * 2;
+    if (l->i0 >= a.Ns) return false;
+    l->rep = a.first_filter + (uint32_t)l->r;
+    l->key0 = a.keyp[0]; l->key1 = a.keyp[1];
+    l->alive = a.scal[l->r].S > 0.0;
+    l->y0 = a.last_obs ? a.last_obs[l->r] : 0.0;
+    l->plane = (size_t)a.Ns;
+    l->yrow = a.y_out + (size_t)l->r * a.H * ny * l->plane + l->i0;
+    l->xrow = a.x_out ? a.x_out + (size_t)l->r * a.H * nx * l->plane + l->i0 : nullptr;
+    return true;
+}
+
+// one horizon's D planes of a lane's pair: an aligned double2 per plane, then the row moves on to the next horizon
+template <int D>
+__device__ __forceinline__ void fc_store_row(double*& row, size_t plane, const double (*v)[2]) {
+#pragma unroll
+    for (int j = 0; j < D; ++j) *reinterpret_cast<double2*>(row + (size_t)j * plane) = make_double2(v[j][0], v[j][1]);
+    row += (size_t)D * plane;
+}
+
+// ---------------------------------------------------------------------------------------
+// All H horizons of lane pairs (2p, 2p + 1).  Per horizon k and particle i: (z_s, z_o) = pair_normals of words 0-1 of
+// Philox(i, t0, filter id, STREAM_FC_SIM + (k << 8)); x <- model_prop(x, z_s, y_prev); y <- gSamp(x, z_o); y_prev <- y
+// (propagate, then observe: liu_west_filter.h:1338-1356).  Rows of the outputs are Ns = N rounded up to even doubles long, so
+// every store is an aligned double2; the pad column of an odd N is computed from a zero state and never copied out.
+// grid = (ceil(Ns / 2 / kFcNT), R), block = kFcNT.
+// ---------------------------------------------------------------------------------------
+template <int MODEL>
+__global__ __launch_bounds__(kFcNT) void k_fc_horizon(const FcArgs a) {
+    __shared__ __attribute__((aligned(16))) DrawTabs lds_dtab;
+    __shared__ __attribute__((aligned(16))) ExpTabEntry lds_etab[SSME_EXP_TABLE_SIZE];
+    fc_load_tables(&lds_dtab, lds_etab);
+    FcLane l;
+    if (!fc_lane(a, 1, 1, &l)) return;
+    const ModelConst mc = a.mc[l.r];
+    const double gs = a.gscale[l.r];
+    const double2 xs = *reinterpret_cast<const double2*>(a.x0 + (size_t)l.r * a.Npad + l.i0);
+    double x[2] = {xs.x, xs.y};
+    double yp[2] = {l.y0, l.y0};
+    for (int k = 0; k < a.H; ++k) {
+        const uint32_t c3 = (uint32_t)STREAM_FC_SIM + ((uint32_t)k << 8);
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            const u32x4 o = philox4x32_10((uint32_t)(l.i0 + c), (uint32_t)a.t0, l.rep, c3, l.key0, l.key1);
+            double zs, zo;
+            pair_normals(o.v0, o.v1, &lds_dtab, &zs, &zo);
+            x[c] = model_prop<MODEL>(mc, x[c], zs, yp[c], lds_etab);
+            const double yv = model_gsamp<MODEL>(gs, x[c], zo, lds_etab);
+            yp[c] = l.alive ? yv : dnan();
+        }
+        fc_store_row<1>(l.yrow, l.plane, &yp);
+        if (l.xrow) fc_store_row<1>(l.xrow, l.plane, &x);
+    }
+}
+
 // ---------------------------------------------------------------------------------------
 // All H horizons of lane pairs (2p, 2p + 1) of a user model.  Per horizon k and particle i, call c in {0, 1} is
 // Philox(i, t0, filter id, S_c + (k << 8)) with S_0 = STREAM_FC_SIM, S_1 = STREAM_FC_SIM2; words 0-1 of call c give
@@ -199,27 +211,17 @@ __global__ __launch_bounds__(kFcNT) void k_fc_horizon_user(const FcArgs a, const
     constexpr int DM = DX > DY ? DX : DY;
     __shared__ __attribute__((aligned(16))) DrawTabs lds_dtab;
     __shared__ __attribute__((aligned(16))) ExpTabEntry lds_etab[SSME_EXP_TABLE_SIZE];
-    load_log_table<kFcNT>(&lds_dtab);
-    load_exp_table<kFcNT>(lds_etab);
-    __syncthreads();
-    const int r = blockIdx.y;
-    const int i0 = ((int)blockIdx.x * kFcNT + (int)threadIdx.x) * 2;
-    if (i0 >= a.Ns) return;
-    const uint32_t rep = a.first_filter + (uint32_t)r;
-    const uint32_t key0 = a.keyp[0], key1 = a.keyp[1];
-    const ModelConst mc = a.mc[r];
-    const bool alive = a.scal[r].S > 0.0;
+    fc_load_tables(&lds_dtab, lds_etab);
+    FcLane l;
+    if (!fc_lane(a, DY, DX, &l)) return;
+    const ModelConst mc = a.mc[l.r];
     double x[DX][2];
 #pragma unroll
     for (int d = 0; d < DX; ++d) {
-        const double2 xs = *reinterpret_cast<const double2*>(a.x0 + (size_t)d * xplane + (size_t)r * a.Npad + i0);
+        const double2 xs = *reinterpret_cast<const double2*>(a.x0 + (size_t)d * xplane + (size_t)l.r * a.Npad + l.i0);
         x[d][0] = xs.x; x[d][1] = xs.y;
     }
-    const double y0 = a.last_obs ? a.last_obs[r] : 0.0;
-    double yp[2] = {y0, y0};                                       // component 0 of the previous observation
-    const size_t plane = (size_t)a.Ns;
-    double* yrow = a.y_out + (size_t)r * a.H * DY * plane + i0;
-    double* xrow = a.x_out ? a.x_out + (size_t)r * a.H * DX * plane + i0 : nullptr;
+    double yp[2] = {l.y0, l.y0};                                   // component 0 of the previous observation
     for (int k = 0; k < a.H; ++k) {
         const uint32_t kk = (uint32_t)k << 8;
         double y[DY][2];
@@ -227,12 +229,12 @@ __global__ __launch_bounds__(kFcNT) void k_fc_horizon_user(const FcArgs a, const
         for (int c = 0; c < 2; ++c) {
             double zs[4], zo[4];
             {
-                const u32x4 o = philox4x32_10((uint32_t)(i0 + c), (uint32_t)a.t0, rep, (uint32_t)STREAM_FC_SIM + kk, key0, key1);
+                const u32x4 o = philox4x32_10((uint32_t)(l.i0 + c), (uint32_t)a.t0, l.rep, (uint32_t)STREAM_FC_SIM + kk, l.key0, l.key1);
                 pair_normals(o.v0, o.v1, &lds_dtab, &zs[0], &zo[0]);
                 if constexpr (DM > 1) pair_normals(o.v2, o.v3, &lds_dtab, &zs[1], &zo[1]);
             }
             if constexpr (DM > 2) {
-                const u32x4 o = philox4x32_10((uint32_t)(i0 + c), (uint32_t)a.t0, rep, (uint32_t)STREAM_FC_SIM2 + kk, key0, key1);
+                const u32x4 o = philox4x32_10((uint32_t)(l.i0 + c), (uint32_t)a.t0, l.rep, (uint32_t)STREAM_FC_SIM2 + kk, l.key0, l.key1);
                 pair_normals(o.v0, o.v1, &lds_dtab, &zs[2], &zo[2]);
                 if constexpr (DM > 3) pair_normals(o.v2, o.v3, &lds_dtab, &zs[3], &zo[3]);
             }
@@ -244,17 +246,11 @@ __global__ __launch_bounds__(kFcNT) void k_fc_horizon_user(const FcArgs a, const
 #pragma unroll
             for (int d = 0; d < DX; ++d) x[d][c] = xn[d];
 #pragma unroll
-            for (int j = 0; j < DY; ++j) y[j][c] = alive ? yv[j] : dnan();
+            for (int j = 0; j < DY; ++j) y[j][c] = l.alive ? yv[j] : dnan();
             yp[c] = y[0][c];
         }
-#pragma unroll
-        for (int j = 0; j < DY; ++j) *reinterpret_cast<double2*>(yrow + (size_t)j * plane) = make_double2(y[j][0], y[j][1]);
-        yrow += (size_t)DY * plane;
-        if (xrow) {
-#pragma unroll
-            for (int d = 0; d < DX; ++d) *reinterpret_cast<double2*>(xrow + (size_t)d * plane) = make_double2(x[d][0], x[d][1]);
-            xrow += (size_t)DX * plane;
-        }
+        fc_store_row<DY>(l.yrow, l.plane, y);
+        if (l.xrow) fc_store_row<DX>(l.xrow, l.plane, x);
     }
 }
 
@@ -267,20 +263,11 @@ __global__ __launch_bounds__(kFcNT) void k_fc_horizon_user(const FcArgs a, const
 //   x <- mean(x, y_prev, tu) + z_s tu[2] sqrt(1 - tu[3]^2);  y <- z_o exp(x / 2);  y_prev <- y
 // e: four normals of one Philox call (STREAM_FC_LW_JIT), (z_s, z_o): words 0-1 of a second one (STREAM_FC_LW_SIM).
 // =======================================================================================
-struct FcLwArgs {
-    const double* x;           // [R][Npad] particles of the last step
-    const double* th;          // [R][Npad][4] their transformed parameters
-    const double* cdf;         // [R][Npad] integer cdf of the second-stage weights
-    const double* l2_T; const double* l2_R; const FilterScalars* scal;
-    const double* last_obs;    // [R]
-    double* x0; double* th0;   // [R][Npad], [R][Npad][4]: the start population
-    uint32_t* start;           // [R][Npad]
+struct FcLwArgs : FcCommon {      // x, x0: [R][Npad]; cdf: of the second-stage weights; last_obs is never null
+    const double* th;          // [R][Npad][4] transformed parameters of the particles of the last step
+    double* th0;               // [R][Npad][4] those of the start population
     double* mom;               // [R][B][16] tile partials of the 14 moments
     const double* prop;        // [R][16] theta-bar[4], L[10]
-    double* y_out; double* x_out;
-    const uint32_t* keyp;
-    uint32_t first_filter;
-    int32_t N, Npad, Ns, B, Bs, Bpow2, t0, H;
     double a_shrink;
     int32_t trans[kDP];
 };
@@ -355,41 +342,31 @@ __global__ __launch_bounds__(64) void k_fc_lw_prop(const double* momtot, int N, 
 __global__ __launch_bounds__(kFcNT) void k_fc_lw_horizon(const FcLwArgs a) {
     __shared__ __attribute__((aligned(16))) DrawTabs lds_dtab;
     __shared__ __attribute__((aligned(16))) ExpTabEntry lds_etab[SSME_EXP_TABLE_SIZE];
-    load_log_table<kFcNT>(&lds_dtab);
-    load_exp_table<kFcNT>(lds_etab);
-    __syncthreads();
-    const int r = blockIdx.y;
-    const int i0 = ((int)blockIdx.x * kFcNT + (int)threadIdx.x) * 2;
-    if (i0 >= a.Ns) return;
-    const uint32_t rep = a.first_filter + (uint32_t)r;
-    const uint32_t key0 = a.keyp[0], key1 = a.keyp[1];
-    const bool alive = a.scal[r].S > 0.0;
+    fc_load_tables(&lds_dtab, lds_etab);
+    FcLane l;
+    if (!fc_lane(a, 1, 1, &l)) return;
     double prop[14];
 #pragma unroll
-    for (int q = 0; q < 14; ++q) prop[q] = a.prop[(size_t)r * 16 + q];       // uniform: scalar loads
-    const size_t rowoff = (size_t)r * a.Npad;
-    const double2 xs = *reinterpret_cast<const double2*>(a.x0 + rowoff + i0);
+    for (int q = 0; q < 14; ++q) prop[q] = a.prop[(size_t)l.r * 16 + q];     // uniform: scalar loads
+    const size_t rowoff = (size_t)l.r * a.Npad;
+    const double2 xs = *reinterpret_cast<const double2*>(a.x0 + rowoff + l.i0);
     double x[2] = {xs.x, xs.y};
     double th[kDP][2];
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
         double trec[kDP];
-        th_load(a.th0, rowoff + (size_t)(i0 + c), trec);
+        th_load(a.th0, rowoff + (size_t)(l.i0 + c), trec);
 #pragma unroll
         for (int d = 0; d < kDP; ++d) th[d][c] = trec[d];
     }
-    const double y0 = a.last_obs[r];
-    double yp[2] = {y0, y0};
-    const size_t plane = (size_t)a.Ns;
-    double* yrow = a.y_out + (size_t)r * a.H * plane + i0;
-    double* xrow = a.x_out ? a.x_out + (size_t)r * a.H * plane + i0 : nullptr;
+    double yp[2] = {l.y0, l.y0};
     const double om = 1.0 - a.a_shrink;
     for (int k = 0; k < a.H; ++k) {
         const uint32_t kk = (uint32_t)k << 8;
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
             double e[kDP];
-            const u32x4 o1 = philox4x32_10((uint32_t)(i0 + c), (uint32_t)a.t0, rep, (uint32_t)STREAM_FC_LW_JIT + kk, key0, key1);
+            const u32x4 o1 = philox4x32_10((uint32_t)(l.i0 + c), (uint32_t)a.t0, l.rep, (uint32_t)STREAM_FC_LW_JIT + kk, l.key0, l.key1);
             pair_normals(o1.v0, o1.v1, &lds_dtab, &e[0], &e[1]);
             pair_normals(o1.v2, o1.v3, &lds_dtab, &e[2], &e[3]);
             double tu[kDP];
@@ -403,18 +380,17 @@ __global__ __launch_bounds__(kFcNT) void k_fc_lw_horizon(const FcLwArgs a) {
                 th[d][c] = mm + acc;
                 tu[d] = tr_inv(a.trans[d], th[d][c], lds_etab);
             }
-            const u32x4 o2 = philox4x32_10((uint32_t)(i0 + c), (uint32_t)a.t0, rep, (uint32_t)STREAM_FC_LW_SIM + kk, key0, key1);
+            const u32x4 o2 = philox4x32_10((uint32_t)(l.i0 + c), (uint32_t)a.t0, l.rep, (uint32_t)STREAM_FC_LW_SIM + kk, l.key0, l.key1);
             double zs, zo;
             pair_normals(o2.v0, o2.v1, &lds_dtab, &zs, &zo);
             const double xk = x[c];
             const double mean = (tu[1] + tu[0] * (xk - tu[1])) + ((yp[c] * tu[3]) * tu[2]) * dexp_scaled_t(-0.5 * xk, 0, lds_etab);
             x[c] = mean + zs * (tu[2] * dsqrt(1.0 - tu[3] * tu[3]));
             const double yv = zo * dexp_scaled_t(0.5 * x[c], 0, lds_etab);
-            yp[c] = alive ? yv : dnan();
+            yp[c] = l.alive ? yv : dnan();
         }
-        *reinterpret_cast<double2*>(yrow) = make_double2(yp[0], yp[1]);
-        yrow += plane;
-        if (xrow) { *reinterpret_cast<double2*>(xrow) = make_double2(x[0], x[1]); xrow += plane; }
+        fc_store_row<1>(l.yrow, l.plane, &yp);
+        if (l.xrow) fc_store_row<1>(l.xrow, l.plane, &x);
     }
 }
 

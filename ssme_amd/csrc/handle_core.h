@@ -1,7 +1,8 @@
 // handle_core.h -- host state and plumbing that the two filter handles of pf_api.hip share (the bootstrap handle ssme_pf_s and
 // the Liu-West handle ssme_lw_s both derive from HandleCore): tile layout, stream and events, device buffers owned by the
 // handle, the dynamic-LDS grants of the kernels (grant_lds), error reporting, the launches and shard bookkeeping that both filters
-// repeat, and the entry points that both C ABIs offer under their own names.
+// repeat, and the entry points that both C ABIs offer under their own names.  The forecast's buffers (Forecast) and what the two
+// *_sim_future_obs do around their own kernels are here too: forecast_prepare, forecast_plan, forecast_finish, forecast_elapsed.
 #pragma once
 #include "../../include/ssme_pf.h"
 #include "pf_kernels.h"
@@ -51,6 +52,20 @@ static bool set_layout(Layout* l, int n_particles, int n_filters, int tile, int 
     return world < 1 || (world - 1) * l->sh_Bl < B;
 }
 
+// forecast (forecast.h, *_sim_future_obs): buffers of its own, allocated on first use (forecast_prepare)
+struct Forecast {
+    std::vector<double> h_last_obs;     // [R] y_prev of this call, as uploaded
+    double *T, *R;               // [R][Bs] level-2 tables of the start draw
+    FilterScalars* scal;         // [R] S' of the start draw
+    double* last;                // [R] h_last_obs on the device
+    double* x0;                  // [planes][R][Npad] states of the start population
+    uint32_t* start;             // [R][Npad] its ancestors
+    double *y, *x;               // samples, rows of Ns doubles: cap_y / cap_x doubles
+    size_t cap_y, cap_x;
+    hipEvent_t ev[3];            // call start, horizon kernel start, horizon kernel end
+    float ms_horizon, ms_call;
+};
+
 struct HandleCore : Layout {
     hipStream_t stream;            // where the handle's work is queued: own_stream, or the caller's (set_stream)
     hipStream_t own_stream;        // the stream created with the handle
@@ -73,6 +88,7 @@ struct HandleCore : Layout {
     int sh_check;                  // 1 while a driver launches a step on the fixed halo: the kernel verifies its source tiles
     long sh_exchanged;             // tiles received from other ranks during the last native series
     std::vector<std::pair<void*, bool>> owned;     // (buffer, pinned) from own_alloc: what release_core frees
+    Forecast fc;
 };
 
 static int fail(HandleCore* h, const char* what, hipError_t e) {
@@ -103,7 +119,7 @@ static hipError_t own_alloc(HandleCore* h, T*& p, size_t bytes, Mem kind = Mem::
     if (kind != Mem::zeroed) return hipSuccess;
     // hipMemset of device memory may return before the fill has run, and the handle's stream is non-blocking: it does not wait for
     // the null stream.  Wait here, so that the fill cannot land after a kernel queued on the handle's stream next (the first
-    // forecast of a handle: S' of k_level2_plan was zeroed again between k_fc_start and k_fc_horizon, which then wrote NaN).
+    // forecast of a handle: S' of k_level2_plan was zeroed again between the start and the horizon kernel, which then wrote NaN).
     e = hipMemset(q, 0, bytes);
     return e != hipSuccess ? e : hipStreamSynchronize(nullptr);
 }
@@ -143,6 +159,7 @@ static void release_core(HandleCore* h) {
     h->owned.clear();
     if (h->ev0) hipEventDestroy(h->ev0);
     if (h->ev1) hipEventDestroy(h->ev1);
+    for (hipEvent_t& e : h->fc.ev) if (e) hipEventDestroy(e);
     if (h->own_stream) hipStreamDestroy(h->own_stream);
 }
 
@@ -236,6 +253,63 @@ static int read_loglik(H* h, double* out) {
 static int elapsed_ms(const HandleCore* h, float* ms) {
     if (!h || !ms) return SSME_ERR_INVALID_ARG;
     *ms = h->last_ms;
+    return SSME_OK;
+}
+
+// ---- forecast: what ssme_pf_sim_future_obs and ssme_lw_sim_future_obs do around their own kernels ---------------------------
+// The common buffers and the events on first use (x0: x0_planes planes of [R][Npad]), the samples grown to ny / nx doubles (nx = 0:
+// no states asked for), the event of the call's start, and fc.h_last_obs (filled by the caller) on its way to the device.
+template <class H>
+static int forecast_prepare(H* h, int x0_planes, size_t ny, size_t nx) {
+    Forecast& f = h->fc;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const size_t R = h->R, nb = R * h->Bs, np = R * h->Npad;
+    if (!f.T) {
+        HIPCHK(own_alloc(h, f.T, sizeof(double) * nb));
+        HIPCHK(own_alloc(h, f.R, sizeof(double) * nb));
+        HIPCHK(own_alloc(h, f.scal, sizeof(FilterScalars) * R, Mem::zeroed));
+        HIPCHK(own_alloc(h, f.last, sizeof(double) * R));
+        HIPCHK(own_alloc(h, f.x0, sizeof(double) * np * x0_planes));
+        HIPCHK(own_alloc(h, f.start, sizeof(uint32_t) * np));
+        for (hipEvent_t& e : f.ev) HIPCHK(hipEventCreate(&e));
+    }
+    // capacity 0 while the buffer is replaced: a failed allocation leaves none
+    if (ny > f.cap_y) { f.cap_y = 0; HIPCHK(own_alloc(h, f.y, sizeof(double) * ny)); f.cap_y = ny; }
+    if (nx > f.cap_x) { f.cap_x = 0; HIPCHK(own_alloc(h, f.x, sizeof(double) * nx)); f.cap_x = nx; }
+    HIPCHK(hipEventRecord(f.ev[0], h->stream));
+    HIPCHK(hipMemcpyAsync(f.last, f.h_last_obs.data(), sizeof(double) * R, hipMemcpyHostToDevice, h->stream));
+    return SSME_OK;
+}
+
+// level-2 of the weights behind p.tsum_in / p.tmax_in (the last step's: those the expectations use) into the forecast's own tables
+// and scalars; p.t = the steps done so far.  Nothing is accounted and no ranges are planned.
+static void forecast_plan(HandleCore* h, StepArgs p) {
+    p.l2_T = h->fc.T; p.l2_R = h->fc.R; p.scal = h->fc.scal;
+    p.finalize_prev = 0; p.per_step = nullptr; p.ll_host = nullptr;
+    hipLaunchKernelGGL(k_level2_plan, dim3(h->R), dim3(1024), h->lds_bytes_plan, h->stream, p, 0);
+}
+
+// After the horizon kernel: its end event, the launches' errors, the downloads of y (rows_y rows of N out of rows of Ns), x (rows_x
+// rows; null: none) and the start draw's ancestors ([R][N] out of [R][Npad]; null: none), the wait, and the two times.
+static int forecast_finish(HandleCore* h, double* y_out, size_t rows_y, double* x_out, size_t rows_x, uint32_t* start_out) {
+    Forecast& f = h->fc;
+    const size_t N = h->N, Ns = (N + 1) & ~(size_t)1;
+    HIPCHK(hipEventRecord(f.ev[2], h->stream));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy2DAsync(y_out, sizeof(double) * N, f.y, sizeof(double) * Ns, sizeof(double) * N, rows_y, hipMemcpyDeviceToHost, h->stream));
+    if (x_out) HIPCHK(hipMemcpy2DAsync(x_out, sizeof(double) * N, f.x, sizeof(double) * Ns, sizeof(double) * N, rows_x, hipMemcpyDeviceToHost, h->stream));
+    if (start_out) HIPCHK(hipMemcpy2DAsync(start_out, sizeof(uint32_t) * N, f.start, sizeof(uint32_t) * h->Npad, sizeof(uint32_t) * N, h->R, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipEventElapsedTime(&f.ms_horizon, f.ev[1], f.ev[2]));
+    HIPCHK(hipEventElapsedTime(&f.ms_call, f.ev[0], f.ev[2]));
+    return SSME_OK;
+}
+
+// HIP-event times of the last forecast: the horizon kernel alone, the whole call without the downloads
+static int forecast_elapsed(const HandleCore* h, float* horizon_kernel_ms, float* call_ms) {
+    if (!h) return SSME_ERR_INVALID_ARG;
+    if (horizon_kernel_ms) *horizon_kernel_ms = h->fc.ms_horizon;
+    if (call_ms) *call_ms = h->fc.ms_call;
     return SSME_OK;
 }
 

@@ -67,17 +67,9 @@ struct ssme_pf_s : HandleCore {
     hipGraphExec_t gexec;
     int g_T, g_has_z, g_debug, g_logw, g_nt;
     std::vector<ModelConst> h_mc;
-    // forecast (forecast.h, ssme_pf_sim_future_obs): buffers of its own, allocated on first use
-    std::vector<double> h_gscale, h_last_obs;   // per filter: scale of the observation draw (set_params), y_prev of this call
-    double *fc_T, *fc_R;         // [R][Bs] level-2 tables of the start draw
-    FilterScalars* fc_scal;      // [R] S' of the start draw
-    double *fc_gscale, *fc_last; // [R]
-    double* fc_x0;               // [dx][R][Npad] states of the start population
-    uint32_t* fc_start;          // [R][Npad] its ancestors
-    double *fc_y, *fc_x;         // [R][H][dy][Ns] / [R][H][dx][Ns] samples, fc_cap doubles each
-    size_t fc_cap_y, fc_cap_x;
-    hipEvent_t fc_ev[3];         // call start, horizon kernel start, horizon kernel end
-    float fc_ms_horizon, fc_ms_call;
+    // forecast (HandleCore::fc): fc.x0 is [dx][R][Npad], the samples fc.y / fc.x [R][H][dy][Ns] / [R][H][dx][Ns]
+    std::vector<double> h_gscale;    // per filter: scale of the observation draw (set_params)
+    double* fc_gscale;               // [R] the same on the device, allocated on first use
 };
 
 // Wait for a stream with the latency of a poll: hipStreamSynchronize spins only briefly and then sleeps on an interrupt,
@@ -476,13 +468,6 @@ static int user_expectations_checked(ssme_pf_handle h) {
 #endif
 }
 
-// the horizon kernel of a forecast (forecast.h), one instantiation per built-in model (user models: launch_fc_user below)
-template <int MODEL>
-static void launch_fc_horizon(ssme_pf_handle h, const FcArgs& a) {
-    if constexpr (MODEL != MODEL_USER0)
-        hipLaunchKernelGGL((k_fc_horizon<MODEL>), dim3((a.Ns / 2 + kFcNT - 1) / kFcNT, h->R), dim3(kFcNT), 0, h->stream, a);
-}
-
 // does the compiled-in user model declare its observation draw (model_api.h: gsamp / gsamp_vec)?
 #if SSME_HAS_USER_MODEL
 constexpr bool kUserHasGsamp = user_gsamp<ssme_user_model0>::has;
@@ -490,17 +475,30 @@ constexpr bool kUserHasGsamp = user_gsamp<ssme_user_model0>::has;
 constexpr bool kUserHasGsamp = false;
 #endif
 
-// the two kernels of a user model's forecast: every state plane gathered at the ancestor's index, then all horizons.  ev: the
-// event recorded between them (start of the horizon kernel).  A template, so that a header without the draw instantiates neither
+// the start population of a forecast (forecast.h), every state plane gathered at the ancestor's index (DX = 1: the built-in models),
+// and the event of the horizon kernel's start
+template <int DX>
+static hipError_t launch_fc_start(ssme_pf_handle h, const FcArgs& a) {
+    hipLaunchKernelGGL((k_fc_start_vec<DX>), dim3(h->B, h->R), dim3(kFcNT), 0, h->stream, a, (size_t)h->R * h->Npad);
+    return hipEventRecord(h->fc.ev[1], h->stream);
+}
+
+// the horizon kernel of a forecast, one instantiation per built-in model
+template <int MODEL>
+static void launch_fc_horizon(ssme_pf_handle h, const FcArgs& a) {
+    if constexpr (MODEL != MODEL_USER0)
+        hipLaunchKernelGGL((k_fc_horizon<MODEL>), dim3((a.Ns / 2 + kFcNT - 1) / kFcNT, h->R), dim3(kFcNT), 0, h->stream, a);
+}
+
+// both kernels of a user model's forecast.  A template, so that a header without the observation draw instantiates neither
 template <class M>
-static hipError_t launch_fc_user(ssme_pf_handle h, const FcArgs& a, hipEvent_t ev) {
+static hipError_t launch_fc_user(ssme_pf_handle h, const FcArgs& a) {
     if constexpr (user_gsamp<M>::has) {
         constexpr int DX = user_dims<M>::dx, DY = user_dims<M>::dy;
-        const size_t xplane = (size_t)h->R * h->Npad;
-        hipLaunchKernelGGL((k_fc_start_vec<DX>), dim3(h->B, h->R), dim3(kFcNT), 0, h->stream, a, xplane);
-        const hipError_t e = hipEventRecord(ev, h->stream);
+        const hipError_t e = launch_fc_start<DX>(h, a);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((k_fc_horizon_user<M, DX, DY>), dim3((a.Ns / 2 + kFcNT - 1) / kFcNT, h->R), dim3(kFcNT), 0, h->stream, a, xplane);
+        hipLaunchKernelGGL((k_fc_horizon_user<M, DX, DY>), dim3((a.Ns / 2 + kFcNT - 1) / kFcNT, h->R), dim3(kFcNT), 0, h->stream, a,
+                           (size_t)h->R * h->Npad);
     }
     return hipSuccess;
 }
@@ -603,7 +601,6 @@ int ssme_pf_destroy(ssme_pf_handle h) {
     hipSetDevice(h->cfg.device);
     if (h->gexec) { hipStreamSynchronize(h->stream); hipGraphExecDestroy(h->gexec); }
     release_core(h);
-    for (hipEvent_t& e : h->fc_ev) if (e) hipEventDestroy(e);      // the forecast's events: after release_core has waited for the stream
     delete h;
     return SSME_OK;
 }
@@ -1313,71 +1310,43 @@ int ssme_pf_sim_future_obs(ssme_pf_handle h, int32_t num_steps, const double* la
     const bool user = h->cfg.model == SSME_MODEL_USER0;
     if (user && !kUserHasGsamp) { h->err = "this user model declares no observation draw (gsamp / gsamp_vec, model_api.h)"; return SSME_ERR_UNSUPPORTED; }
     if (!h->params_set || h->t < 1) { h->err = "sim_future_obs before the first step"; return SSME_ERR_STATE; }
-    HIPCHK(hipSetDevice(h->cfg.device));
     const int H = num_steps, R = h->R, N = h->N;
-    const int Ns = (N + 1) & ~1;
     const int dx = h->dx, dy = h->dy;                      // 1 unless this is a vector user model
-    const size_t nb = (size_t)R * h->Bs, np = (size_t)R * h->Npad, rows = (size_t)R * H;
-    const size_t nsy = rows * dy * Ns, nsx = rows * dx * Ns;
-    if (!h->fc_T) {
-        HIPCHK(own_alloc(h, h->fc_T, sizeof(double) * nb));
-        HIPCHK(own_alloc(h, h->fc_R, sizeof(double) * nb));
-        HIPCHK(own_alloc(h, h->fc_scal, sizeof(FilterScalars) * R, Mem::zeroed));
-        HIPCHK(own_alloc(h, h->fc_gscale, sizeof(double) * R));
-        HIPCHK(own_alloc(h, h->fc_last, sizeof(double) * R));
-        HIPCHK(own_alloc(h, h->fc_x0, sizeof(double) * np * dx));
-        HIPCHK(own_alloc(h, h->fc_start, sizeof(uint32_t) * np));
-        for (hipEvent_t& e : h->fc_ev) HIPCHK(hipEventCreate(&e));
-    }
-    if (nsy > h->fc_cap_y) { h->fc_cap_y = 0; HIPCHK(own_alloc(h, h->fc_y, sizeof(double) * nsy)); h->fc_cap_y = nsy; }
-    if (x_out && nsx > h->fc_cap_x) { h->fc_cap_x = 0; HIPCHK(own_alloc(h, h->fc_x, sizeof(double) * nsx)); h->fc_cap_x = nsx; }
-    h->h_last_obs.assign(R, 0.0);
-    if (last_obs) for (int r = 0; r < R; ++r) h->h_last_obs[r] = h->cfg.dtype == SSME_F32 ? f32r(last_obs[r]) : last_obs[r];
-    HIPCHK(hipEventRecord(h->fc_ev[0], h->stream));
+    const size_t Ns = (N + 1) & ~1, rows = (size_t)R * H;
+    h->fc.h_last_obs.assign(R, 0.0);
+    if (last_obs) for (int r = 0; r < R; ++r) h->fc.h_last_obs[r] = h->cfg.dtype == SSME_F32 ? f32r(last_obs[r]) : last_obs[r];
+    int rc = forecast_prepare(h, dx, rows * dy * Ns, x_out ? rows * dx * Ns : 0);
+    if (rc != SSME_OK) return rc;
+    if (!h->fc_gscale) HIPCHK(own_alloc(h, h->fc_gscale, sizeof(double) * R));
     HIPCHK(hipMemcpyAsync(h->fc_gscale, h->h_gscale.data(), sizeof(double) * R, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->fc_last, h->h_last_obs.data(), sizeof(double) * R, hipMemcpyHostToDevice, h->stream));
     {
-        // level-2 of the last step's weights (the weights ssme_pf_get_expectations uses) into the forecast's own tables and scalars
+        // level-2 of the last step's weights (the weights ssme_pf_get_expectations uses): step_args reads buffers `cur`
         StepArgs p = step_args(h);
-        p.tsum_in = h->tsum[h->cur]; p.tmax_in = h->tmax[h->cur];
-        p.l2_T = h->fc_T; p.l2_R = h->fc_R; p.scal = h->fc_scal;
-        p.t = h->t; p.finalize_prev = 0; p.per_step = nullptr; p.ll_host = nullptr;
-        hipLaunchKernelGGL(k_level2_plan, dim3(R), dim3(1024), h->lds_bytes_plan, h->stream, p, 0);
+        p.t = h->t;
+        forecast_plan(h, p);
     }
     FcArgs a{};
-    a.x = h->x[h->cur]; a.cdf = h->cdf[h->cur]; a.l2_T = h->fc_T; a.l2_R = h->fc_R; a.scal = h->fc_scal; a.mc = h->mc;
-    a.gscale = h->fc_gscale; a.last_obs = h->fc_last; a.x0 = h->fc_x0; a.start = h->fc_start;
-    a.y_out = h->fc_y; a.x_out = x_out ? h->fc_x : nullptr;
+    a.x = h->x[h->cur]; a.cdf = h->cdf[h->cur]; a.l2_T = h->fc.T; a.l2_R = h->fc.R; a.scal = h->fc.scal; a.mc = h->mc;
+    a.gscale = h->fc_gscale; a.last_obs = h->fc.last; a.x0 = h->fc.x0; a.start = h->fc.start;
+    a.y_out = h->fc.y; a.x_out = x_out ? h->fc.x : nullptr;
     a.keyp = h->keybuf; a.first_filter = h->cfg.first_filter_id;
-    a.N = N; a.Npad = h->Npad; a.Ns = Ns; a.B = h->B; a.Bs = h->Bs; a.Bpow2 = h->Bpow2; a.tile = h->tile; a.t0 = h->t; a.H = H;
+    a.N = N; a.Npad = h->Npad; a.Ns = (int)Ns; a.B = h->B; a.Bs = h->Bs; a.Bpow2 = h->Bpow2; a.tile = h->tile; a.t0 = h->t; a.H = H;
     if (user) {
 #if SSME_HAS_USER_MODEL
-        HIPCHK(launch_fc_user<ssme_user_model0>(h, a, h->fc_ev[1]));
+        HIPCHK(launch_fc_user<ssme_user_model0>(h, a));
 #endif
     } else {
-        hipLaunchKernelGGL(k_fc_start, dim3(h->B, R), dim3(kFcNT), 0, h->stream, a);
-        HIPCHK(hipEventRecord(h->fc_ev[1], h->stream));
+        HIPCHK(launch_fc_start<1>(h, a));
         with_model(h->cfg.model, [&](auto m) { launch_fc_horizon<decltype(m)::value>(h, a); });
     }
-    HIPCHK(hipEventRecord(h->fc_ev[2], h->stream));
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy2DAsync(y_out, sizeof(double) * N, h->fc_y, sizeof(double) * Ns, sizeof(double) * N, rows * dy, hipMemcpyDeviceToHost, h->stream));
-    if (x_out) HIPCHK(hipMemcpy2DAsync(x_out, sizeof(double) * N, h->fc_x, sizeof(double) * Ns, sizeof(double) * N, rows * dx, hipMemcpyDeviceToHost, h->stream));
-    if (start_out) HIPCHK(hipMemcpy2DAsync(start_out, sizeof(uint32_t) * N, h->fc_start, sizeof(uint32_t) * h->Npad, sizeof(uint32_t) * N, R, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipEventElapsedTime(&h->fc_ms_horizon, h->fc_ev[1], h->fc_ev[2]));
-    HIPCHK(hipEventElapsedTime(&h->fc_ms_call, h->fc_ev[0], h->fc_ev[2]));
+    rc = forecast_finish(h, y_out, rows * dy, x_out, rows * dx, start_out);
+    if (rc != SSME_OK) return rc;
     round_out(h, y_out, rows * dy * N);
     round_out(h, x_out, rows * dx * N);
     return SSME_OK;
 }
 
-int ssme_pf_forecast_elapsed_ms(ssme_pf_handle h, float* horizon_kernel_ms, float* call_ms) {
-    if (!h) return SSME_ERR_INVALID_ARG;
-    if (horizon_kernel_ms) *horizon_kernel_ms = h->fc_ms_horizon;
-    if (call_ms) *call_ms = h->fc_ms_call;
-    return SSME_OK;
-}
+int ssme_pf_forecast_elapsed_ms(ssme_pf_handle h, float* horizon_kernel_ms, float* call_ms) { return forecast_elapsed(h, horizon_kernel_ms, call_ms); }
 
 int ssme_pf_last_elapsed_ms(ssme_pf_handle h, float* ms) { return elapsed_ms(h, ms); }
 
@@ -1635,15 +1604,9 @@ struct ssme_lw_s : HandleCore {
     int32_t *l2lo[2], *l2hi[2];
     FilterScalars* l2s[2];
     LwScalars* scal;
-    // forecast (forecast.h, ssme_lw_sim_future_obs): buffers of its own, allocated on first use
-    std::vector<double> h_last_obs;
-    double *fc_T, *fc_R, *fc_last, *fc_x0, *fc_th0, *fc_mom, *fc_momtot, *fc_prop;
-    FilterScalars* fc_scal;
-    uint32_t* fc_start;
-    double *fc_y, *fc_x;             // [R][H][Ns] samples
-    size_t fc_cap_y, fc_cap_x;
-    hipEvent_t fc_ev[3];             // call start, horizon kernel start, horizon kernel end
-    float fc_ms_horizon, fc_ms_call;
+    // forecast (HandleCore::fc; samples [R][H][Ns]): the start population's parameter records [R][Npad][4], their moment partials
+    // [R][B][16] and totals [R][16], theta-bar and L [R][16]; allocated on first use
+    double *fc_th0, *fc_mom, *fc_momtot, *fc_prop;
 };
 
 static LwArgs lw_args(ssme_lw_handle h) {
@@ -1788,7 +1751,6 @@ int ssme_lw_destroy(ssme_lw_handle h) {
     if (!h) return SSME_ERR_INVALID_ARG;
     hipSetDevice(h->cfg.device);
     release_core(h);
-    for (hipEvent_t& e : h->fc_ev) if (e) hipEventDestroy(e);      // the forecast's events: after release_core has waited for the stream
     delete h;
     return SSME_OK;
 }
@@ -2289,42 +2251,25 @@ int ssme_lw_sim_future_obs(ssme_lw_handle h, int32_t num_steps, const double* la
     if (!h || !y_out || !last_obs || num_steps < 1 || num_steps > kFcMaxSteps) return SSME_ERR_INVALID_ARG;
     if (h->shard_world > 0) { h->err = "forecasts of particle-sharded filters are not implemented"; return SSME_ERR_UNSUPPORTED; }
     if (h->t < 1) { h->err = "sim_future_obs before the first step"; return SSME_ERR_STATE; }
-    HIPCHK(hipSetDevice(h->cfg.device));
     const int H = num_steps, R = h->R, N = h->N;
-    const int Ns = (N + 1) & ~1;
-    const size_t nb = (size_t)R * h->Bs, np = (size_t)R * h->Npad, ns = (size_t)R * H * Ns;
-    if (!h->fc_T) {
-        HIPCHK(own_alloc(h, h->fc_T, sizeof(double) * nb));
-        HIPCHK(own_alloc(h, h->fc_R, sizeof(double) * nb));
-        HIPCHK(own_alloc(h, h->fc_scal, sizeof(FilterScalars) * R, Mem::zeroed));
-        HIPCHK(own_alloc(h, h->fc_last, sizeof(double) * R));
-        HIPCHK(own_alloc(h, h->fc_x0, sizeof(double) * np));
-        HIPCHK(own_alloc(h, h->fc_th0, sizeof(double) * np * kDP));
-        HIPCHK(own_alloc(h, h->fc_start, sizeof(uint32_t) * np));
+    const size_t Ns = (N + 1) & ~1, rows = (size_t)R * H;
+    h->fc.h_last_obs.assign(last_obs, last_obs + R);
+    int rc = forecast_prepare(h, 1, rows * Ns, x_out ? rows * Ns : 0);
+    if (rc != SSME_OK) return rc;
+    if (!h->fc_th0) {
+        HIPCHK(own_alloc(h, h->fc_th0, sizeof(double) * (size_t)R * h->Npad * kDP));
         HIPCHK(own_alloc(h, h->fc_mom, sizeof(double) * (size_t)R * h->B * 16));
         HIPCHK(own_alloc(h, h->fc_momtot, sizeof(double) * (size_t)R * 16, Mem::zeroed));
         HIPCHK(own_alloc(h, h->fc_prop, sizeof(double) * (size_t)R * 16, Mem::zeroed));
-        for (hipEvent_t& e : h->fc_ev) HIPCHK(hipEventCreate(&e));
     }
-    if (ns > h->fc_cap_y) { h->fc_cap_y = 0; HIPCHK(own_alloc(h, h->fc_y, sizeof(double) * ns)); h->fc_cap_y = ns; }
-    if (x_out && ns > h->fc_cap_x) { h->fc_cap_x = 0; HIPCHK(own_alloc(h, h->fc_x, sizeof(double) * ns)); h->fc_cap_x = ns; }
-    h->h_last_obs.assign(last_obs, last_obs + R);
-    HIPCHK(hipEventRecord(h->fc_ev[0], h->stream));
-    HIPCHK(hipMemcpyAsync(h->fc_last, h->h_last_obs.data(), sizeof(double) * R, hipMemcpyHostToDevice, h->stream));
-    {
-        // level-2 of the second-stage weights of the last step (the weights ssme_lw_get_expectations uses) into the forecast's own tables
-        StepArgs p{};
-        p.tsum_in = h->tsumB; p.tmax_in = h->tmaxB; p.l2_T = h->fc_T; p.l2_R = h->fc_R; p.scal = h->fc_scal;
-        p.B = h->B; p.Bs = h->Bs; p.Bpow2 = h->Bpow2; p.rshift = h->rshift; p.R = R; p.N = N; p.tile = kTile;
-        p.resampler = RESAMP_MULTINOMIAL; p.resamp_sched = 1; p.t = h->t;
-        hipLaunchKernelGGL(k_level2_plan, dim3(R), dim3(1024), h->lds_bytes_plan, h->stream, p, 0);
-    }
+    // level-2 of the second-stage weights of the last step (the weights ssme_lw_get_expectations uses)
+    forecast_plan(h, lw_plan_args(h, 0, h->t, 0, h->tsumB, h->tmaxB));
     FcLwArgs a{};
-    a.x = h->xB; a.th = h->thB; a.cdf = h->cdfB; a.l2_T = h->fc_T; a.l2_R = h->fc_R; a.scal = h->fc_scal; a.last_obs = h->fc_last;
-    a.x0 = h->fc_x0; a.th0 = h->fc_th0; a.start = h->fc_start; a.mom = h->fc_mom; a.prop = h->fc_prop;
-    a.y_out = h->fc_y; a.x_out = x_out ? h->fc_x : nullptr;
+    a.x = h->xB; a.th = h->thB; a.cdf = h->cdfB; a.l2_T = h->fc.T; a.l2_R = h->fc.R; a.scal = h->fc.scal; a.last_obs = h->fc.last;
+    a.x0 = h->fc.x0; a.th0 = h->fc_th0; a.start = h->fc.start; a.mom = h->fc_mom; a.prop = h->fc_prop;
+    a.y_out = h->fc.y; a.x_out = x_out ? h->fc.x : nullptr;
     a.keyp = h->keybuf; a.first_filter = h->cfg.first_filter_id;
-    a.N = N; a.Npad = h->Npad; a.Ns = Ns; a.B = h->B; a.Bs = h->Bs; a.Bpow2 = h->Bpow2; a.t0 = h->t; a.H = H;
+    a.N = N; a.Npad = h->Npad; a.Ns = (int)Ns; a.B = h->B; a.Bs = h->Bs; a.Bpow2 = h->Bpow2; a.t0 = h->t; a.H = H;
     a.a_shrink = (3.0 * h->cfg.delta - 1.0) / (2.0 * h->cfg.delta);
     for (int d = 0; d < kDP; ++d) a.trans[d] = h->cfg.transforms[d];
     hipLaunchKernelGGL(k_fc_lw_start, dim3(h->B, R), dim3(kLwNT), 0, h->stream, a);
@@ -2334,27 +2279,18 @@ int ssme_lw_sim_future_obs(ssme_lw_handle h, int32_t num_steps, const double* la
         hipLaunchKernelGGL(k_lw_mom_totals, dim3(kNMom, R), dim3(64), 0, h->stream, m);
     }
     hipLaunchKernelGGL(k_fc_lw_prop, dim3(R), dim3(64), 0, h->stream, (const double*)h->fc_momtot, N, a.a_shrink, h->fc_prop);
-    HIPCHK(hipEventRecord(h->fc_ev[1], h->stream));
-    hipLaunchKernelGGL(k_fc_lw_horizon, dim3((Ns / 2 + kFcNT - 1) / kFcNT, R), dim3(kFcNT), 0, h->stream, a);
-    HIPCHK(hipEventRecord(h->fc_ev[2], h->stream));
-    HIPCHK(hipGetLastError());
-    const size_t rows = (size_t)R * H;
-    HIPCHK(hipMemcpy2DAsync(y_out, sizeof(double) * N, h->fc_y, sizeof(double) * Ns, sizeof(double) * N, rows, hipMemcpyDeviceToHost, h->stream));
-    if (x_out) HIPCHK(hipMemcpy2DAsync(x_out, sizeof(double) * N, h->fc_x, sizeof(double) * Ns, sizeof(double) * N, rows, hipMemcpyDeviceToHost, h->stream));
-    if (start_out) HIPCHK(hipMemcpy2DAsync(start_out, sizeof(uint32_t) * N, h->fc_start, sizeof(uint32_t) * h->Npad, sizeof(uint32_t) * N, R, hipMemcpyDeviceToHost, h->stream));
-    if (prop_out) HIPCHK(hipMemcpyAsync(prop_out, h->fc_prop, sizeof(double) * (size_t)R * 16, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipEventElapsedTime(&h->fc_ms_horizon, h->fc_ev[1], h->fc_ev[2]));
-    HIPCHK(hipEventElapsedTime(&h->fc_ms_call, h->fc_ev[0], h->fc_ev[2]));
+    HIPCHK(hipEventRecord(h->fc.ev[1], h->stream));
+    hipLaunchKernelGGL(k_fc_lw_horizon, dim3((a.Ns / 2 + kFcNT - 1) / kFcNT, R), dim3(kFcNT), 0, h->stream, a);
+    rc = forecast_finish(h, y_out, rows, x_out, rows, start_out);
+    if (rc != SSME_OK) return rc;
+    if (prop_out) {                                   // after the times are taken: ev[2] closes on the horizon kernel, as for the bootstrap
+        HIPCHK(hipMemcpyAsync(prop_out, h->fc_prop, sizeof(double) * (size_t)R * 16, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+    }
     return SSME_OK;
 }
 
-int ssme_lw_forecast_elapsed_ms(ssme_lw_handle h, float* horizon_kernel_ms, float* call_ms) {
-    if (!h) return SSME_ERR_INVALID_ARG;
-    if (horizon_kernel_ms) *horizon_kernel_ms = h->fc_ms_horizon;
-    if (call_ms) *call_ms = h->fc_ms_call;
-    return SSME_OK;
-}
+int ssme_lw_forecast_elapsed_ms(ssme_lw_handle h, float* horizon_kernel_ms, float* call_ms) { return forecast_elapsed(h, horizon_kernel_ms, call_ms); }
 
 int ssme_lw_last_elapsed_ms(ssme_lw_handle h, float* ms) { return elapsed_ms(h, ms); }
 

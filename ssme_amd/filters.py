@@ -33,6 +33,29 @@ def user_model_has_gsamp():
     return bool(capi.lib().ssme_pf_user_model_has_gsamp())
 
 
+def _forecast(chk, fn, h, r, n, H, last_obs, dx=1, dy=1, states=False, start=False, prop=None):
+    """What the sim_future_obs methods share: y[r, H, n] ([r, H, dy, n] for dy > 1) and, when asked for, the states x (dx as dy), the
+    start draw's ancestors [r, n] and the Liu-West proposal [r, 16] are allocated, fn(h, H, last_obs, y, x, start[, prop]) is called
+    and checked, and y alone or the tuple of what was asked for is returned.  prop = None: the bootstrap call, which has no such
+    argument and takes last_obs = None as a null pointer."""
+    H = int(H)
+    lo = None if last_obs is None and prop is None else np.ascontiguousarray(np.broadcast_to(np.asarray(last_obs, dtype=np.float64), (r,)))
+    y = np.empty((r, max(H, 0), n) if dy == 1 else (r, max(H, 0), dy, n))
+    x = np.empty((r, max(H, 0), n) if dx == 1 else (r, max(H, 0), dx, n)) if states else None
+    st = np.empty((r, n), dtype=np.uint32) if start else None
+    pr = np.empty((r, 16)) if prop else None
+    chk(fn(h, H, capi.dptr(lo), capi.dptr(y), capi.dptr(x), capi.u32ptr(st), *(() if prop is None else (capi.dptr(pr),))))
+    out = tuple(v for v in (y, x, st, pr) if v is not None)
+    return y if len(out) == 1 else out
+
+
+def _forecast_elapsed_ms(chk, fn, h):
+    """HIP-event times (ms) of the last sim_future_obs: (horizon kernel alone, whole call without the download)."""
+    a, b = C.c_float(), C.c_float()
+    chk(fn(h, C.byref(a), C.byref(b)))
+    return a.value, b.value
+
+
 class ParticleFilterBank:
     """R independent bootstrap filters of N particles on one GPU (one C-ABI handle).
 
@@ -189,21 +212,12 @@ class ParticleFilterBank:
         and by user models whose prop reads its covariate).  states / start: also return the simulated states x[R, H, N] / the
         ancestors [R, N] of the start draw: y, or (y[, x][, start]).  A user model that declares its observation draw
         (user_model_has_gsamp) with a vector observation / state returns y[R, H, dim_y, N] / x[R, H, dim_x, N]."""
-        H = int(H)
         dx, dy = self._dims()
-        lo = None if last_obs is None else np.ascontiguousarray(np.broadcast_to(np.asarray(last_obs, dtype=np.float64), (self.r,)))
-        y = np.empty((self.r, max(H, 0), self.n) if dy == 1 else (self.r, max(H, 0), dy, self.n))
-        x = (np.empty((self.r, max(H, 0), self.n) if dx == 1 else (self.r, max(H, 0), dx, self.n))) if states else None
-        st = np.empty((self.r, self.n), dtype=np.uint32) if start else None
-        self._chk(capi.lib().ssme_pf_sim_future_obs(self._h, H, capi.dptr(lo), capi.dptr(y), capi.dptr(x), capi.u32ptr(st)))
-        out = (y,) + ((x,) if states else ()) + ((st,) if start else ())
-        return y if len(out) == 1 else out
+        return _forecast(self._chk, capi.lib().ssme_pf_sim_future_obs, self._h, self.r, self.n, H, last_obs, dx, dy, states, start)
 
     def forecast_elapsed_ms(self):
         """HIP-event times (ms) of the last sim_future_obs: (horizon kernel alone, whole call without the download)."""
-        a, b = C.c_float(), C.c_float()
-        self._chk(capi.lib().ssme_pf_forecast_elapsed_ms(self._h, C.byref(a), C.byref(b)))
-        return a.value, b.value
+        return _forecast_elapsed_ms(self._chk, capi.lib().ssme_pf_forecast_elapsed_ms, self._h)
 
     def weights(self, f=0):
         """(x, w) of filter f after the last step for host-side functionals: w = exp(logw - max logw); x: [dim_x, N] for a vector model."""
@@ -556,21 +570,12 @@ class svol_lw_1_par:
         (ssme_lw_sim_future_obs): y[R, H, N].  last_obs: the last observation, a scalar or one value per filter.  states / start /
         prop: also return the simulated states x[R, H, N] / the ancestors [R, N] of the start draw / [R, 16] = theta-bar[4] and
         the Cholesky factor L[10] (lower triangle by rows) of the start population as used."""
-        H = int(H)
-        lo = np.ascontiguousarray(np.broadcast_to(np.asarray(last_obs, dtype=np.float64), (self.r,)))
-        y = np.empty((self.r, max(H, 0), self.n))
-        x = np.empty_like(y) if states else None
-        st = np.empty((self.r, self.n), dtype=np.uint32) if start else None
-        pr = np.empty((self.r, 16)) if prop else None
-        self._chk(capi.lib().ssme_lw_sim_future_obs(self._h, H, capi.dptr(lo), capi.dptr(y), capi.dptr(x), capi.u32ptr(st), capi.dptr(pr)))
-        out = (y,) + ((x,) if states else ()) + ((st,) if start else ()) + ((pr,) if prop else ())
-        return y if len(out) == 1 else out
+        return _forecast(self._chk, capi.lib().ssme_lw_sim_future_obs, self._h, self.r, self.n, H, last_obs, states=states, start=start,
+                         prop=bool(prop))
 
     def forecast_elapsed_ms(self):
         """HIP-event times (ms) of the last sim_future_obs: (horizon kernel alone, whole call without the download)."""
-        a, b = C.c_float(), C.c_float()
-        self._chk(capi.lib().ssme_lw_forecast_elapsed_ms(self._h, C.byref(a), C.byref(b)))
-        return a.value, b.value
+        return _forecast_elapsed_ms(self._chk, capi.lib().ssme_lw_forecast_elapsed_ms, self._h)
 
     def last_elapsed_ms(self):
         ms = C.c_float()

@@ -1,4 +1,4 @@
-"""The forecast kernels (csrc/forecast.h: k_fc_start, k_fc_horizon, k_fc_lw_start, k_fc_lw_prop, k_fc_lw_horizon; the k_level2_plan and
+"""The forecast kernels (csrc/forecast.h: k_fc_start_vec, k_fc_horizon, k_fc_lw_start, k_fc_lw_prop, k_fc_lw_horizon; the k_level2_plan and
 k_lw_mom_totals launches of ssme_pf_sim_future_obs / ssme_lw_sim_future_obs in csrc/pf_api.hip) at the inputs of tests/fc_edge_cases.py,
 through the C ABI.  For every pair of that list:
   * start, x and y equal the numpy restatement of tests/forecast_ref.py to the bit (NaN for NaN, -0 != +0).  The bootstrap side starts
