@@ -74,6 +74,7 @@ struct HandleCore : Layout {
     std::string err;               // last_error
     int t;                         // next time index
     int32_t* plan_dev;             // [world][2] source-tile ranges (k_shard_plan)
+    int32_t* plan_pin;             // the same on their way to the host (pinned): what shard_plan_to_host stages in
     double* pin;                   // pinned, device-mapped host staging; the step API's R results are written here by the device
     double* pin_dev;               // the same memory as the device sees it
     uint32_t* keybuf;              // [2] Philox key = seed (lo, hi)
@@ -85,7 +86,6 @@ struct HandleCore : Layout {
                                    // [3] max of [0] over all ranks (reduce_flags after the time loop): what the fallback decision reads
     int32_t sh_stats[4];           // host copy of sh_flag after the last native series
     int sh_margin, sh_rows;        // halo margin (tiles on each side) and rows [margin | Bl own | margin] of the halo buffers
-    int sh_check;                  // 1 while a driver launches a step on the fixed halo: the kernel verifies its source tiles
     long sh_exchanged;             // tiles received from other ranks during the last native series
     std::vector<std::pair<void*, bool>> owned;     // (buffer, pinned) from own_alloc: what release_core frees
     Forecast fc;
@@ -218,6 +218,13 @@ static int enqueue_window_download(HandleCore* h, const int32_t* l2_lo, const in
         HIPCHK(hipMemcpyAsync(stage + 2 * d, l2_lo + d * Bl, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipMemcpyAsync(stage + 2 * d + 1, l2_hi + last, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     }
+    return SSME_OK;
+}
+
+// the plan buffers of a sharded handle: every rank's window on the device and its pinned staging
+static int alloc_plan_buffers(HandleCore* h) {
+    HIPCHK(own_alloc(h, h->plan_dev, sizeof(int32_t) * 2 * h->shard_world));
+    HIPCHK(own_alloc(h, h->plan_pin, sizeof(int32_t) * 2 * h->shard_world, Mem::pinned));
     return SSME_OK;
 }
 

@@ -86,6 +86,23 @@ static hipError_t wait_stream_low_latency(hipStream_t s) {
     }
 }
 
+// The tail of both *_shard_plan: every rank's window [lo, hi] on its way to the caller through plan_pin.  every_tile: unsorted
+// targets need every tile; else the windows come from the split level-2's per-tile ranges (more than 1024 tiles in total) or from
+// plan_dev (k_shard_plan).  Synchronises.
+static int shard_plan_to_host(HandleCore* h, bool every_tile, const int32_t* l2_lo, const int32_t* l2_hi, int32_t* lo_hi) {
+    if (every_tile) {
+        for (int d = 0; d < h->shard_world; ++d) { h->plan_pin[2 * d] = 0; h->plan_pin[2 * d + 1] = h->B - 1; }
+    } else if (h->split_l2) {
+        const int rc = enqueue_window_download(h, l2_lo, l2_hi, h->plan_pin);
+        if (rc != SSME_OK) return rc;
+    } else {
+        HIPCHK(hipMemcpyAsync(h->plan_pin, h->plan_dev, sizeof(int32_t) * 2 * h->shard_world, hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(wait_stream_low_latency(h->stream));
+    for (int d = 0; d < 2 * h->shard_world; ++d) lo_hi[d] = h->plan_pin[d];
+    return SSME_OK;
+}
+
 // Step APIs: the R results are awaited where they land.  The host marks the mapped result slots kStepPending (a NaN
 // payload no computation produces) before the launch and polls them instead of the stream's completion signal, which
 // trails the kernel's last store by its end-of-kernel cache write-back.  The stream stays ordered: the next call
@@ -158,6 +175,17 @@ static int n_theta_of(int model) {
 #endif
     return model == SSME_MODEL_SVOL_LEVERAGE ? 4 : 3;
 }
+// The bootstrap handle's pinned, device-mapped staging (pin / pin_dev), as offsets in doubles for a handle of R filters
+struct PinLayout {
+    static constexpr size_t kSwarmSlots = 8;                                // kMaxFunctionals means, then the mean log conditional likelihood
+    static_assert(kMaxFunctionals + 1 <= kSwarmSlots, "the swarm aggregates have 8 slots");
+    static constexpr size_t yz = 0;                                         // y and z of the step API
+    static constexpr size_t results = 2;                                    // its R results, written by the device
+    static size_t swarm(int R) { return results + (size_t)R; }              // ssme_pf_swarm_aggregate*
+    static size_t user(int R) { return swarm(R) + kSwarmSlots; }            // ssme_pf_swarm_aggregate_user: kMaxUserFunctionals means + 1
+    static size_t size(int R) { return user(R) + kMaxUserFunctionals + 1; }
+};
+
 static bool logw_needed(ssme_pf_handle h) { return h->keep_logw || h->cfg.resamp_sched > 1; }
 
 // arguments of the step that reads buffers `cur` and writes `cur ^ 1`
@@ -345,9 +373,9 @@ static void enqueue_step(ssme_pf_handle h, int t, int yi, int gi, bool has_z, bo
     StepArgs a = step_args(h);
     a.z = has_z ? h->zbuf : nullptr;
     if (from_step_staging) {
-        a.by_value = 1; a.y_now = h->pin[0]; a.z_now = has_z ? h->pin[1] : 0.0;
+        a.by_value = 1; a.y_now = h->pin[PinLayout::yz]; a.z_now = has_z ? h->pin[PinLayout::yz + 1] : 0.0;
         for (int d = 1; d < h->dy; ++d) a.y_now_v[d - 1] = h->y_step_v[d - 1];
-        if (!h->split_l2) { a.ticket = h->ticket; a.ll_host = results_to_host ? h->pin_dev + 2 : nullptr; }     // accounting inside the step kernel (its last workgroup)
+        if (!h->split_l2) { a.ticket = h->ticket; a.ll_host = results_to_host ? h->pin_dev + PinLayout::results : nullptr; }     // accounting inside the step kernel (its last workgroup)
     }
     a.per_step = record_per_step ? h->per_step : nullptr;
     a.t = t; a.yi = yi; a.gi = gi; a.finalize_prev = finalize_prev ? 1 : 0;
@@ -560,7 +588,7 @@ static int create_impl(const ssme_pf_config* cfg, int shard_rank, int shard_worl
         int rc2 = create_stream(h);
         if (rc2 != SSME_OK) return rc2;
         const size_t np = (size_t)h->R * h->Npad, nb = (size_t)h->R * h->Bs;
-        if (h->shard_world > 0) HIPCHK(own_alloc(h, h->plan_dev, sizeof(int32_t) * 2 * h->shard_world));
+        if (h->shard_world > 0 && (rc2 = alloc_plan_buffers(h)) != SSME_OK) return rc2;
         for (int i = 0; i < 2 && h->shard_world == 0; ++i) {   // a sharded handle works on the caller's buffers
             HIPCHK(own_alloc(h, h->x[i], sizeof(double) * np * h->dx, Mem::zeroed));          // dim_x planes of [R][Npad]
             HIPCHK(own_alloc(h, h->cdf[i], sizeof(double) * np, Mem::zeroed));
@@ -583,7 +611,7 @@ static int create_impl(const ssme_pf_config* cfg, int shard_rank, int shard_worl
         HIPCHK(own_alloc(h, h->yz_step, sizeof(double) * 2));
         HIPCHK(own_alloc(h, h->ticket, sizeof(int32_t) * h->R, Mem::zeroed));
         HIPCHK(own_alloc(h, h->l2_ticket, sizeof(int32_t) * h->R, Mem::zeroed));
-        HIPCHK(own_alloc(h, h->pin, sizeof(double) * (2 + (size_t)h->R + 64 + 8 + kMaxUserFunctionals + 1), Mem::pinned));   // + 128 ints for the shard plan + 8 swarm aggregates + 17 of the user model's functionals
+        HIPCHK(own_alloc(h, h->pin, sizeof(double) * PinLayout::size(h->R), Mem::pinned));
         HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->pin_dev), h->pin, 0));
         rc2 = upload_key(h);
         if (rc2 != SSME_OK) return rc2;
@@ -704,18 +732,25 @@ int ssme_pf_shard_plan(ssme_pf_handle h, const double* tsum_all, const double* t
     HIPCHK(hipSetDevice(h->cfg.device));
     shard_plan_device(h, t, tsum_all, tmax_all);
     HIPCHK(hipGetLastError());
-    int32_t* stage = reinterpret_cast<int32_t*>(h->pin + 2 + h->R);            // pinned
-    if (h->split_l2 && h->cfg.resampler == SSME_RESAMP_MULTINOMIAL_IID) {
-        for (int d = 0; d < h->shard_world; ++d) { stage[2 * d] = 0; stage[2 * d + 1] = h->B - 1; }      // unsorted targets need every tile
-    } else if (h->split_l2) {
-        // more than 1024 tiles in total: the split level-2 plans every tile
-        const int rc = enqueue_window_download(h, h->l2_lo, h->l2_hi, stage);
-        if (rc != SSME_OK) return rc;
-    } else {
-        HIPCHK(hipMemcpyAsync(stage, h->plan_dev, sizeof(int32_t) * 2 * h->shard_world, hipMemcpyDeviceToHost, h->stream));
-    }
-    HIPCHK(wait_stream_low_latency(h->stream));
-    for (int d = 0; d < 2 * h->shard_world; ++d) lo_hi[d] = stage[d];
+    return shard_plan_to_host(h, h->split_l2 && h->cfg.resampler == SSME_RESAMP_MULTINOMIAL_IID, h->l2_lo, h->l2_hi, lo_hi);
+}
+
+// Step t of this rank's tiles: sources in the window that starts at global tile win_tile0, outputs in the caller's buffers.
+// check_halo (the native driver's fixed-halo path): the window is the whole halo buffer, and a step that resamples verifies its
+// source tiles against it (StepArgs::win_tiles / win_flag).
+static int shard_launch_step(ssme_pf_handle h, int t, const double* x_win, const double* cdf_win, int win_tile0, const double* tsum_all,
+                             const double* tmax_all, double* x_out, double* cdf_out, double* tsum_out, double* tmax_out, uint32_t* anc_out,
+                             bool check_halo) {
+    StepArgs a = shard_args(h, t, tsum_all, tmax_all);
+    a.x_in = x_win; a.cdf_in = cdf_win; a.win_tile0 = win_tile0;
+    if (check_halo && (t % h->cfg.resamp_sched) == 0) { a.win_tiles = h->sh_rows; a.win_flag = h->sh_flag; }
+    a.x_out = x_out; a.cdf_out = cdf_out; a.tsum_out = tsum_out; a.tmax_out = tmax_out;
+    a.anc = anc_out;
+    a.finalize_prev = t > 0 ? 1 : 0;
+    a.tile0 = h->shard_rank * h->sh_Bl;
+    launch_step_on(h, a, dim3(h->sh_Bown, 1));
+    HIPCHK(hipGetLastError());
+    h->t = t + 1;
     return SSME_OK;
 }
 
@@ -730,17 +765,7 @@ int ssme_pf_shard_step(ssme_pf_handle h, int32_t t, const double* x_win, const d
     if (h->shard_world < 1 || !h->params_set) return SSME_ERR_STATE;
     if (t >= h->tcap) return SSME_ERR_STATE;            // ssme_pf_shard_prepare sizes the series
     HIPCHK(hipSetDevice(h->cfg.device));
-    StepArgs a = shard_args(h, t, tsum_all, tmax_all);
-    a.x_in = x_win; a.cdf_in = cdf_win; a.win_tile0 = win_tile0;
-    if (h->sh_check && (t % h->cfg.resamp_sched) == 0) { a.win_tiles = h->sh_rows; a.win_flag = h->sh_flag; }
-    a.x_out = x_out; a.cdf_out = cdf_out; a.tsum_out = tsum_out; a.tmax_out = tmax_out;
-    a.anc = anc_out;
-    a.finalize_prev = t > 0 ? 1 : 0;
-    a.tile0 = h->shard_rank * h->sh_Bl;
-    launch_step_on(h, a, dim3(h->sh_Bown, 1));
-    HIPCHK(hipGetLastError());
-    h->t = t + 1;
-    return SSME_OK;
+    return shard_launch_step(h, t, x_win, cdf_win, win_tile0, tsum_all, tmax_all, x_out, cdf_out, tsum_out, tmax_out, anc_out, false);
 }
 
 int ssme_pf_shard_finalize(ssme_pf_handle h, int32_t t, const double* tsum_all, const double* tmax_all) {
@@ -810,13 +835,13 @@ static int shard_alloc(ssme_pf_handle h, bool exact) {
 }
 
 // One series on one path.  fast: fixed halo exchange, no host synchronisation inside the loop; exact: planned exchange.
-static int shard_series(ssme_pf_handle h, ncclComm_t comm, const double* y, const double* z, int T, bool fast, bool* overflow) {
+static int shard_series(ssme_pf_handle h, void* nccl_comm, const double* y, const double* z, int T, bool fast, bool* overflow) {
     const int rank = h->shard_rank, Bl = h->sh_Bl, m = h->sh_margin, tile0 = rank * Bl;
     const size_t TL = kTile;
-    int rc = ssme_pf_shard_prepare(h, y, z, T);
+    ncclComm_t comm;
+    int rc = native_begin(h, nccl_comm, &comm);
+    if (rc == SSME_OK) rc = ssme_pf_shard_prepare(h, y, z, T);
     if (rc != SSME_OK) return rc;
-    HIPCHK(hipMemsetAsync(h->sh_flag, 0, sizeof(int32_t) * 4, h->stream));
-    h->sh_exchanged = 0;
     int cur = 0;
     std::vector<int32_t> lo_hi(2 * (size_t)h->shard_world);
     // tile sums and tile maxima of all ranks, each straight into its final [B] array
@@ -852,9 +877,8 @@ static int shard_series(ssme_pf_handle h, ncclComm_t comm, const double* y, cons
                 xw = h->sh_winx; cw = h->sh_winc; win0 = lo_hi[2 * rank];
             }
         }
-        h->sh_check = (fast && t > 0) ? 1 : 0;                                         // the step kernel checks its sources against the halo
-        rc = ssme_pf_shard_step(h, t, xw, cw, win0, h->sh_tsum, h->sh_tmax, xo, co, h->sh_loc, h->sh_loc + Bl, nullptr);
-        h->sh_check = 0;
+        rc = shard_launch_step(h, t, xw, cw, win0, h->sh_tsum, h->sh_tmax, xo, co, h->sh_loc, h->sh_loc + Bl, nullptr,
+                               /*check_halo=*/fast && t > 0);
         if (rc != SSME_OK) return rc;
         cur ^= 1;
     }
@@ -864,29 +888,23 @@ static int shard_series(ssme_pf_handle h, ncclComm_t comm, const double* y, cons
     if (rc != SSME_OK) return rc;
     h->cur = cur;                                                                     // sh_x[cur] holds the final particles
     *overflow = false;
-    if (fast) {           // (the exact path has no halo to leave; sh_stats keeps the record of the fixed-halo pass it may be the rerun of)
-        rc = reduce_flags(h, comm);
-        if (rc != SSME_OK) return rc;
-        *overflow = h->sh_stats[3] != 0;
-    }
-    return SSME_OK;
+    // (the exact path has no halo to leave; sh_stats keeps the record of the fixed-halo pass it may be the rerun of)
+    return fast ? reduce_flags(h, comm, overflow) : SSME_OK;
 }
 
 int ssme_pf_shard_run_series(ssme_pf_handle h, void* nccl_comm, const double* y, const double* z, int32_t T, int32_t mode, double* loglik_out) {
     if (!h || !nccl_comm || !y || mode < 0 || mode > 2) return SSME_ERR_INVALID_ARG;
     if (h->shard_world < 1 || !h->params_set) return SSME_ERR_STATE;
     if (T < 1) return SSME_ERR_LENGTH;
-    if (!rccl().ok) { h->err = "RCCL (librccl.so) not found in this process"; return SSME_ERR_UNSUPPORTED; }
     if (h->cfg.resampler == SSME_RESAMP_MULTINOMIAL_IID && mode == 1) return SSME_ERR_UNSUPPORTED;      // unsorted targets need every tile
     HIPCHK(hipSetDevice(h->cfg.device));
-    ncclComm_t comm = reinterpret_cast<ncclComm_t>(nccl_comm);
     const bool want_fast = mode != 2 && h->cfg.resampler != SSME_RESAMP_MULTINOMIAL_IID;
     int rc = shard_alloc(h, !want_fast);
     if (rc != SSME_OK) return rc;
     bool overflow = false;
     std::memset(h->sh_stats, 0, sizeof(h->sh_stats));
     h->sh_path = want_fast ? 1 : 2;
-    rc = shard_series(h, comm, y, z, T, want_fast, &overflow);
+    rc = shard_series(h, nccl_comm, y, z, T, want_fast, &overflow);
     if (rc != SSME_OK) return rc;
     if (overflow) {
         // a window left the fixed halo on SOME rank (the reduced flag: every rank reads the same value and takes the same branch):
@@ -895,7 +913,7 @@ int ssme_pf_shard_run_series(ssme_pf_handle h, void* nccl_comm, const double* y,
         rc = shard_alloc(h, true);
         if (rc != SSME_OK) return rc;
         h->sh_path = 2;
-        rc = shard_series(h, comm, y, z, T, false, &overflow);
+        rc = shard_series(h, nccl_comm, y, z, T, false, &overflow);
         if (rc != SSME_OK) return rc;
     }
     if (loglik_out) return ssme_pf_get_loglik(h, loglik_out);
@@ -1015,21 +1033,23 @@ int ssme_pf_step(ssme_pf_handle h, const double* y, const double* z, double* out
     // y and z travel in the kernel arguments; the R results come back through device-mapped pinned memory, written by the
     // last workgroup of the step kernel itself: a filter() call is one launch and a poll (two launches with the split
     // level-2 of very large filters), no copy operation in either direction
-    h->pin[0] = *y; h->pin[1] = z ? *z : 0.0;
+    double* const yz = h->pin + PinLayout::yz;
+    yz[0] = *y; yz[1] = z ? *z : 0.0;
     for (int d = 1; d < h->dy; ++d) h->y_step_v[d - 1] = y[d];
-    if (h->cfg.dtype == SSME_F32) { h->pin[0] = f32r(h->pin[0]); h->pin[1] = f32r(h->pin[1]); }
-    h->last_z = h->pin[1];
+    if (h->cfg.dtype == SSME_F32) { yz[0] = f32r(yz[0]); yz[1] = f32r(yz[1]); }
+    h->last_z = yz[1];
     const int gi = h->cfg.resampler == SSME_RESAMP_MULTINOMIAL ? step_gamma_row(h, launch_gamma) : 0;
     // out == NULL (the swarm classes: the aggregation that follows hands the data back): the step is only queued -- no result
     // slots, no wait; anything that reads the handle afterwards is ordered behind it on the stream
     const bool want = out != nullptr;
-    if (want) mark_results_pending(h->pin + 2, h->R);
+    double* const res = h->pin + PinLayout::results;
+    if (want) mark_results_pending(res, h->R);
     enqueue_step(h, h->t, 0, gi, z != nullptr, /*finalize_prev=*/false, /*per_step=*/false, /*from_step_staging=*/true, want);
-    if (h->split_l2) launch_kf(h, h->t, false, want ? h->pin_dev + 2 : nullptr);
+    if (h->split_l2) launch_kf(h, h->t, false, want ? h->pin_dev + PinLayout::results : nullptr);
     HIPCHK(hipGetLastError());
     h->t += 1;
-    if (want) HIPCHK(wait_results(h->stream, h->pin + 2, h->R));
-    if (out) for (int r = 0; r < h->R; ++r) out[r] = h->pin[2 + r];
+    if (want) HIPCHK(wait_results(h->stream, res, h->R));
+    if (out) for (int r = 0; r < h->R; ++r) out[r] = res[r];
     round_out(h, out, h->R);
     return SSME_OK;
 }
@@ -1181,11 +1201,12 @@ int ssme_pf_swarm_aggregate_threads(ssme_pf_handle h, const int32_t* functionals
         if (rc != SSME_OK) return rc;
     }
     // one launch writes the n + 1 means straight into mapped host memory, where the host waits for them (see wait_results)
-    double* pin = h->pin + 2 + h->R + 64;
+    const size_t slot0 = PinLayout::swarm(h->R);
+    double* pin = h->pin + slot0;
     mark_results_pending(pin, n);
     mark_results_pending(pin + kMaxFunctionals, 1);
     hipLaunchKernelGGL(k_swarm_means, dim3(n + 1), dim3(kThreads), 0, h->stream, (const double*)h->exp_out, (const FilterScalars*)h->scal,
-                       h->R, n, kMaxFunctionals, h->pin_dev + 2 + h->R + 64, (int)num_threads);
+                       h->R, n, kMaxFunctionals, h->pin_dev + slot0, (int)num_threads);
     HIPCHK(hipGetLastError());
     HIPCHK(wait_results(h->stream, pin + kMaxFunctionals, 1));
     if (n > 0) HIPCHK(wait_results(h->stream, pin, n));
@@ -1215,7 +1236,7 @@ int ssme_pf_swarm_aggregate_user(ssme_pf_handle h, int32_t num_threads, double* 
     const int rc = user_expectations_checked(h);
     if (rc != SSME_OK) return rc;
     const int n = ssme_pf_user_model_n_h();
-    const size_t slot0 = 2 + (size_t)h->R + 64 + 8;
+    const size_t slot0 = PinLayout::user(h->R);
     double* pin = h->pin + slot0;
     mark_results_pending(pin, kMaxUserFunctionals + 1);
     hipLaunchKernelGGL(k_swarm_means, dim3(n + 1), dim3(kThreads), 0, h->stream, (const double*)h->uexp_out, (const FilterScalars*)h->scal,
@@ -1593,8 +1614,6 @@ struct ssme_lw_s : HandleCore {
     uint32_t *anc, *kidx;
     uint32_t* ancbuf;        // unsharded handles: this step's resampling ancestors, stage 1 -> stage 2 (compose mode, lw_kernels.h)
     int fixed_trans;                 // the transform set is (logit, null, log, twice_fisher): stage kernels with it compiled in (lw_trans_kind)
-    int th_plane_tiles;              // sharded: rows (tiles) per theta plane of the caller's OUTPUT buffers (default Bl)
-    int32_t* plan_pin;               // pinned staging of the plan download
     // C++ shard driver (ssme_lw_shard_run_series): halo buffers ([margin | own | margin] rows of 2048 doubles; theta rows of 8192),
     // this rank's stage outputs for the gathers, the gathered arrays
     double *sh_xB, *sh_thB, *sh_cdfB, *sh_xr, *sh_thr, *sh_g1, *sh_cdfA;
@@ -1797,9 +1816,7 @@ static int lw_create_impl(const ssme_lw_config* cfg, int shard_rank, int shard_w
             for (double** p : {&h->tsumA, &h->tmaxA, &h->tsumB, &h->tmaxB}) HIPCHK(own_alloc(h, *p, sizeof(double) * nb, Mem::zeroed));
             HIPCHK(own_alloc(h, h->ancbuf, sizeof(uint32_t) * np, Mem::zeroed));
         } else {
-            HIPCHK(own_alloc(h, h->plan_dev, sizeof(int32_t) * 2 * h->shard_world));
-            HIPCHK(own_alloc(h, h->plan_pin, sizeof(int32_t) * 2 * h->shard_world, Mem::pinned));
-            h->th_plane_tiles = h->sh_Bl;
+            if ((rc2 = alloc_plan_buffers(h)) != SSME_OK) return rc2;
             if (h->rs > 1)                       // the carried second-stage log-weights of this rank's own particles (local offsets)
                 HIPCHK(own_alloc(h, h->lwB, sizeof(double) * (size_t)h->sh_Bl * kTile, Mem::zeroed));
         }
@@ -1840,14 +1857,6 @@ int ssme_lw_shard_layout(ssme_lw_handle h, int32_t* out4) { return shard_layout(
 
 int ssme_lw_set_stream(ssme_lw_handle h, void* hip_stream) { return set_stream(h, hip_stream); }
 
-int ssme_lw_shard_set_plane_tiles(ssme_lw_handle h, int32_t tiles) {
-    if (!h || tiles < 1) return SSME_ERR_INVALID_ARG;
-    if (h->shard_world < 1) return SSME_ERR_STATE;
-    if (tiles < h->sh_Bl) return SSME_ERR_INVALID_ARG;
-    h->th_plane_tiles = tiles;
-    return SSME_OK;
-}
-
 int ssme_lw_shard_prepare(ssme_lw_handle h, const double* y, const double* z, int32_t T) {
     if (!h || !y) return SSME_ERR_INVALID_ARG;
     if (h->shard_world < 1) return SSME_ERR_STATE;
@@ -1865,14 +1874,15 @@ int ssme_lw_shard_prepare(ssme_lw_handle h, const double* y, const double* z, in
     return SSME_OK;
 }
 
-static LwArgs lw_shard_args(ssme_lw_handle h, int t) {
+// check_halo (the native driver's stages on the fixed halo): the source windows are whole halo buffers, and the stage kernel
+// verifies its source tiles against them (LwArgs::win_tiles / win_flag)
+static LwArgs lw_shard_args(ssme_lw_handle h, int t, bool check_halo = false) {
     LwArgs a = lw_args(h);
-    const int Bl = h->sh_Bl;
-    a.t = t; a.yi = t; a.gi = t; a.finalize_prev = t > 1 || t == 1 ? 1 : 0;
+    a.t = t; a.yi = t; a.gi = t; a.finalize_prev = t >= 1 ? 1 : 0;
     a.per_step = h->per_step;
-    a.tile0 = h->shard_rank * Bl;
+    a.tile0 = h->shard_rank * h->sh_Bl;
     a.anc = nullptr; a.kidx = nullptr;
-    if (h->sh_check) { a.win_tiles = h->sh_rows; a.win_flag = h->sh_flag; }
+    if (check_halo) { a.win_tiles = h->sh_rows; a.win_flag = h->sh_flag; }
     return a;
 }
 
@@ -1893,22 +1903,31 @@ int ssme_lw_shard_plan(ssme_lw_handle h, int32_t which, int32_t t, const double*
     if (!h || !tsum_all || !tmax_all || !lo_hi || t < 1 || which < 0 || which > 1) return SSME_ERR_INVALID_ARG;
     if (h->shard_world < 1) return SSME_ERR_STATE;
     HIPCHK(hipSetDevice(h->cfg.device));
-    if (h->split_l2) {
+    if (h->split_l2)
         lw_launch_plan(h, which, t, t, tsum_all, tmax_all, true);
-        HIPCHK(hipGetLastError());
-        const int rc = enqueue_window_download(h, h->l2lo[which], h->l2hi[which], h->plan_pin);
-        if (rc != SSME_OK) return rc;
-    } else {
+    else
         hipLaunchKernelGGL(k_shard_plan, dim3(1), dim3(512), sizeof(double) * (h->Bpow2 < 2 ? 2 : h->Bpow2), h->stream,
                            lw_plan_args(h, which, t, t, tsum_all, tmax_all), h->shard_world, h->sh_Bl, h->plan_dev);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(h->plan_pin, h->plan_dev, sizeof(int32_t) * 2 * h->shard_world, hipMemcpyDeviceToHost, h->stream));
-    }
-    HIPCHK(wait_stream_low_latency(h->stream));
-    for (int d = 0; d < 2 * h->shard_world; ++d) lo_hi[d] = h->plan_pin[d];
+    HIPCHK(hipGetLastError());
+    return shard_plan_to_host(h, false, h->l2lo[which], h->l2hi[which], lo_hi);
+}
+
+// Stage 1 of step t on this rank's tiles: sources in the windows that start at global tile win_tile0, outputs in the caller's buffers
+static int lw_shard_launch_stage1(ssme_lw_handle h, int t, int win_tile0, const double* w_xB, const double* w_thB, const double* w_cdfB,
+                                  const double* tsumB_all, const double* tmaxB_all, double* xr, double* thr, double* lw1, double* cdfA,
+                                  double* tsumA, double* tmaxA, double* mom, uint32_t* anc, bool check_halo) {
+    LwArgs a = lw_shard_args(h, t, check_halo);
+    a.xB = const_cast<double*>(w_xB); a.thB = const_cast<double*>(w_thB); a.cdfB = const_cast<double*>(w_cdfB);
+    a.tsumB = const_cast<double*>(tsumB_all); a.tmaxB = const_cast<double*>(tmaxB_all);
+    a.win_tile0 = win_tile0;
+    a.xr = xr; a.thr = thr; a.lw1 = lw1; a.cdfA = cdfA; a.tsumA = tsumA; a.tmaxA = tmaxA; a.mom = mom;
+    a.anc = anc;
+    lw_launch_stage(h, 1, dim3(h->sh_Bown, 1), a);
+    HIPCHK(hipGetLastError());
     return SSME_OK;
 }
 
+// (win_tiles of the two stage calls is validated and not read: the window's first tile is all a stage kernel needs)
 int ssme_lw_shard_stage1(ssme_lw_handle h, int32_t t, int32_t win_tile0, int32_t win_tiles, const double* w_xB, const double* w_thB,
                          const double* w_cdfB, const double* tsumB_all, const double* tmaxB_all, double* xr, double* thr, double* lw1,
                          double* cdfA, double* tsumA, double* tmaxA, double* mom, uint32_t* anc) {
@@ -1918,15 +1937,7 @@ int ssme_lw_shard_stage1(ssme_lw_handle h, int32_t t, int32_t win_tile0, int32_t
     if (h->shard_world < 1) return SSME_ERR_STATE;
     if (t >= h->tcap) return SSME_ERR_STATE;
     HIPCHK(hipSetDevice(h->cfg.device));
-    LwArgs a = lw_shard_args(h, t);
-    a.xB = const_cast<double*>(w_xB); a.thB = const_cast<double*>(w_thB); a.cdfB = const_cast<double*>(w_cdfB);
-    a.tsumB = const_cast<double*>(tsumB_all); a.tmaxB = const_cast<double*>(tmaxB_all);
-    a.win_tile0 = win_tile0; (void)win_tiles;
-    a.xr = xr; a.thr = thr; a.lw1 = lw1; a.cdfA = cdfA; a.tsumA = tsumA; a.tmaxA = tmaxA; a.mom = mom;
-    a.anc = anc;
-    lw_launch_stage(h, 1, dim3(h->sh_Bown, 1), a);
-    HIPCHK(hipGetLastError());
-    return SSME_OK;
+    return lw_shard_launch_stage1(h, t, win_tile0, w_xB, w_thB, w_cdfB, tsumB_all, tmaxB_all, xr, thr, lw1, cdfA, tsumA, tmaxA, mom, anc, false);
 }
 
 int ssme_lw_shard_mid(ssme_lw_handle h, int32_t t, const double* tsumA_all, const double* tmaxA_all, const double* mom_all) {
@@ -1941,6 +1952,22 @@ int ssme_lw_shard_mid(ssme_lw_handle h, int32_t t, const double* tsumA_all, cons
     return SSME_OK;
 }
 
+// Stage 2 of step t, likewise
+static int lw_shard_launch_stage2(ssme_lw_handle h, int t, int win_tile0, const double* w_xr, const double* w_thr, const double* w_lw1,
+                                  const double* w_cdfA, const double* tsumA_all, const double* tmaxA_all, double* xB, double* thB,
+                                  double* cdfB, double* tsumB, double* tmaxB, uint32_t* kidx, bool check_halo) {
+    LwArgs a = lw_shard_args(h, t, check_halo);
+    a.xr = const_cast<double*>(w_xr); a.thr = const_cast<double*>(w_thr); a.lw1 = const_cast<double*>(w_lw1);
+    a.cdfA = const_cast<double*>(w_cdfA); a.tsumA = const_cast<double*>(tsumA_all); a.tmaxA = const_cast<double*>(tmaxA_all);
+    a.win_tile0 = win_tile0;
+    a.xB = xB; a.thB = thB; a.cdfB = cdfB; a.tsumB = tsumB; a.tmaxB = tmaxB;
+    a.kidx = kidx;
+    lw_launch_stage(h, 2, dim3(h->sh_Bown, 1), a);
+    HIPCHK(hipGetLastError());
+    h->t = t + 1;
+    return SSME_OK;
+}
+
 int ssme_lw_shard_stage2(ssme_lw_handle h, int32_t t, int32_t win_tile0, int32_t win_tiles, const double* w_xr, const double* w_thr,
                          const double* w_lw1, const double* w_cdfA, const double* tsumA_all, const double* tmaxA_all, double* xB,
                          double* thB, double* cdfB, double* tsumB, double* tmaxB, uint32_t* kidx) {
@@ -1949,16 +1976,7 @@ int ssme_lw_shard_stage2(ssme_lw_handle h, int32_t t, int32_t win_tile0, int32_t
         return SSME_ERR_INVALID_ARG;
     if (h->shard_world < 1) return SSME_ERR_STATE;
     HIPCHK(hipSetDevice(h->cfg.device));
-    LwArgs a = lw_shard_args(h, t);
-    a.xr = const_cast<double*>(w_xr); a.thr = const_cast<double*>(w_thr); a.lw1 = const_cast<double*>(w_lw1);
-    a.cdfA = const_cast<double*>(w_cdfA); a.tsumA = const_cast<double*>(tsumA_all); a.tmaxA = const_cast<double*>(tmaxA_all);
-    a.win_tile0 = win_tile0; (void)win_tiles;
-    a.xB = xB; a.thB = thB; a.cdfB = cdfB; a.tsumB = tsumB; a.tmaxB = tmaxB;
-    a.kidx = kidx;
-    lw_launch_stage(h, 2, dim3(h->sh_Bown, 1), a);
-    HIPCHK(hipGetLastError());
-    h->t = t + 1;
-    return SSME_OK;
+    return lw_shard_launch_stage2(h, t, win_tile0, w_xr, w_thr, w_lw1, w_cdfA, tsumA_all, tmaxA_all, xB, thB, cdfB, tsumB, tmaxB, kidx, false);
 }
 
 int ssme_lw_shard_finalize(ssme_lw_handle h, int32_t t, const double* tsumB_all, const double* tmaxB_all) {
@@ -2003,19 +2021,15 @@ int ssme_lw_shard_run_series(ssme_lw_handle h, void* nccl_comm, const double* y,
     if (!h || !nccl_comm || !y) return SSME_ERR_INVALID_ARG;
     if (h->shard_world < 1) return SSME_ERR_STATE;
     if (T < 1) return SSME_ERR_LENGTH;
-    if (!rccl().ok) { h->err = "RCCL (librccl.so) not found in this process"; return SSME_ERR_UNSUPPORTED; }
     HIPCHK(hipSetDevice(h->cfg.device));
-    ncclComm_t comm = reinterpret_cast<ncclComm_t>(nccl_comm);
+    ncclComm_t comm;
     int rc = lw_shard_alloc(h);
+    if (rc == SSME_OK) rc = native_begin(h, nccl_comm, &comm);
     if (rc != SSME_OK) return rc;
     const int Bl = h->sh_Bl, m = h->sh_margin, tile0 = h->shard_rank * Bl;
     const size_t TL = kTile, off = (size_t)m * TL;
-    rc = ssme_lw_shard_set_plane_tiles(h, h->sh_rows);
-    if (rc != SSME_OK) return rc;
     rc = ssme_lw_shard_prepare(h, y, z, T);
     if (rc != SSME_OK) return rc;
-    HIPCHK(hipMemsetAsync(h->sh_flag, 0, sizeof(int32_t) * 4, h->stream));
-    h->sh_exchanged = 0;
     double *tsB = h->sh_locB, *tmB = h->sh_locB + Bl;
     double *tsA = h->sh_locA, *tmA = h->sh_locA + Bl, *momL = h->sh_locA + 2 * Bl;
     auto gatherB = [&] { return all_gather(h, comm, {{tsB, h->sh_allB_s, (size_t)Bl}, {tmB, h->sh_allB_m, (size_t)Bl}}); };
@@ -2031,14 +2045,11 @@ int ssme_lw_shard_run_series(ssme_lw_handle h, void* nccl_comm, const double* y,
         if (resampled) {
             rc = halo_exchange(h, comm, {{h->sh_xB, TL}, {h->sh_thB, TL * kDP}, {h->sh_cdfB, TL}});
             if (rc != SSME_OK) return rc;
-            h->sh_check = 1;
-            rc = ssme_lw_shard_stage1(h, t, tile0 - m, h->sh_rows, h->sh_xB, h->sh_thB, h->sh_cdfB, h->sh_allB_s, h->sh_allB_m,
-                                      h->sh_xr + off, h->sh_thr + off * kDP, h->sh_g1 + off, h->sh_cdfA + off, tsA, tmA, momL, nullptr);
-            h->sh_check = 0;
-        } else {
-            rc = ssme_lw_shard_stage1(h, t, tile0, Bl, h->sh_xB + off, h->sh_thB + off * kDP, h->sh_cdfB + off, h->sh_allB_s, h->sh_allB_m,
-                                      h->sh_xr + off, h->sh_thr + off * kDP, h->sh_g1 + off, h->sh_cdfA + off, tsA, tmA, momL, nullptr);
         }
+        const size_t src = resampled ? 0 : off;                   // the whole halo buffers, or this rank's own rows
+        rc = lw_shard_launch_stage1(h, t, resampled ? tile0 - m : tile0, h->sh_xB + src, h->sh_thB + src * kDP, h->sh_cdfB + src, h->sh_allB_s,
+                                    h->sh_allB_m, h->sh_xr + off, h->sh_thr + off * kDP, h->sh_g1 + off, h->sh_cdfA + off, tsA, tmA, momL, nullptr,
+                                    /*check_halo=*/resampled);
         if (rc != SSME_OK) return rc;
         rc = all_gather(h, comm, {{tsA, h->sh_allA_s, (size_t)Bl}, {tmA, h->sh_allA_m, (size_t)Bl}, {momL, h->sh_mom_all, (size_t)Bl * 16}});
         if (rc != SSME_OK) return rc;
@@ -2052,19 +2063,18 @@ int ssme_lw_shard_run_series(ssme_lw_handle h, void* nccl_comm, const double* y,
             rc = halo_exchange(h, comm, {{h->sh_xr, TL}, {h->sh_thr, TL * kDP}, {h->sh_g1, TL}, {h->sh_cdfA, TL}});
             if (rc != SSME_OK) return rc;
         }
-        h->sh_check = 1;
-        rc = ssme_lw_shard_stage2(h, t, tile0 - m, h->sh_rows, h->sh_xr, h->sh_thr, h->sh_g1, h->sh_cdfA, h->sh_allA_s, h->sh_allA_m,
-                                  h->sh_xB + off, h->sh_thB + off * kDP, h->sh_cdfB + off, tsB, tmB, nullptr);
-        h->sh_check = 0;
+        rc = lw_shard_launch_stage2(h, t, tile0 - m, h->sh_xr, h->sh_thr, h->sh_g1, h->sh_cdfA, h->sh_allA_s, h->sh_allA_m,
+                                    h->sh_xB + off, h->sh_thB + off * kDP, h->sh_cdfB + off, tsB, tmB, nullptr, /*check_halo=*/true);
         if (rc != SSME_OK) return rc;
     }
     rc = gatherB();
     if (rc != SSME_OK) return rc;
     rc = ssme_lw_shard_finalize(h, T - 1, h->sh_allB_s, h->sh_allB_m);           // synchronises
     if (rc != SSME_OK) return rc;
-    rc = reduce_flags(h, comm);
+    bool overflow = false;
+    rc = reduce_flags(h, comm, &overflow);
     if (rc != SSME_OK) return rc;
-    if (h->sh_stats[3]) { h->err = "a resampling window left the fixed halo on some rank: run the exact host-planned loop"; return SSME_ERR_STATE; }
+    if (overflow) { h->err = "a resampling window left the fixed halo on some rank: run the exact host-planned loop"; return SSME_ERR_STATE; }
     if (loglik_out) return ssme_lw_get_loglik(h, loglik_out);
     return SSME_OK;
 }

@@ -77,6 +77,16 @@ static const RcclApi& rccl() {
 
 // ---- the transport of both drivers: collectives and copies on the handle's stream ---------------------------------------
 
+// what a native series starts with (the driver has allocated its buffers): RCCL present, the caller's communicator, the flags and
+// the count of received tiles cleared
+static int native_begin(HandleCore* h, void* nccl_comm, ncclComm_t* comm) {
+    if (!rccl().ok) { h->err = "RCCL (librccl.so) not found in this process"; return SSME_ERR_UNSUPPORTED; }
+    *comm = reinterpret_cast<ncclComm_t>(nccl_comm);
+    HIPCHK(hipMemsetAsync(h->sh_flag, 0, sizeof(int32_t) * 4, h->stream));
+    h->sh_exchanged = 0;
+    return SSME_OK;
+}
+
 // halo margin in tiles: a rank's resampling window normally reaches a tile or two into its neighbours (the cumulative tile
 // weights wander like sqrt(tiles) around the uniform split); 4 tiles or 1/64 of the share, never more than the share
 static int halo_margin(int Bl, int world) {
@@ -155,11 +165,12 @@ static int planned_exchange(HandleCore* h, ncclComm_t comm, const int32_t* lo_hi
 }
 
 // end of a fixed-halo series: the fallback decision must be the SAME on every rank, so every rank's flag [0] is reduced (max)
-// into [3] before anyone reads it; then sh_stats = the flags.  One int, once per series; synchronises.
-static int reduce_flags(HandleCore* h, ncclComm_t comm) {
+// into [3] before anyone reads it; then sh_stats = the flags and *overflow = the reduced one.  One int, once per series; synchronises.
+static int reduce_flags(HandleCore* h, ncclComm_t comm, bool* overflow) {
     NCCLCHK(rccl().AllReduce(h->sh_flag, h->sh_flag + 3, 1, ncclInt32, ncclMax, comm, h->stream));
     HIPCHK(hipMemcpyAsync(h->sh_stats, h->sh_flag, sizeof(h->sh_stats), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
+    *overflow = h->sh_stats[3] != 0;
     return SSME_OK;
 }
 

@@ -20,6 +20,9 @@ RNG counters use global particle indices and the Gamma tables global tile ids, s
 The reference has no distributed filter; the single-process semantics reproduced are BSFilter::filter's
 (example/estimate_univ_svol.h:121-127).  Collectives go through torch.distributed: backend "nccl" (= RCCL over xGMI)
 exchanges device tensors; backend "gloo" (CPU rehearsal, several ranks on one GPU) stages them through host memory.
+
+Both filter classes drive their steps through `_ShardedFilter`: `_gather` (one collective per gather), `_plan` (every rank's window)
+and `_windows` (halo exchange in place, or -- a window wider than the margins -- the assembled window; `window_routes` records which).
 """
 import ctypes as C
 
@@ -71,35 +74,43 @@ def exchange_plan(lo_hi, tiles_per_rank, rank):
     return sends, recvs
 
 
+def _post(recvs, sends, group, stage_through_host):
+    """One grouped exchange.  recvs: [(tensor to fill, rank it comes from)], sends: [(tensor, rank it goes to)], ranks of `group`
+    (translated here to the global ranks that P2POp takes).  stage_through_host (gloo): host copies travel, and what was received is
+    copied into its tensor after the wait."""
+    import torch
+    import torch.distributed as dist
+    peer = (lambda r: r) if group is None else (lambda r: dist.get_global_rank(group, r))
+    ops, staged = [], []
+    for dst, s in recvs:
+        buf = torch.empty_like(dst, device="cpu") if stage_through_host else dst
+        if stage_through_host:
+            staged.append((dst, buf))
+        ops.append(dist.P2POp(dist.irecv, buf, peer(s), group))
+    for src, d in sends:
+        ops.append(dist.P2POp(dist.isend, src.cpu() if stage_through_host else src.contiguous(), peer(d), group))
+    if ops:
+        for req in dist.batch_isend_irecv(ops):
+            req.wait()
+    for dst, buf in staged:
+        dst.copy_(buf)
+
+
 def exchange_tiles(local, my_first_tile, sends, recvs, rank, group=None, stage_through_host=False):
     """Grouped point-to-point exchange of whole tiles.  local: [tiles_per_rank, W] tensor (this rank's tiles);
     returns the window [sum(recv counts), W] in global tile order.  Works for any backend with send/recv."""
     import torch
-    import torch.distributed as dist
-    world = len(sends)
-    total = sum(c for _, c in recvs)
-    comm_dev = torch.device("cpu") if stage_through_host else local.device
-    window = torch.empty((total, local.shape[1]), dtype=local.dtype, device=comm_dev)
-    src = local.to(comm_dev) if stage_through_host else local
-    ops, off = [], 0
-    for s in range(world):
-        first, cnt = recvs[s]
-        if cnt:
-            piece = window[off:off + cnt]
-            if s == rank:
-                piece.copy_(src[first - my_first_tile:first - my_first_tile + cnt])
-            else:
-                ops.append(dist.P2POp(dist.irecv, piece, s if group is None else dist.get_global_rank(group, s), group))
-            off += cnt
-    for d in range(world):
-        first, cnt = sends[d]
-        if cnt and d != rank:
-            piece = src[first - my_first_tile:first - my_first_tile + cnt].contiguous()
-            ops.append(dist.P2POp(dist.isend, piece, d if group is None else dist.get_global_rank(group, d), group))
-    if ops:
-        for req in dist.batch_isend_irecv(ops):
-            req.wait()
-    return window.to(local.device) if stage_through_host else window
+    rows = lambda first, cnt: local[first - my_first_tile:first - my_first_tile + cnt]
+    window = torch.empty((sum(c for _, c in recvs), local.shape[1]), dtype=local.dtype, device=local.device)
+    get, off = [], 0
+    for s, (first, cnt) in enumerate(recvs):
+        if cnt and s == rank:
+            window[off:off + cnt].copy_(rows(first, cnt))
+        elif cnt:
+            get.append((window[off:off + cnt], s))
+        off += cnt
+    _post(get, [(rows(first, cnt), d) for d, (first, cnt) in enumerate(sends) if cnt and d != rank], group, stage_through_host)
+    return window
 
 
 def gather_flat(local_flat, world, group=None, stage_through_host=False):
@@ -161,7 +172,6 @@ def exchange_halos(bufs, tile0, plan, tiles_per_rank, rank, group=None, stage_th
     """One grouped exchange for several HaloBuffers that share a plan: every piece another rank owns is received straight
     into the margin rows, every piece another rank needs is sent from the own rows.  Returns (win_tile0, win_tiles) or
     None if the window does not fit the margins."""
-    import torch.distributed as dist
     lo, hi = plan[rank]
     # The decision is GLOBAL: every rank holds the whole plan and evaluates every rank's window against the (identical)
     # margins, so that all ranks take the same path and post the same grouping of sends/receives (a mixed grouping is
@@ -169,33 +179,15 @@ def exchange_halos(bufs, tile0, plan, tiles_per_rank, rank, group=None, stage_th
     if not all(b.fits(plan[g][0], plan[g][1], g * tiles_per_rank) for g in range(len(plan)) for b in bufs):
         return None
     sends, recvs = exchange_plan(plan, tiles_per_rank, rank)
-    peer = (lambda r: r) if group is None else (lambda r: dist.get_global_rank(group, r))
-    ops, staged = [], []
-    for b in bufs:
-        for s, (first, cnt) in enumerate(recvs):
-            if cnt and s != rank:
-                dst = b.rows(first, cnt, tile0)
-                if stage_through_host:
-                    tmp = dst.cpu()
-                    staged.append((dst, tmp))
-                    ops.append(dist.P2POp(dist.irecv, tmp, peer(s), group))
-                else:
-                    ops.append(dist.P2POp(dist.irecv, dst, peer(s), group))
-        for d, (first, cnt) in enumerate(sends):
-            if cnt and d != rank:
-                src = b.rows(first, cnt, tile0)
-                ops.append(dist.P2POp(dist.isend, src.cpu() if stage_through_host else src, peer(d), group))
-    if ops:
-        for req in dist.batch_isend_irecv(ops):
-            req.wait()
-    for dst, tmp in staged:
-        dst.copy_(tmp)
+    pieces = lambda ranges: [(b.rows(first, cnt, tile0), r) for b in bufs for r, (first, cnt) in enumerate(ranges) if cnt and r != rank]
+    _post(pieces(recvs), pieces(sends), group, stage_through_host)
     return lo, hi - lo + 1
 
 
 class _ShardedFilter:
     """What the sharded bootstrap and Liu-West filters share: the process group and this rank's layout, the handle's side
-    stream, its life cycle, the native communicator and the statistics.  _api: the C ABI's prefix of the handle type."""
+    stream, its life cycle, the native communicator, the statistics, and the pieces of the host-planned series loop: the stream
+    hand-over (run_series), the gathers, the plan and the source windows of a draw.  _api: the C ABI's prefix of the handle type."""
 
     _api = "ssme_pf"
 
@@ -210,7 +202,10 @@ class _ShardedFilter:
         self.n, self.B, self.Bl, self.Bown, self.n_local = shard_layout(n_particles, self.rank, self.world)
         self.tile0 = self.rank * self.Bl
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        # halo rows on each side of the own tiles (the rule of the host-planned loops; the C++ drivers have halo_margin)
+        self.margin = min(self.B - self.Bl, max(2, self.Bl // 2)) if self.world > 1 else 0
         self.exchanged_tiles = 0                                # tiles received from other ranks (statistics)
+        self.window_routes = []                                 # per draw that exchanged: (t, [which,] "in_place" | "assembled")
         self._T = 0
         self._h = C.c_void_p()
         self._comm = None
@@ -252,6 +247,46 @@ class _ShardedFilter:
             self._comm = make_native_comm(self.rank, self.world, self.device.index or 0, self.group)
         return self._comm
 
+    def run_series(self, y, z=None):
+        """log p(y_{1:T}) of the sharded filter through the host-planned loop; identical on every rank."""
+        import torch
+        self.exchanged_tiles, self.window_routes = 0, []
+        self._stream.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(self._stream):
+            return self._run_series(capi.as_f64(y), None if z is None else capi.as_f64(z))
+
+    def _gather(self, local_flat, dests):
+        """ONE collective: every rank's local_flat, its columns scattered into dests = [(array of world x Bl entries, columns per
+        rank), ...] in the order they lie in local_flat (rank g's land at g * columns)."""
+        G = gather_flat(local_flat, self.world, self.group, self.stage)
+        off = 0
+        for dest, cols in dests:
+            dest.view(self.world, cols).copy_(G[:, off:off + cols])
+            off += cols
+
+    def _plan(self, *args):
+        """ssme_*_shard_plan(handle, *args, lo_hi): every rank's inclusive source-tile window [(lo, hi)].  Synchronises."""
+        lo_hi = (C.c_int32 * (2 * self.world))()
+        self._chk(self._fn("shard_plan")(self._h, *args, lo_hi))
+        return [(lo_hi[2 * g], lo_hi[2 * g + 1]) for g in range(self.world)]
+
+    def _windows(self, plan, halos, draw):
+        """The exchange of one draw (`draw`: what window_routes calls it).  Returns (first tile of this rank's window, [source window
+        per HaloBuffer]).  If every rank's window fits the margins (exchange_halos decides it for all ranks alike) own tiles stay
+        where they are and only halo tiles travel; otherwise every window is assembled afresh.  The caller holds the returned windows
+        until it has queued the launch that reads them, and that is enough: they are allocated on the side stream, where that launch
+        runs too, and torch's allocator gives a freed block only to later work of the stream it was allocated on."""
+        lo, hi = plan[self.rank]
+        if exchange_halos(halos, self.tile0, plan, self.Bl, self.rank, self.group, self.stage) is not None:
+            route, wins = "in_place", [hb.rows(lo, hi - lo + 1, self.tile0) for hb in halos]
+        else:
+            sends, recvs = exchange_plan(plan, self.Bl, self.rank)
+            route = "assembled"
+            wins = [exchange_tiles(hb.own(), self.tile0, sends, recvs, self.rank, self.group, self.stage) for hb in halos]
+        self.window_routes.append(draw + (route,))
+        self._count_exchanged(lo, hi)
+        return lo, wins
+
     def per_step(self):
         out = np.empty((1, self._T))
         self._chk(self._fn("get_per_step")(self._h, capi.dptr(out), self._T))
@@ -272,9 +307,8 @@ class ShardedParticleFilter(_ShardedFilter):
         self._use_side_stream()
         f64 = dict(dtype=torch.float64, device=self.device)
         # particles and tile-local integer cdf (integers < 2^53 in fp64) after the last step: ping-pong halo buffers
-        margin = min(self.B - self.Bl, max(2, self.Bl // 2)) if self.world > 1 else 0
-        self._hx = [HaloBuffer(self.Bl, TILE, margin, self.device, torch.float64) for _ in range(2)]
-        self._hc = [HaloBuffer(self.Bl, TILE, margin, self.device, torch.float64) for _ in range(2)]
+        self._hx = [HaloBuffer(self.Bl, TILE, self.margin, self.device, torch.float64) for _ in range(2)]
+        self._hc = [HaloBuffer(self.Bl, TILE, self.margin, self.device, torch.float64) for _ in range(2)]
         self._cur = 0
         self.tiles_loc = torch.zeros((2, self.Bl), **f64)       # row 0: tile sums, row 1: tile maxima
         self.tiles_all = torch.zeros((2, self.world * self.Bl), **f64)      # gathered: world x Bl entries, the first B are tiles
@@ -289,31 +323,13 @@ class ShardedParticleFilter(_ShardedFilter):
         import torch
         self.anc = torch.zeros((self.Bl, TILE), dtype=torch.int32, device=self.device) if on else None
 
-    # ---- collectives --------------------------------------------------------------------------------------------
-    def _gather_tiles(self):
-        """tiles_all[:, g*Bl:(g+1)*Bl] = rank g's tiles_loc."""
-        G = gather_flat(self.tiles_loc.reshape(-1), self.world, self.group, self.stage)          # [world, 2 * Bl]
-        self.tiles_all[0].view(self.world, self.Bl).copy_(G[:, :self.Bl])
-        self.tiles_all[1].view(self.world, self.Bl).copy_(G[:, self.Bl:])
-
     # ---- the series loop ------------------------------------------------------------------------------------------
-    def run_series(self, y, z=None):
-        """log p(y_{1:T}) of the sharded filter; identical on every rank."""
-        import torch
-        self._stream.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(self._stream):
-            return self._run_series(y, z)
-
-    def _run_series(self, y, z):
-        import torch
-        yv = capi.as_f64(y)
-        zv = None if z is None else capi.as_f64(z)
+    def _run_series(self, yv, zv):
         T = yv.size
         L = capi.lib()
         self._chk(L.ssme_pf_shard_prepare(self._h, capi.dptr(yv), capi.dptr(zv), T))
         ts, tm = self.tiles_all[0], self.tiles_all[1]
-        lo_hi = (C.c_int32 * (2 * self.world))()
-        self.exchanged_tiles = 0
+        gather = lambda: self._gather(self.tiles_loc.reshape(-1), [(ts, self.Bl), (tm, self.Bl)])
         for t in range(T):
             hx, hc = self._hx[self._cur], self._hc[self._cur]            # sources: the last step's outputs (+ halos)
             ox, oc = self._hx[self._cur ^ 1], self._hc[self._cur ^ 1]    # this step's outputs go to the other pair
@@ -323,30 +339,19 @@ class ShardedParticleFilter(_ShardedFilter):
             elif t % self.resamp_sched != 0:
                 # no resampling draw closes step t - 1: every particle continues itself with its carried log-weight; the
                 # sources are this rank's own tiles, nothing travels but the tile sums (for the step's log-likelihood)
-                self._gather_tiles()
+                gather()
                 if self.B > 1024:
-                    self._chk(L.ssme_pf_shard_plan(self._h, self._ptr(ts), self._ptr(tm), t, lo_hi))     # split level-2: accounts the step
+                    self._plan(self._ptr(ts), self._ptr(tm), t)          # split level-2: accounts the step
                 xw, cw, win0 = hx.own(), hc.own(), self.tile0
             else:
-                self._gather_tiles()
-                self._chk(L.ssme_pf_shard_plan(self._h, self._ptr(ts), self._ptr(tm), t, lo_hi))
-                plan = [(lo_hi[2 * g], lo_hi[2 * g + 1]) for g in range(self.world)]
-                got = exchange_halos([hc, hx], self.tile0, plan, self.Bl, self.rank, self.group, self.stage)
-                if got is None:                                          # window wider than the margins: assemble it
-                    sends, recvs = exchange_plan(plan, self.Bl, self.rank)
-                    cw = exchange_tiles(hc.own(), self.tile0, sends, recvs, self.rank, self.group, self.stage)
-                    xw = exchange_tiles(hx.own(), self.tile0, sends, recvs, self.rank, self.group, self.stage)
-                    win0 = plan[self.rank][0]
-                else:
-                    win0, wt = got
-                    cw, xw = hc.rows(win0, wt, self.tile0), hx.rows(win0, wt, self.tile0)
-                self._count_exchanged(*plan[self.rank])
+                gather()
+                win0, (cw, xw) = self._windows(self._plan(self._ptr(ts), self._ptr(tm), t), [hc, hx], (t,))
             self._chk(L.ssme_pf_shard_step(
                 self._h, t, None if xw is None else self._ptr(xw), None if cw is None else self._ptr(cw), win0,
                 self._ptr(ts), self._ptr(tm), self._ptr(ox.own()), self._ptr(oc.own()), self._ptr(self.tiles_loc[0]),
                 self._ptr(self.tiles_loc[1]), None if self.anc is None else self._ptr(self.anc)))
             self._cur ^= 1
-        self._gather_tiles()
+        gather()
         self._chk(L.ssme_pf_shard_finalize(self._h, T - 1, self._ptr(ts), self._ptr(tm)))
         self._T = T
         out = np.empty(1)
@@ -413,14 +418,12 @@ class ShardedLiuWest(_ShardedFilter):
         self._use_side_stream()
         f64 = dict(dtype=torch.float64, device=self.device)
         Bl = self.Bl
-        margin = min(self.B - Bl, max(2, Bl // 2)) if self.world > 1 else 0
-        self._rows = Bl + 2 * margin
-        mk = lambda: HaloBuffer(Bl, TILE, margin, self.device, torch.float64)
+        mk = lambda: HaloBuffer(Bl, TILE, self.margin, self.device, torch.float64)
         # stage-2 outputs / stage-1 sources, and stage-1 outputs / stage-2 sources; theta: one 32-byte record per particle,
         # i.e. rows of 2048 x 4 doubles that travel with their tile
         self.xB, self.cdfB, self.xr, self.lw1, self.cdfA = mk(), mk(), mk(), mk(), mk()
-        self.thB = HaloBuffer(Bl, TILE * 4, margin, self.device, torch.float64)
-        self.thr = HaloBuffer(Bl, TILE * 4, margin, self.device, torch.float64)
+        self.thB = HaloBuffer(Bl, TILE * 4, self.margin, self.device, torch.float64)
+        self.thr = HaloBuffer(Bl, TILE * 4, self.margin, self.device, torch.float64)
         self.tilesB = torch.zeros((2, Bl), **f64)            # rows: tile sums, tile maxima (second-stage weights)
         self._locA = torch.zeros(18 * Bl, **f64)             # stage-1 outputs in one buffer: tile sums | tile maxima | 16 moments per tile
         self.tilesA = self._locA[:2 * Bl].view(2, Bl)
@@ -430,77 +433,37 @@ class ShardedLiuWest(_ShardedFilter):
         self.mom_all = torch.zeros((self.world * Bl, 16), **f64)
         torch.cuda.synchronize(self.device)
 
-    def _gather_B(self):
-        G = gather_flat(self.tilesB.reshape(-1), self.world, self.group, self.stage)               # [world, 2 Bl]
-        self.allB[0].view(self.world, self.Bl).copy_(G[:, :self.Bl])
-        self.allB[1].view(self.world, self.Bl).copy_(G[:, self.Bl:])
-
-    def _gather_A(self):
-        Bl = self.Bl
-        G = gather_flat(self._locA, self.world, self.group, self.stage)                             # [world, 18 Bl]: ONE collective
-        self.allA[0].view(self.world, Bl).copy_(G[:, :Bl])
-        self.allA[1].view(self.world, Bl).copy_(G[:, Bl:2 * Bl])
-        self.mom_all.view(self.world, Bl * 16).copy_(G[:, 2 * Bl:])
-
-    def _windows(self, which, t, tiles_all, halos2d, halo_th):
-        """plan + exchange for one draw.  Returns (win_tile0, window tiles, [2-D source windows], theta source window).
-        Own tiles stay where they are; only halo tiles travel."""
-        import torch
-        lo_hi = (C.c_int32 * (2 * self.world))()
-        self._chk(capi.lib().ssme_lw_shard_plan(self._h, which, t, self._ptr(tiles_all[0]), self._ptr(tiles_all[1]), lo_hi))
-        plan = [(lo_hi[2 * g], lo_hi[2 * g + 1]) for g in range(self.world)]
-        lo_r, hi_r = plan[self.rank]
-        self._count_exchanged(lo_r, hi_r)
-        got = exchange_halos(halos2d + [halo_th], self.tile0, plan, self.Bl, self.rank, self.group, self.stage)
-        if got is not None:
-            w0, wt = got
-            return w0, wt, [hb.rows(w0, wt, self.tile0) for hb in halos2d], halo_th.rows(w0, wt, self.tile0)
-        sends, recvs = exchange_plan(plan, self.Bl, self.rank)             # window wider than the margins: assemble it
-        wins = [exchange_tiles(hb.own(), self.tile0, sends, recvs, self.rank, self.group, self.stage) for hb in halos2d]
-        wth = exchange_tiles(halo_th.own(), self.tile0, sends, recvs, self.rank, self.group, self.stage)
-        self._keep = (wins, wth)                                           # keep the assembled windows alive until the launch
-        return lo_r, hi_r - lo_r + 1, wins, wth
-
-    def run_series(self, y, z=None):
-        import torch
-        self._stream.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(self._stream):
-            return self._run_series(y, z)
-
-    def _run_series(self, y, z):
-        L, p = capi.lib(), self._ptr
-        yv = capi.as_f64(y)
-        zv = None if z is None else capi.as_f64(z)
+    def _run_series(self, yv, zv):
+        L, p, Bl = capi.lib(), self._ptr, self.Bl
         T = yv.size
         self._chk(L.ssme_lw_shard_prepare(self._h, capi.dptr(yv), capi.dptr(zv), T))
-        self.exchanged_tiles = 0
+        gather_B = lambda: self._gather(self.tilesB.reshape(-1), [(self.allB[0], Bl), (self.allB[1], Bl)])
         thB_own, thr_own = p(self.thB.own()), p(self.thr.own())
         self._chk(L.ssme_lw_shard_init(self._h, p(self.xB.own()), thB_own, p(self.cdfB.own()), p(self.tilesB[0]), p(self.tilesB[1])))
         for t in range(1, T):
-            self._gather_B()
+            gather_B()
             if t % self.rs == 0:
-                w0, rows, (w_x, w_cdf), w_th = self._windows(0, t, self.allB, [self.xB, self.cdfB], self.thB)
+                plan = self._plan(0, t, p(self.allB[0]), p(self.allB[1]))
+                w0, (w_x, w_cdf, w_th) = self._windows(plan, [self.xB, self.cdfB, self.thB], (t, 0))
             else:       # no resampling draw closes step t - 1: the sources of stage 1 are this rank's own particles
                 if self.B > 1024:      # split level-2: the plan provides (m, S) of the second-stage weights for the accounting
-                    lo_hi = (C.c_int32 * (2 * self.world))()
-                    self._chk(L.ssme_lw_shard_plan(self._h, 0, t, p(self.allB[0]), p(self.allB[1]), lo_hi))
-                w0, rows = self.tile0, self.Bl
-                w_x, w_cdf, w_th = self.xB.own(), self.cdfB.own(), self.thB.own()
-            self._chk(L.ssme_lw_shard_stage1(self._h, t, w0, rows, p(w_x), p(w_th), p(w_cdf), p(self.allB[0]), p(self.allB[1]),
+                    self._plan(0, t, p(self.allB[0]), p(self.allB[1]))
+                w0, w_x, w_cdf, w_th = self.tile0, self.xB.own(), self.cdfB.own(), self.thB.own()
+            self._chk(L.ssme_lw_shard_stage1(self._h, t, w0, w_x.shape[0], p(w_x), p(w_th), p(w_cdf), p(self.allB[0]), p(self.allB[1]),
                                              p(self.xr.own()), thr_own, p(self.lw1.own()), p(self.cdfA.own()), p(self.tilesA[0]),
                                              p(self.tilesA[1]), p(self.mom), None))
-            self._gather_A()
+            self._gather(self._locA, [(self.allA[0], Bl), (self.allA[1], Bl), (self.mom_all, 16 * Bl)])
             # the plan of the k draw first: with the split level-2 it also provides the (m, S) that mid turns into lse1
             if self.form == 0:
-                w0, rows, (w_x, w_lw1, w_cdf), w_th = self._windows(1, t, self.allA, [self.xr, self.lw1, self.cdfA], self.thr)
+                plan = self._plan(1, t, p(self.allA[0]), p(self.allA[1]))
+                w0, (w_x, w_lw1, w_cdf, w_th) = self._windows(plan, [self.xr, self.lw1, self.cdfA, self.thr], (t, 1))
             else:       # SISR form: every particle continues itself -- the sources of stage 2 are this rank's own stage-1 outputs
-                w0, rows = self.tile0, self.Bl
-                w_x, w_lw1, w_cdf, w_th = self.xr.own(), self.lw1.own(), self.cdfA.own(), self.thr.own()
+                w0, w_x, w_lw1, w_cdf, w_th = self.tile0, self.xr.own(), self.lw1.own(), self.cdfA.own(), self.thr.own()
             self._chk(L.ssme_lw_shard_mid(self._h, t, p(self.allA[0]), p(self.allA[1]), p(self.mom_all)))
-            self._chk(L.ssme_lw_shard_stage2(self._h, t, w0, rows, p(w_x), p(w_th), p(w_lw1), p(w_cdf), p(self.allA[0]),
+            self._chk(L.ssme_lw_shard_stage2(self._h, t, w0, w_x.shape[0], p(w_x), p(w_th), p(w_lw1), p(w_cdf), p(self.allA[0]),
                                              p(self.allA[1]), p(self.xB.own()), thB_own, p(self.cdfB.own()), p(self.tilesB[0]),
                                              p(self.tilesB[1]), None))
-        self._gather_B()
+        gather_B()
         self._chk(L.ssme_lw_shard_finalize(self._h, T - 1, p(self.allB[0]), p(self.allB[1])))
         self._T = T
         out = np.empty(1)

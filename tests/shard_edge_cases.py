@@ -61,6 +61,17 @@ def halo_margin(Bl, world):
     return min(m, Bl)
 
 
+def py_margin(B, Bl, world):
+    """ssme_amd/sharded.py (_ShardedFilter.margin), the rule of the host-planned loops: 2 tiles or half the share, never more than the
+    tiles other ranks own.  A different rule from halo_margin; on PY_LAYOUT (Bl = 2, world 2 and 4) both give 2."""
+    return min(B - Bl, max(2, Bl // 2)) if world > 1 else 0
+
+
+def py_layout(world):
+    """PY_LAYOUT for `world` ranks of the Python drivers: Bl = 2 tiles per rank (world 4: LAYOUTS["4x2"] itself)."""
+    return dict(LAYOUTS[PY_LAYOUT], world=world, n=world * 2 * TILE)
+
+
 def shares(n, world):
     """(B, Bl, [tiles rank r owns], [particles rank r owns]) or None if a rank would own no tile (set_layout returns false)."""
     B = -(-n // TILE)
@@ -346,16 +357,22 @@ def lw_oracle_run(oracle, case, layout, form):
     return _LW_RUNS[key]
 
 
-def lw_must_leave(oracle, case, layout, form):
-    """True where the oracle proves a window leaves the halo: at some step every ancestor of the resampling draw lies in ONE source tile
-    (so the window is that tile whichever way the indices are recorded) and that tile is further than the margin from some rank."""
+def lw_must_leave_steps(oracle, case, layout, form):
+    """The steps at which the oracle proves that a window of the RESAMPLING draw leaves the halo: every ancestor of that draw lies in
+    ONE source tile (so the window is that tile whichever way the indices are recorded) and that tile is further than the margin from
+    some rank.  Only the resampling draw (which = 0) is looked at; the k draw of stage 2 (which = 1) is not covered."""
     B, Bl, own, parts = shares(layout["n"], layout["world"])
     margin = halo_margin(Bl, layout["world"])
+    out = []
     for t in range(1, LW_T):
         a = np.asarray(lw_oracle_run(oracle, case, layout, form)[t][1]["anc"]).astype(np.int64) // TILE
         if a.min() == a.max():
             b = int(a[0])
-            for r in range(layout["world"]):
-                if r * Bl - b > margin or b - (r * Bl + own[r] - 1) > margin:
-                    return True
-    return False
+            if any(r * Bl - b > margin or b - (r * Bl + own[r] - 1) > margin for r in range(layout["world"])):
+                out.append(t)
+    return out
+
+
+def lw_must_leave(oracle, case, layout, form):
+    """True where the oracle proves a window leaves the halo at some step."""
+    return bool(lw_must_leave_steps(oracle, case, layout, form))

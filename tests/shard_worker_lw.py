@@ -33,7 +33,8 @@ def main():
     rs = int(sys.argv[10]) if len(sys.argv) > 10 else 1
     f = ShardedLiuWest(delta, 0.8, 0.99, -0.1, 0.1, 0.01, 0.1, -0.5, -0.01, nparts=n, seed=seed, form=form, rs=rs)
     ll = f.run_series(y, z)
-    np.savez(out, ll=ll, per_step=f.per_step(), x=f.local_particles(), theta=f.local_theta(), exchanged=f.exchanged_tiles)
+    np.savez(out, ll=ll, per_step=f.per_step(), x=f.local_particles(), theta=f.local_theta(), exchanged=f.exchanged_tiles,
+             routes=np.array([(str(t), str(which), route) for t, which, route in f.window_routes], dtype=str).reshape(-1, 3))
     f.close()
     dist.barrier()
     dist.destroy_process_group()

@@ -107,3 +107,25 @@ def test_liu_west_cases_reach_their_step(oracle, cname, lname):
             assert must == (lname != "2r-one-particle")                        # tile 0 is within the margin of both ranks there
         else:
             assert not must                                                    # the path of huge-y is an observation
+
+
+def test_python_driver_pairs_reach_both_routes(oracle):
+    """The pairs of test_shard_edges_gpu.py's Python-driver tests (nan-y and huge-y on shard_edge_cases.py_layout, Bl = 2) reach both
+    routes of _ShardedFilter._windows.  World 2: B - Bl = 2 is within the margin, so every window fits and every draw is in place.
+    World 4 (the layout 4x2 itself): must_leave is non-empty for both bootstrap cases -- test_pair_reaches_what_it_is_listed_for holds
+    it to the oracle's ancestors exactly -- and the Liu-West resampling draw of nan-y's step 3 needs tile 0 on ranks 2 and 3; the
+    Liu-West huge-y proves nothing (its route is an observation)."""
+    for world in (2, 4):
+        B, Bl, own, parts = sc.shares(sc.py_layout(world)["n"], world)
+        assert (B, Bl) == (2 * world, 2) and sc.py_margin(B, Bl, world) == 2 == sc.halo_margin(Bl, world)
+    assert sc.py_margin(8 * 64, 64, 8) == 32 and sc.py_margin(3, 1, 3) == 2 and sc.py_margin(2, 1, 2) == 1 and sc.py_margin(4, 4, 1) == 0
+    B, Bl, own, parts = sc.shares(sc.py_layout(2)["n"], 2)
+    assert B - Bl <= sc.py_margin(B, Bl, 2)
+    layout = sc.py_layout(4)
+    assert layout == sc.LAYOUTS["4x2"]
+    for cname, want in (("nan-y", ((3, 2), (3, 3))), ("huge-y", ((3, 0), (3, 1)))):
+        case = sc.CASES[cname]
+        assert sc.must_leave(case, layout, 0) == want == tuple(sc.must_leave_from_oracle(oracle, case, layout, 0)[0])
+        assert sc.shape(case, layout)[1] > 3                                   # step 3 is inside the series
+    assert 3 in sc.lw_must_leave_steps(oracle, sc.LW_CASES["nan-y"], layout, 0) and sc.LW_T > 3
+    assert sc.lw_must_leave_steps(oracle, sc.LW_CASES["huge-y"], layout, 0) == []

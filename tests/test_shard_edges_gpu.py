@@ -325,12 +325,36 @@ def _run_workers(script, world, args_of, outs):
     return [np.load(o) for o in outs]
 
 
+def _window_routes(res, name, world, margin):
+    """window_routes as every rank saved it: the same list on every rank (the fit decision is global), every entry one of the two routes.
+    World 2: B - Bl = 2 = the margin, so no window can fail to fit -- every draw exchanges in place, and some rank received tiles."""
+    per_rank = [[tuple(int(v) for v in row[:-1]) + (str(row[-1]),) for row in r["routes"]] for r in res]
+    print(f"SHARDROUTE {name} world {world} routes {per_rank[0]} exchanged {[int(r['exchanged']) for r in res]}")
+    assert all(p == per_rank[0] for p in per_rank), per_rank
+    assert per_rank[0] and {e[-1] for e in per_rank[0]} <= {"in_place", "assembled"}, per_rank[0]
+    if world == 2:
+        B, Bl, own, parts = sc.shares(sc.py_layout(2)["n"], 2)
+        assert B - Bl <= margin
+        assert all(e[-1] == "in_place" for e in per_rank[0]), per_rank[0]
+        assert sum(int(r["exchanged"]) for r in res) > 0
+    return per_rank[0]
+
+
+def _py_margin(layout):
+    B, Bl, own, parts = sc.shares(layout["n"], layout["world"])
+    margin = sc.py_margin(B, Bl, layout["world"])
+    assert margin == 2 == sc.halo_margin(Bl, layout["world"])               # the two rules agree on this layout: the oracle's lists apply
+    return margin
+
+
 @pytest.mark.parametrize("world", [2, 4])
 @pytest.mark.parametrize("cname", ["nan-y", "huge-y"])
 def test_python_bootstrap_driver(oracle, tmp_path, cname, world):
     """ShardedParticleFilter.run_series (the host-planned loop: ssme_pf_shard_plan, the halo or the assembled window, ssme_pf_shard_step)
-    over a collapsed cloud, Bl = 2: the oracle's bits on every rank."""
-    case, layout = sc.CASES[cname], dict(sc.LAYOUTS[sc.PY_LAYOUT], world=world, n=world * 2 * sc.TILE)
+    over a collapsed cloud, Bl = 2: the oracle's bits on every rank, and the route of every draw (window_routes: (t, route)).  World 2
+    must stay in place (_window_routes); at world 4 every step of shard_edge_cases.must_leave must be assembled on every rank: the
+    oracle's needed reach exceeds the margin there, and the planned window contains the needed one."""
+    case, layout = sc.CASES[cname], sc.py_layout(world)
     n, T = sc.shape(case, layout)
     yset, zset, theta = sc.overrides(case, T)
     outs = [str(tmp_path / f"rank{r}.npz") for r in range(world)]
@@ -344,14 +368,24 @@ def test_python_bootstrap_driver(oracle, tmp_path, cname, world):
     same_bits(np.concatenate([r["x"] for r in res]), so["x"], "final particles")
     np.testing.assert_array_equal(np.concatenate([r["cdf"] for r in res]).astype(np.uint64), so["cdf"])
     np.testing.assert_array_equal(np.concatenate([r["anc"] for r in res]).astype(np.uint32), so["anc"])
+    routes = _window_routes(res, cname, world, _py_margin(layout))
+    assert [t for t, _ in routes] == sc.resampled_steps(case, T)             # one entry per draw that exchanged
+    if world == 4:
+        must = sc.must_leave(case, layout, 0)
+        assert must == {"nan-y": ((3, 2), (3, 3)), "huge-y": ((3, 0), (3, 1))}[cname]
+        for t in sorted({t for t, _ in must}):
+            assert (t, "assembled") in routes, (t, routes)
 
 
 @pytest.mark.parametrize("world", [2, 4])
 @pytest.mark.parametrize("cname", ["nan-y", "huge-y"])
 def test_python_liu_west_driver(oracle, tmp_path, cname, world):
     """ShardedLiuWest.run_series -- the host-planned loop that run_series_native hands over to when the C++ driver returns
-    SSME_ERR_STATE (that hand-over itself needs one GPU per rank) -- over a collapsed cloud: the oracle's bits on every rank."""
-    case, layout = sc.LW_CASES[cname], dict(sc.LAYOUTS[sc.PY_LAYOUT], world=world, n=world * 2 * sc.TILE)
+    SSME_ERR_STATE (that hand-over itself needs one GPU per rank) -- over a collapsed cloud: the oracle's bits on every rank, and the
+    route of every draw (window_routes: (t, which, route)).  World 2 must stay in place (_window_routes); at world 4 the resampling draw
+    (which = 0) of every step in shard_edge_cases.lw_must_leave_steps must be assembled on every rank.  That list does not cover the k draw
+    (which = 1) nor the steps whose ancestors span several tiles (all of huge-y): those draws are held to rank agreement only."""
+    case, layout = sc.LW_CASES[cname], sc.py_layout(world)
     lst = lambda d: ",".join(f"{t}:{sc._fmt(v)}" for t, v in sorted(d.items())) or "-"
     outs = [str(tmp_path / f"lw_rank{r}.npz") for r in range(world)]
     res = _run_workers("shard_worker_lw.py", world, [str(layout["n"]), str(sc.LW_T), str(sc.SEED), repr(sc.LW_DELTA), "0", "1", lst(case["y_set"]),
@@ -364,3 +398,8 @@ def test_python_liu_west_driver(oracle, tmp_path, cname, world):
     so = run[sc.LW_T - 1][1]
     same_bits(np.concatenate([r["x"] for r in res]), so["x"], "final particles")
     same_bits(np.concatenate([r["theta"] for r in res], axis=1), so["theta"], "final parameters")
+    routes = _window_routes(res, "lw " + cname, world, _py_margin(layout))
+    assert [(t, which) for t, which, _ in routes] == [(t, which) for t in range(1, sc.LW_T) for which in (0, 1)]   # form 0, rs 1: two draws per step
+    if world == 4:
+        for t in sc.lw_must_leave_steps(oracle, case, layout, 0):
+            assert (t, 0, "assembled") in routes, (t, routes)
