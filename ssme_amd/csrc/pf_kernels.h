@@ -197,27 +197,53 @@ __device__ __forceinline__ double dpp_f64_perm(double v) {       // full permuta
     const int hi = __builtin_amdgcn_mov_dpp((int)(uint32_t)(b >> 32), CTRL, 0xF, 0xF, true);
     return bits2d(((u64)(uint32_t)hi << 32) | (u64)(uint32_t)lo);
 }
+// The v_max_f64 that dmaxnum ends in, alone.  __builtin_fmax first canonicalises both operands (v_max_f64 x, x, x: quiets a
+// signalling NaN, changes nothing else), three instructions per maximum; the maxima below never see a signalling NaN (NaN travels
+// as a flag, or as the quiet dnan() in an LDS slot), so the same instruction on the same operands in the same order gives the
+// same bits, signed zeros included.  (Not compare + select: that differs at (-0, +0).)
+// The result feeds DPP moves directly (wave_max_f64), which must not read a VGPR within two wait states of the VALU write: this
+// relies on the compiler's hazard recognizer tracking the register an inline-asm statement defines.  It does (an s_nop or two
+// independent instructions follow every maximum in the assembly); look at that again after a compiler upgrade.
+__device__ __forceinline__ double dmax_raw(double a, double b) {
+    double d;
+    asm("v_max_f64 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
+    return d;
+}
 __device__ __forceinline__ double wave_max_f64(double v) {
-    v = dmaxnum(v, dpp_f64_perm<0xB1>(v));            // quad_perm [1,0,3,2]
-    v = dmaxnum(v, dpp_f64_perm<0x4E>(v));            // quad_perm [2,3,0,1]
-    v = dmaxnum(v, dpp_f64_perm<0x141>(v));           // row_half_mirror
-    v = dmaxnum(v, dpp_f64_perm<0x140>(v));           // row_mirror: every lane of a row holds the row's maximum
-    v = dmaxnum(v, dpp_f64_neginf<0x142, 0xA>(v));
-    v = dmaxnum(v, dpp_f64_neginf<0x143, 0xC>(v));
+    v = dmax_raw(v, dpp_f64_perm<0xB1>(v));            // quad_perm [1,0,3,2]
+    v = dmax_raw(v, dpp_f64_perm<0x4E>(v));            // quad_perm [2,3,0,1]
+    v = dmax_raw(v, dpp_f64_perm<0x141>(v));           // row_half_mirror
+    v = dmax_raw(v, dpp_f64_perm<0x140>(v));           // row_mirror: every lane of a row holds the row's maximum
+    v = dmax_raw(v, dpp_f64_neginf<0x142, 0xA>(v));
+    v = dmax_raw(v, dpp_f64_neginf<0x143, 0xC>(v));
     return bits2d(readlane_u64(d2bits(v), 63));
 }
 
-// Block max with NaN propagation: returns NaN if any thread passes nan = true.
+// Block max with NaN propagation: returns dnan() if any thread passes nan = true.
+// Precondition: m is not NaN in any thread -- a NaN is reported through the flag, as every caller does (mx starts at -inf and is
+// replaced only where v > mx).  A NaN in m is not defined behaviour of this function: one that only some lanes of a wave pass is
+// dropped by v_max_f64, one that every lane of a wave passes reaches the slot and makes the result dnan().
 // lds: NT/64 doubles, not reused by the caller before its next barrier.  One barrier.
+// The flag rides in the wave's own slot (a wave with a flagged lane writes dnan() instead of its maximum), so there is no
+// block-wide or-reduction (__syncthreads_or is three barriers and an LDS atomic) and no LDS beyond the slots.  Every thread
+// folds the slots with v_max_f64, which drops a quiet NaN operand, and finds a NaN slot with unordered compares, two slots each.
 template <int NT>
 __device__ __forceinline__ double block_max_nanprop(double m, bool nan, double* lds) {
+    constexpr int NW = NT / 64;
     m = wave_max_f64(m);
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = m;
-    const int any_nan = __syncthreads_or(nan ? 1 : 0);
-    double r = lds[0];
+    const bool any = __ballot(nan) != 0;               // scalar
+    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = any ? dnan() : m;
+    __syncthreads();
+    double s[NW];
 #pragma unroll
-    for (int w = 1; w < NT / 64; ++w) r = dmaxnum(r, lds[w]);
-    return any_nan ? dnan() : r;
+    for (int w = 0; w < NW; ++w) s[w] = lds[w];
+    double r = s[0];
+    bool un = false;
+#pragma unroll
+    for (int w = 1; w < NW; ++w) r = dmax_raw(r, s[w]);
+#pragma unroll
+    for (int w = 0; w < NW; w += 2) un = un || __builtin_isunordered(s[w], s[w + 1 < NW ? w + 1 : w]);   // (one-wave blocks: NW = 1)
+    return un ? dnan() : r;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -422,6 +448,9 @@ __device__ __forceinline__ void level2_scan(const double (&A)[2048 / NT], const 
 #pragma unroll
     for (int e = 0; e < NE; ++e) {
         if (e * NT < B) {
+            // legs e >= 1 exist only in filters of more than NT tiles: kept a uniform branch (as selects under scalar masks they
+            // cost every filter some 20 instructions per wave)
+            if (e) asm volatile("");
             const int j = e * NT + threadIdx.x;
             if (j < B) { const double v = mb[e]; nan = nan || (v != v); mx = (v > mx) ? v : mx; }
         }
