@@ -57,21 +57,13 @@ struct FcArgs : FcCommon {
 };
 
 // The start draw of particle i: u = u01_mid40 of words 0-1 of Philox(i, t0, filter id, STREAM_FC_START), target = ceil(u S'),
-// source tile b = min(#{j < B : T'_j < target}, B - 1), tile-local target tloc = ceil((target - T'_{b-1}) A_b / A'_b),
-// j = #{q : cdf_b[q] < tloc} (count_less_pow2: at most tile - 1), ancestor = min(b tile + j, N - 1).  Probes go to L2.
+// ancestor = the filters' general search of that target (probe_ancestor, pf_kernels.h).
 // Shared by the bootstrap and the Liu-West start kernels.
 __device__ __forceinline__ int fc_draw_ancestor(const double* T, const double* Rr, const double* cdf_r, double S, int B, int Bpow2,
                                                 int tile, int N, int i, uint32_t t0, uint32_t rep, uint32_t key0, uint32_t key1) {
     const u32x4 o = philox4x32_10((uint32_t)i, t0, rep, STREAM_FC_START, key0, key1);
     const double target = __builtin_ceil(u01_mid40(o.v0, o.v1) * S);
-    int bb = count_less_pow2(Bpow2, target, [&](int j) { return j < B ? T[j] : dinf(); });
-    bb = bb < B - 1 ? bb : B - 1;
-    const double Pb = bb ? T[bb - 1] : 0.0;
-    const double tloc = __builtin_ceil((target - Pb) * Rr[bb]);
-    const double* tl = cdf_r + (size_t)bb * tile;
-    const int j = count_less_pow2(tile, tloc, [&](int q) { return tl[q]; });
-    const int an = bb * tile + j;
-    return an < N - 1 ? an : N - 1;
+    return probe_ancestor(target, [&](int j) { return j < B ? T[j] : dinf(); }, [&](int j) { return Rr[j]; }, cdf_r, B, Bpow2, tile, 0, N);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -138,12 +138,13 @@ __device__ __forceinline__ double lw_propmu(double x, double z, const double (&t
 
 // ---------------------------------------------------------------------------------------
 // Shared selection: indices idx[k][c] = #{j : C_j < tau} for this tile's sorted-uniform targets against the exact
-// integer cdf (tile sums tsum / maxima tmax / tile-local cdf).  Same arithmetic as k_filter_step.
+// integer cdf (tile sums tsum / maxima tmax / tile-local cdf): the level-2 head of a Liu-West stage, then the selection
+// pieces of pf_kernels.h in k_filter_step's order.
 // Returns the level-2 results m (global max log-weight) and S (integer weight sum).  Block = 512 threads.
 // ---------------------------------------------------------------------------------------
 struct LwLds {
     double* lds_T; double* lds_R; double* lds_stage;     // dynamic LDS
-    double* seg_a; double* seg_l2; double* d1; int* cnt;
+    double* seg_a; double* seg_l2; double* d1; int* cnt; double* R3;
     const LogTabEntry* ltab; const ExpTabEntry* etab;    // dlog_u / dexp_scaled_t tables in LDS
 };
 
@@ -162,15 +163,16 @@ __device__ __forceinline__ void lw_select(const double* tsum, const double* tmax
     __builtin_amdgcn_s_setprio(3);                 // wave priority falls as the workgroup advances (see prio_at)
     double t_scale;
     int lo, hi;
+    double A2[NE], Ap[NE];                         // in-LDS level-2: the tile sums this thread holds, for publish_ratios
     if constexpr (BIG) {
         m_out = v.m; S_out = v.S;
         t_scale = v.S / G;
         lo = v.lo[b]; hi = v.hi[b];
     } else {
-        double A2[NE], M2[NE];
+        double M2[NE];
         level2_load<NT>(tsum, tmax, B, A2, M2);
         if (tid == 0) { L.cnt[0] = 0; L.cnt[1] = 0; }
-        double Ap[NE], Tinc[NE], m, S;
+        double Tinc[NE], m, S;
         level2_scan<NT>(A2, M2, B, rshift, m, Ap, Tinc, S, L.d1, L.seg_l2, L.etab);
         m_out = m; S_out = S;
         t_scale = S / G;
@@ -180,10 +182,7 @@ __device__ __forceinline__ void lw_select(const double* tsum, const double* tmax
         for (int e = 0; e < NE; ++e) {
             if (e * NT < Bpow2) {
                 const int j = e * NT + tid;
-                if (j < Bpow2) {
-                    L.lds_T[j] = (j < B) ? Tinc[e] : dinf();
-                    L.lds_R[j] = (j < B) ? A2[e] / Ap[e] : 0.0;
-                }
+                if (j < Bpow2) L.lds_T[j] = (j < B) ? Tinc[e] : dinf();
                 const int w_lo = __popcll(__ballot(j < B && Tinc[e] < t_lo));
                 const int w_hi = __popcll(__ballot(j < B && Tinc[e] < t_hi));
                 if ((tid & 63) == 0) { if (w_lo) atomicAdd(&L.cnt[0], w_lo); if (w_hi) atomicAdd(&L.cnt[1], w_hi); }
@@ -196,78 +195,25 @@ __device__ __forceinline__ void lw_select(const double* tsum, const double* tmax
     hi = hi < B - 1 ? hi : B - 1;
     int bb_min = __builtin_amdgcn_readfirstlane(lo);
     int span = __builtin_amdgcn_readfirstlane(hi) - bb_min + 1;
-    if (win_flag) {
-        // fixed-halo sharding (see k_filter_step): sources outside the exchanged window are reported; this launch stays in bounds
-        const int first = win_tile0 > 0 ? win_tile0 : 0, last = win_tile0 + win_tiles - 1 < B - 1 ? win_tile0 + win_tiles - 1 : B - 1;
-        if (bb_min < first || bb_min + span - 1 > last) {
-            if (tid == 0) atomicOr(win_flag, 1);
-            bb_min = bb_min < first ? first : (bb_min > last ? last : bb_min);
-            span = 1;
-        }
-    }
-    double2 stg0[NK], stg1[NK], stg2[NK];
-#pragma unroll
-    for (int k = 0; k < NK; ++k) { stg0[k] = make_double2(0.0, 0.0); stg1[k] = stg0[k]; stg2[k] = stg0[k]; }
-    if (span <= kStageTiles) {
-        const double* src = cdf + (size_t)(bb_min - win_tile0) * kTile + tid * 2;
-#pragma unroll
-        for (int k = 0; k < NK; ++k) stg0[k] = *reinterpret_cast<const double2*>(src + k * NT * 2);
-        if (span >= 2) {
-#pragma unroll
-            for (int k = 0; k < NK; ++k) stg1[k] = *reinterpret_cast<const double2*>(src + kTile + k * NT * 2);
-        }
-        if (span >= 3) {
-#pragma unroll
-            for (int k = 0; k < NK; ++k) stg2[k] = *reinterpret_cast<const double2*>(src + 2 * kTile + k * NT * 2);
-        }
-    }
+    clamp_to_window(win_flag, win_tile0, win_tiles, B, bb_min, span);
+    if constexpr (!BIG) publish_ratios<NT>(A2, Ap, B, Bpow2, bb_min, span, L.R3, L.lds_R);
+    StagedTiles<NT, NK, kTile> stg;
+    stg.load(cdf + (size_t)(bb_min - win_tile0) * kTile, span);
     __builtin_amdgcn_s_setprio(2);
-    // exponential spacings (liu_west_filter.h:105-139), exact tile scan; hides the tile loads
-    double qe[NK][2], le[NK][2], se;
-#pragma unroll
-    for (int k = 0; k < NK; ++k) {
-        const int i0 = i_first + (k * NT + tid) * 2;
-        double e0, e1;
-        pair_spacings(draw[k], L.ltab, &e0, &e1);          // words 2-3 of the pair's draw (32-bit uniforms, table log)
-        qe[k][0] = __builtin_rint(e0 * 34359738368.0);
-        qe[k][1] = __builtin_rint(e1 * 34359738368.0);
-        if (i_first + kTile > N) {        // uniform: only the ragged last tile masks the particles beyond N
-            asm volatile("");
-            if (!(i0 < N)) qe[k][0] = 0.0;
-            if (!(i0 + 1 < N)) qe[k][1] = 0.0;
-        }
-    }
-    block_scan_f64<NT, NK>(qe, le, se, L.seg_a);
-    const double ratio = gam / se;
+    // words 2-3 of the pair's draw -> spacings (32-bit uniforms, table log) -> targets; the arithmetic hides the tile loads
     double tau[NK][2];
-#pragma unroll
-    for (int k = 0; k < NK; ++k) {
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            const double t1 = ratio * le[k][c];
-            const double t2 = pgam + t1;
-            tau[k][c] = __builtin_ceil(t2 * t_scale);
-        }
-    }
+    multinomial_targets<NT, NK, kTile>([&](int k, double& e0, double& e1) { pair_spacings(draw[k], L.ltab, &e0, &e1); },
+                                       i_first, N, gam, pgam, t_scale, L.seg_a, tau);
+    auto Tof = [&](int j) -> double { return BIG ? v.T[j] : L.lds_T[j]; };                               // j < B
+    auto Tinf = [&](int j) -> double { return BIG ? (j < B ? v.T[j] : dinf()) : L.lds_T[j]; };           // lds_T holds +inf beyond B
     if (span <= kStageTiles) {
-        double* dst = L.lds_stage + tid * 2;
-#pragma unroll
-        for (int k = 0; k < NK; ++k) *reinterpret_cast<double2*>(dst + k * NT * 2) = stg0[k];
-        if (span >= 2) {
-#pragma unroll
-            for (int k = 0; k < NK; ++k) *reinterpret_cast<double2*>(dst + kTile + k * NT * 2) = stg1[k];
-        }
-        if (span >= 3) {
-#pragma unroll
-            for (int k = 0; k < NK; ++k) *reinterpret_cast<double2*>(dst + 2 * kTile + k * NT * 2) = stg2[k];
-        }
-        const int b1 = bb_min + 1 < B ? bb_min + 1 : B - 1, b2 = bb_min + 2 < B ? bb_min + 2 : B - 1;
-        const double T0 = BIG ? v.T[bb_min] : L.lds_T[bb_min];
-        const double T1 = (bb_min + 1 < B) ? (BIG ? v.T[bb_min + 1] : L.lds_T[bb_min + 1]) : dinf();
-        const double Pm = bb_min ? (BIG ? v.T[bb_min - 1] : L.lds_T[bb_min - 1]) : 0.0;
-        const double R0 = BIG ? v.R[bb_min] : L.lds_R[bb_min], R1 = BIG ? v.R[b1] : L.lds_R[b1], R2 = BIG ? v.R[b2] : L.lds_R[b2];
+        stg.store(L.lds_stage, span);
+        double Pm, T0, T1, R0, R1, R2;
+        staged_prefixes(Tof, bb_min, B, Pm, T0, T1);
         __syncthreads();
-        // the four count-searches of a thread descend together (staged_search, pf_kernels.h)
+        if (BIG) staged_ratios([&](int j) { return v.R[j]; }, bb_min, B, R0, R1, R2);
+        else { R0 = L.R3[0]; R1 = L.R3[1]; R2 = L.R3[2]; }
+        // the four count-searches of a thread descend together
         int soff[NK][2];
         staged_search<kTile, NK>(tau, span, Pm, T0, T1, R0, R1, R2, L.lds_stage, soff);
 #pragma unroll
@@ -282,17 +228,8 @@ __device__ __forceinline__ void lw_select(const double* tsum, const double* tmax
 #pragma unroll
         for (int k = 0; k < NK; ++k) {
 #pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                const double target = tau[k][c];
-                int bb = count_less_pow2(Bpow2, target, [&](int j) { return BIG ? (j < B ? v.T[j] : dinf()) : L.lds_T[j]; });
-                bb = bb < B - 1 ? bb : B - 1;
-                const double Pb = bb ? (BIG ? v.T[bb - 1] : L.lds_T[bb - 1]) : 0.0;
-                const double tloc = __builtin_ceil((target - Pb) * (BIG ? v.R[bb] : L.lds_R[bb]));
-                const double* tile = cdf + (size_t)(bb - win_tile0) * kTile;
-                const int j = count_less_pow2(kTile, tloc, [&](int q) { return tile[q]; });
-                int a = bb * kTile + j;
-                idx[k][c] = a < N - 1 ? a : N - 1;
-            }
+            for (int c = 0; c < 2; ++c)
+                idx[k][c] = probe_ancestor(tau[k][c], Tinf, [&](int j) { return BIG ? v.R[j] : L.lds_R[j]; }, cdf, B, Bpow2, kTile, win_tile0, N);
         }
     }
     __builtin_amdgcn_s_setprio(1);
@@ -348,13 +285,14 @@ __device__ __forceinline__ void lw_store_cdf(const double (&lg)[2][2], int /*N*/
     __shared__ double lds_d1[16];                                                                         \
     __shared__ double lds_d2[16];                                                                         \
     __shared__ int lds_cnt[2];                                                                            \
+    __shared__ double lds_R3[4];                                                                          \
     __shared__ __attribute__((aligned(16))) DrawTabs lds_dtab;                                                 \
     __shared__ ExpTabEntry lds_etab[SSME_EXP_TABLE_SIZE];                                                 \
     load_log_table<kLwNT>(&lds_dtab);                                                                      \
     load_exp_table<kLwNT>(lds_etab);                                                                      \
     LwLds L;                                                                                              \
     L.lds_stage = reinterpret_cast<double*>(smem); L.lds_T = L.lds_stage + kStageTiles * kTile; L.lds_R = L.lds_T + nT2;  \
-    L.seg_a = lds_seg_a; L.seg_l2 = lds_seg_l2; L.d1 = lds_d1; L.cnt = lds_cnt;                           \
+    L.seg_a = lds_seg_a; L.seg_l2 = lds_seg_l2; L.d1 = lds_d1; L.cnt = lds_cnt; L.R3 = lds_R3;            \
     L.ltab = lds_dtab.log; L.etab = lds_etab;                                                                 \
     __syncthreads();
 
@@ -481,8 +419,7 @@ __global__ __launch_bounds__(kLwNT) void k_lw_stage1(const LwArgs a) {
         // log p(y_{t-1} | y_{1:t-2}).  Auxiliary form: :1047-1051 (two log-sum-exps minus twice that of the weights the step
         // started from; :1136 at t-1 = 0); SISR form: :2257-2264 (:2301 at t-1 = 0).
         LwScalars* sc = a.scal + r;
-        const double Sd = (SB > 0.0) ? dldexp(SB, -a.rshift) : dnan();
-        const double lseB = mB + dlog(Sd);
+        const double lseB = lse_of(mB, SB, a.rshift);
         const double ll = (a.form == 0 && a.t > 1) ? (lseB + sc->lse1) - 2.0 * sc->prev : lseB - sc->prev;
         sc->mB = mB; sc->SB = SB; sc->last_ll = ll; sc->loglik = sc->loglik + ll;
         sc->prev = resampled ? a.logN : lseB;
@@ -671,8 +608,7 @@ __global__ __launch_bounds__(kThreads) void k_lw_mid(const LwArgs a) {
     __syncthreads();
     if (tid == 0) {
         LwScalars* sc = a.scal + r;
-        const double Sd = (S > 0.0) ? dldexp(S, -a.rshift) : dnan();
-        if (aux) sc->lse1 = m + dlog(Sd);
+        if (aux) sc->lse1 = lse_of(m, S, a.rshift);
         lw_proposal_components(sums, a.N, a.a_shrink, a.prop + (size_t)r * 16);
     }
 }
@@ -776,10 +712,7 @@ __global__ __launch_bounds__(kLwNT) void k_lw_stage2(const LwArgs a) {
             if (b == a.tile0) {                            // the filter's first workgroup keeps k_lw_mid's records
                 double* p = a.prop + (size_t)r * 16;
                 for (int q = 0; q < 14; ++q) p[q] = lds_prop[q];
-                if (a.form == 0) {
-                    const double Sd = (SA > 0.0) ? dldexp(SA, -a.rshift) : dnan();
-                    a.scal[r].lse1 = mA + dlog(Sd);
-                }
+                if (a.form == 0) a.scal[r].lse1 = lse_of(mA, SA, a.rshift);
             }
         }
         __syncthreads();
@@ -874,8 +807,7 @@ __global__ __launch_bounds__(kThreads) void k_lw_finalize(const LwArgs a) {
     }
     if (tid == 0) {
         LwScalars* sc = a.scal + r;
-        const double Sd = (S > 0.0) ? dldexp(S, -a.rshift) : dnan();
-        const double lseB = m + dlog(Sd);
+        const double lseB = lse_of(m, S, a.rshift);
         const double ll = (a.form == 0 && a.t > 0) ? (lseB + sc->lse1) - 2.0 * sc->prev : lseB - sc->prev;
         sc->mB = m; sc->SB = S; sc->last_ll = ll; sc->loglik = sc->loglik + ll;
         sc->prev = ((a.t + 1) % a.resamp_sched == 0) ? a.logN : lseB;

@@ -165,6 +165,15 @@ __device__ __forceinline__ double wave_incl_scan_f64(double v) {
     v = v + dpp_f64_zero<0x143, 0xC>(v);
     return v;
 }
+// the same inside every row of 16 lanes: lane l of a row receives the sum of the row's lanes 0 .. l (the segment totals of the
+// block scans and the block totals of the level-2 kernels live in one row)
+__device__ __forceinline__ double row16_incl_scan(double v) {
+    v = v + dpp_f64_zero<0x111, 0xF>(v);
+    v = v + dpp_f64_zero<0x112, 0xF>(v);
+    v = v + dpp_f64_zero<0x114, 0xF>(v);
+    v = v + dpp_f64_zero<0x118, 0xF>(v);
+    return v;
+}
 __device__ __forceinline__ double wave_shr1_f64(double v) { return dpp_f64_zero<0x138, 0xF>(v); }
 __device__ __forceinline__ double readlane_f64(double v, int lane) {
     const u64 b = d2bits(v);
@@ -269,11 +278,7 @@ __device__ __forceinline__ void block_scan_f64(const double (&q)[NK][2], double 
         if (lane == 63) lds_seg[k * WPR + wave] = inc;
     }
     __syncthreads();
-    double sv = (lane & 15) < NSEG ? lds_seg[lane & 15] : 0.0;
-    sv = sv + dpp_f64_zero<0x111, 0xF>(sv);
-    sv = sv + dpp_f64_zero<0x112, 0xF>(sv);
-    sv = sv + dpp_f64_zero<0x114, 0xF>(sv);
-    sv = sv + dpp_f64_zero<0x118, 0xF>(sv);
+    const double sv = row16_incl_scan((lane & 15) < NSEG ? lds_seg[lane & 15] : 0.0);
     total = readlane_f64(sv, 15);
 #pragma unroll
     for (int k = 0; k < NK; ++k) {
@@ -475,11 +480,7 @@ __device__ __forceinline__ void level2_scan(const double (&A)[2048 / NT], const 
     for (int e = 0; e < NE; ++e) {
         Tinc[e] = 0.0;
         if (e * NT < B) {
-            double sv = (lane & 15) < NW ? lds_seg[e * 16 + (lane & 15)] : 0.0;
-            sv = sv + dpp_f64_zero<0x111, 0xF>(sv);
-            sv = sv + dpp_f64_zero<0x112, 0xF>(sv);
-            sv = sv + dpp_f64_zero<0x114, 0xF>(sv);
-            sv = sv + dpp_f64_zero<0x118, 0xF>(sv);
+            const double sv = row16_incl_scan((lane & 15) < NW ? lds_seg[e * 16 + (lane & 15)] : 0.0);
             const double pre = wave ? readlane_f64(sv, wave - 1) : 0.0;
             Tinc[e] = (carry + pre) + inc[e];
             carry = carry + readlane_f64(sv, 15);
@@ -520,6 +521,47 @@ __device__ __forceinline__ void tile_target_bounds(int resampler, double S, int 
     }
 }
 
+// The draw constants of a step's resampling that do not depend on the tile: G = sum(Gamma) + E_{N+1} of the multinomial draw
+// (gtot row a.gi), or the systematic offset u0 (Philox counter (0, t, filter, STREAM_RESAMP_EXTRA)); 1 and 0 where unused.
+__device__ __forceinline__ double systematic_u0(uint32_t t, uint32_t rep, uint32_t key0, uint32_t key1) {
+    const u32x4 ox = philox4x32_10(0u, t, rep, STREAM_RESAMP_EXTRA, key0, key1);
+    return u01_co(ox.v0, ox.v1);
+}
+__device__ __forceinline__ void draw_consts(const StepArgs& a, int resampler, int r, uint32_t rep, double& G, double& u0) {
+    G = 1.0; u0 = 0.0;
+    if (resampler == RESAMP_MULTINOMIAL) G = a.gtot[(size_t)a.gi * a.R + r];
+    else if (resampler == RESAMP_SYSTEMATIC) u0 = systematic_u0((uint32_t)a.t, rep, a.keyp[0], a.keyp[1]);
+}
+
+// log-sum-exp of a step's log-weights from the level-2 results: m + log(S 2^-rshift); NaN when no weight is positive
+__device__ __forceinline__ double lse_of(double m, double S, int rshift) {
+    const double Sd = (S > 0.0) ? dldexp(S, -rshift) : dnan();
+    return m + dlog(Sd);
+}
+// Accounts one step of a bootstrap filter: log p(y_t | y_{1:t-1}) = lse_t - prev, where prev is the log-sum-exp the step started
+// from (log N after a resampling).  `resampled`: the NEXT step starts from equal weights.  Returns the log conditional likelihood.
+__device__ __forceinline__ double account_step(FilterScalars* sc, double m, double S, int rshift, bool resampled, double logN) {
+    const double lse = lse_of(m, S, rshift);
+    const double ll = lse - sc->prev;
+    sc->m = m;
+    sc->S = S;
+    sc->last_ll = ll;
+    sc->loglik = sc->loglik + ll;
+    sc->prev = resampled ? logN : lse;
+    return ll;
+}
+
+// Maximum of the KMAX tile maxima a thread of the split level-2 kernels holds in registers (tile k * NT + tid), NaN reported as a
+// flag (block_max_nanprop's precondition).
+template <int NT, int KMAX>
+__device__ __forceinline__ void reg_max_nanflag(const double (&Mreg)[KMAX], int B, double& mx, bool& nan) {
+    mx = -dinf();
+    nan = false;
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) {
+        if (k * NT + (int)threadIdx.x < B) { const double v = Mreg[k]; nan = nan || (v != v); mx = (v > mx) ? v : mx; }
+    }
+}
 
 // Wave priority by phase.  Two workgroups share a CU and the hardware issues the OLDER waves first, so without this the
 // first-dispatched workgroup runs at full speed, the second one lags by ~5 us, and for that tail the CU holds half its
@@ -676,6 +718,168 @@ __device__ __forceinline__ void staged_search(const double (&tau)[NK][2], int sp
     }
 }
 
+// ---------------------------------------------------------------------------------------
+// The pieces of a multinomial selection against the exact integer cdf, in the order a kernel calls them:
+// clamp_to_window, publish_ratios, StagedTiles::load, multinomial_targets, StagedTiles::store, staged_prefixes, (barrier),
+// staged_ratios, staged_search -- or probe_ancestor per target when the tile's sources span more than kStageTiles tiles.
+// Callers: k_filter_step, the Liu-West stages (lw_select) and, for probe_ancestor, the forecast's start draw (fc_draw_ancestor).
+// A caller says where T'_j and A_j / A'_j live by passing accessors; the pieces know nothing else about it.
+// ---------------------------------------------------------------------------------------
+// Fixed-halo sharding: the source window this rank holds ([win_tile0, win_tile0 + win_tiles) of B tiles) was exchanged BEFORE
+// anyone knew the plan.  If the sources [bb_min, bb_min + span) of this output tile leave it, say so in flag[0] (the host reruns
+// the series on the exact path) and stay inside the buffer for this launch.  flag = null: unchecked.
+__device__ __forceinline__ void clamp_to_window(int32_t* flag, int win_tile0, int win_tiles, int B, int& bb_min, int& span) {
+    if (!flag) return;
+    const int first = win_tile0 > 0 ? win_tile0 : 0, last = win_tile0 + win_tiles - 1 < B - 1 ? win_tile0 + win_tiles - 1 : B - 1;
+    if (bb_min < first || bb_min + span - 1 > last) {
+        if (threadIdx.x == 0) atomicOr(flag, 1);
+        bb_min = bb_min < first ? first : (bb_min > last ? last : bb_min);
+        span = 1;
+    }
+}
+
+// In-LDS level-2: A_b / A'_b (maps a global target into its tile's fixed point) from the entries the threads hold (thread tid:
+// j = e * NT + tid).  Only the staged tiles' ratios are needed, so the IEEE division runs in the one or two waves that hold those
+// entries, off the path to the first barrier (R3[sl]: tile min(bb_min + sl, B - 1)); an output tile spanning more than
+// kStageTiles source tiles (iid resampling, degenerate weights) publishes all of them in R_all and passes a barrier.  R3 is
+// visible after the caller's next barrier.
+template <int NT>
+__device__ __forceinline__ void publish_ratios(const double (&A)[2048 / NT], const double (&Ap)[2048 / NT], int B, int Bpow2, int bb_min,
+                                               int span, double* R3, double* R_all) {
+    constexpr int NE = 2048 / NT;
+    const int tid = threadIdx.x;
+    if (span <= kStageTiles) {
+#pragma unroll
+        for (int e = 0; e < NE; ++e) {
+            if (e * NT < Bpow2) {
+                const int j = e * NT + tid;
+#pragma unroll
+                for (int sl = 0; sl < kStageTiles; ++sl) {
+                    const int bs = bb_min + sl < B ? bb_min + sl : B - 1;
+                    if (j == bs) R3[sl] = A[e] / Ap[e];
+                }
+            }
+        }
+    } else {
+#pragma unroll
+        for (int e = 0; e < NE; ++e) {
+            if (e * NT < Bpow2) {
+                const int j = e * NT + tid;
+                if (j < Bpow2) R_all[j] = (j < B) ? A[e] / Ap[e] : 0.0;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// The (at most) three source cdf tiles of an output tile on their way from memory to LDS, in registers in between so that the
+// spacings' arithmetic hides the loads: thread tid holds pairs k * NT + tid of each tile.  Three explicitly named register
+// tiles (a run-time indexed array would be placed in scratch memory).
+template <int NT, int NK, int TILE>
+struct StagedTiles {
+    double2 stg0[NK], stg1[NK], stg2[NK];
+    // src: the first staged tile (uniform).  Coalesced 16-byte loads at a uniform base (scalar registers) plus a 32-bit lane
+    // offset: no 64-bit address arithmetic per lane.
+    __device__ __forceinline__ void load(const double* src, int span) {
+#pragma unroll
+        for (int k = 0; k < NK; ++k) { stg0[k] = make_double2(0.0, 0.0); stg1[k] = stg0[k]; stg2[k] = stg0[k]; }
+        if (span > kStageTiles) return;
+        const unsigned char* base = reinterpret_cast<const unsigned char*>(src);
+        const uint32_t lane_off = (uint32_t)threadIdx.x * 16u;
+#pragma unroll
+        for (int k = 0; k < NK; ++k) stg0[k] = *reinterpret_cast<const double2*>(base + (lane_off + (uint32_t)(k * NT * 16)));
+        if (span >= 2) {
+#pragma unroll
+            for (int k = 0; k < NK; ++k) stg1[k] = *reinterpret_cast<const double2*>(base + (lane_off + (uint32_t)(TILE * 8 + k * NT * 16)));
+        }
+        if (span >= 3) {
+#pragma unroll
+            for (int k = 0; k < NK; ++k) stg2[k] = *reinterpret_cast<const double2*>(base + (lane_off + (uint32_t)(2 * TILE * 8 + k * NT * 16)));
+        }
+    }
+    // span <= kStageTiles; visible after the caller's next barrier
+    __device__ __forceinline__ void store(double* lds_stage, int span) const {
+        double* dst = lds_stage + threadIdx.x * 2;
+#pragma unroll
+        for (int k = 0; k < NK; ++k) *reinterpret_cast<double2*>(dst + k * NT * 2) = stg0[k];
+        if (span >= 2) {
+#pragma unroll
+            for (int k = 0; k < NK; ++k) *reinterpret_cast<double2*>(dst + TILE + k * NT * 2) = stg1[k];
+        }
+        if (span >= 3) {
+#pragma unroll
+            for (int k = 0; k < NK; ++k) *reinterpret_cast<double2*>(dst + 2 * TILE + k * NT * 2) = stg2[k];
+        }
+    }
+};
+
+// Integer resampling targets in [0, S'] of the multinomial draw (liu_west_filter.h:105-139): sorted uniforms by exponential
+// spacings.  spacings(k, e0, e1): the spacings of particles i_first + (k * NT + tid) * 2 + {0, 1} from the pair's draw words;
+// qE = rne(E 2^35), exact tile scan (one barrier, lds_seg: 16 doubles), target = ceil((pgam + Gamma_b E_cum / E_tile) S'/G) with
+// t_scale = S'/G.  The caller's draw runs INSIDE the per-pair loop: a pair's Philox + log chain then ends at the ragged-tile
+// branch of its own pair; all pairs' chains in one block interleave and cost k_filter_step two VGPRs and a wave per SIMD.
+template <int NT, int NK, int TILE, class EF>
+__device__ __forceinline__ void multinomial_targets(EF spacings, int i_first, int N, double gam, double pgam, double t_scale,
+                                                    double* lds_seg, double (&tau)[NK][2]) {
+    double qe[NK][2], le[NK][2], se;
+#pragma unroll
+    for (int k = 0; k < NK; ++k) {
+        double e0, e1;
+        spacings(k, e0, e1);
+        qe[k][0] = __builtin_rint(e0 * 34359738368.0 /* 2^35 */);
+        qe[k][1] = __builtin_rint(e1 * 34359738368.0);
+        if (i_first + TILE > N) {         // only the last tile of a filter whose N is not a multiple of the tile: a uniform branch
+            asm volatile("");             // (kept a branch: as selects these masks cost every tile 12 instructions per particle pair)
+            const int i0 = i_first + (k * NT + (int)threadIdx.x) * 2;
+            if (!(i0 < N)) qe[k][0] = 0.0;
+            if (!(i0 + 1 < N)) qe[k][1] = 0.0;
+        }
+    }
+    block_scan_f64<NT, NK>(qe, le, se, lds_seg);
+    const double ratio = gam / se;        // per tile: Gamma_b * E_j / sum_tile(E)
+#pragma unroll
+    for (int k = 0; k < NK; ++k) {
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            const double t1 = ratio * le[k][c];
+            const double t2 = pgam + t1;
+            tau[k][c] = __builtin_ceil(t2 * t_scale);
+        }
+    }
+}
+
+// Operands of staged_search for the staged tiles bb_min .. : the prefixes Pm / T0 / T1 from Tof(j) = T'_j (read before the barrier
+// that makes the staged tiles visible, so that their latency is hidden behind it) and the ratios R0..R2 from Rof(j) = A_j / A'_j,
+// a table of the split level-2 (the in-LDS level-2 has them in publish_ratios' R3[0..2] already, read after that barrier).
+template <class TF>
+__device__ __forceinline__ void staged_prefixes(TF Tof, int bb_min, int B, double& Pm, double& T0, double& T1) {
+    T0 = Tof(bb_min);
+    T1 = (bb_min + 1 < B) ? Tof(bb_min + 1) : dinf();
+    Pm = bb_min ? Tof(bb_min - 1) : 0.0;
+}
+template <class RF>
+__device__ __forceinline__ void staged_ratios(RF Rof, int bb_min, int B, double& R0, double& R1, double& R2) {
+    const int b1 = bb_min + 1 < B ? bb_min + 1 : B - 1, b2 = bb_min + 2 < B ? bb_min + 2 : B - 1;
+    R0 = Rof(bb_min); R1 = Rof(b1); R2 = Rof(b2);
+}
+
+// The general search of one target (iid multinomial, an output tile spanning many cdf tiles, the forecast's start draw): source
+// tile b = min(#{j < Bpow2 : Tof(j) < target}, B - 1) (Tof(j) = +inf for B <= j < Bpow2: the caller's accessor says so), tile-local target
+// tloc = ceil((target - T'_{b-1}) A_b / A'_b), j = #{q : cdf_b[q] < tloc} (count_less_pow2: at most tile - 1); returns the
+// ancestor min(b tile + j, N - 1).  cdf_row starts at tile win_tile0.  Probes go to L2.
+template <class TF, class RF>
+__device__ __forceinline__ int probe_ancestor(double target, TF Tof, RF Rof, const double* cdf_row, int B, int Bpow2, int tile,
+                                              int win_tile0, int N) {
+    int bb = count_less_pow2(Bpow2, target, Tof);
+    bb = bb < B - 1 ? bb : B - 1;
+    const double Pb = bb ? Tof(bb - 1) : 0.0;
+    const double tloc = __builtin_ceil((target - Pb) * Rof(bb));
+    const double* tl = cdf_row + (size_t)(bb - win_tile0) * tile;
+    const int j = count_less_pow2(tile, tloc, [&](int q) { return tl[q]; });
+    const int anc = bb * tile + j;
+    return anc < N - 1 ? anc : N - 1;
+}
+
 // 16-byte store of a particle pair.  stream = 1: non-temporal, the lines leave the XCD's L2 as they are written.  A launch
 // whose workgroups are all resident at once ends with every L2 full of dirty lines (2 MB per XCD at N = 2^20), and the
 // write-back at the end of the kernel is then serial time: 15.9 -> 14.3 us per step at N = 2^20.  Grids of several
@@ -770,11 +974,12 @@ __global__ __launch_bounds__(NT) void k_filter_step(const StepArgs a) {
     double l2win_o = 0.0, l2win_t = dinf();
     if (l2ink && need_l2 && sorted && tid < 64 && l2w0 + tid < a.B) { l2win_o = l2of[(l2w0 + tid) >> 10]; l2win_t = l2ts[l2w0 + tid]; }
     if (tid == 0) { lds_cnt[0] = 0; lds_cnt[1] = 0; }
-    double gam = 0.0, pgam = 0.0, pgam_next = 0.0, G = 1.0;
+    double gam = 0.0, pgam = 0.0, pgam_next = 0.0, G = 1.0, u0 = 0.0;
     const bool multinomial = resampled && rsm == RESAMP_MULTINOMIAL;
+    if (resampled) draw_consts(a, rsm, r, rep, G, u0);
     if (multinomial) {
         const size_t gidx = ((size_t)a.gi * a.R + r) * a.B + b;
-        gam = a.gam[gidx]; pgam = a.pgam[gidx]; G = a.gtot[(size_t)a.gi * a.R + r];
+        gam = a.gam[gidx]; pgam = a.pgam[gidx];
         pgam_next = (b + 1 < a.B) ? a.pgam[gidx + 1] : G;
     }
 
@@ -782,15 +987,11 @@ __global__ __launch_bounds__(NT) void k_filter_step(const StepArgs a) {
     PRIO_AT(1);
     // --- level-2: global max, rescaled tile sums A', inclusive prefixes T', total S'; tile range of my targets ---
     double S = 0.0;
-    double t_scale = 0.0, u0 = 0.0;
+    double t_scale = 0.0;
     if (need_l2 && BIG) {
         // split level-2: S', T', A/A' and this tile's source range were computed once per filter by k_level2_plan
         S = a.scal[r].S;
         double t_lo, t_hi;
-        if (rsm == RESAMP_SYSTEMATIC) {
-            const u32x4 ox = philox4x32_10(0u, (uint32_t)a.t, rep, STREAM_RESAMP_EXTRA, key0, key1);
-            u0 = u01_co(ox.v0, ox.v1);
-        }
         tile_target_bounds(rsm, S, a.N, i_first, nvalid, pgam, pgam_next, G, u0, t_scale, t_lo, t_hi);
         if (l2ink && sorted && tid < 64) {
             // lo = #{T'_j < t_lo}, hi = #{T'_j < t_hi}.  T' is nondecreasing, so the window [w0, w0 + 64) gives a count
@@ -854,10 +1055,6 @@ __global__ __launch_bounds__(NT) void k_filter_step(const StepArgs a) {
         STAMP(a, 14);
         // bounds [t_lo, t_hi] of this tile's targets, known to every thread without the spacings
         double t_lo = 0.0, t_hi = dinf();
-        if (rsm == RESAMP_SYSTEMATIC) {
-            const u32x4 ox = philox4x32_10(0u, (uint32_t)a.t, rep, STREAM_RESAMP_EXTRA, key0, key1);
-            u0 = u01_co(ox.v0, ox.v1);
-        }
         tile_target_bounds(rsm, S, a.N, i_first, nvalid, pgam, pgam_next, G, u0, t_scale, t_lo, t_hi);
 #pragma unroll
         for (int e = 0; e < NE; ++e) {
@@ -874,15 +1071,7 @@ __global__ __launch_bounds__(NT) void k_filter_step(const StepArgs a) {
         }
         STAMP(a, 15);
         if (bloc == 0 && tid == 0 && a.finalize_prev) {
-            FilterScalars* sc = a.scal + r;
-            const double Sdd = (S > 0.0) ? dldexp(S, -a.rshift) : dnan();
-            const double lse = m + dlog(Sdd);
-            const double ll = lse - sc->prev;
-            sc->m = m;
-            sc->S = S;
-            sc->last_ll = ll;
-            sc->loglik = sc->loglik + ll;
-            sc->prev = resampled ? a.logN : lse;
+            const double ll = account_step(a.scal + r, m, S, a.rshift, resampled, a.logN);
             if (a.per_step) a.per_step[(size_t)r * a.Tcap + (a.t - 1)] = ll;
         }
     }
@@ -891,10 +1080,7 @@ __global__ __launch_bounds__(NT) void k_filter_step(const StepArgs a) {
 
     // --- request the cdf tiles my targets fall into (coalesced 16-byte loads into registers) ---
     int bb_min = 0, span = kStageTiles + 1;
-    // three explicitly named register tiles (a runtime-indexed array would be placed in scratch memory)
-    double2 stg0[NK], stg1[NK], stg2[NK];
-#pragma unroll
-    for (int k = 0; k < NK; ++k) { stg0[k] = make_double2(0.0, 0.0); stg1[k] = stg0[k]; stg2[k] = stg0[k]; }
+    StagedTiles<NT, NK, TILE> stg;
     const double* cdf_r = a.cdf_in + rowoff;
     const double* xin_r = a.x_in + rowoff;
     if (resampled) {
@@ -908,90 +1094,32 @@ __global__ __launch_bounds__(NT) void k_filter_step(const StepArgs a) {
             bb_min = __builtin_amdgcn_readfirstlane(lo);
             span = __builtin_amdgcn_readfirstlane(hi) - bb_min + 1;
         }
-        if (a.win_flag) {
-            // fixed-halo sharding: the window this rank holds was exchanged BEFORE anyone knew the plan.  If my sources
-            // leave it, say so (the host reruns the series on the exact path) and stay inside the buffer for this launch.
-            const int first = a.win_tile0 > 0 ? a.win_tile0 : 0, last = a.win_tile0 + a.win_tiles - 1 < a.B - 1 ? a.win_tile0 + a.win_tiles - 1 : a.B - 1;
-            if (bb_min < first || bb_min + span - 1 > last) {
-                if (tid == 0) atomicOr(a.win_flag, 1);
-                bb_min = bb_min < first ? first : (bb_min > last ? last : bb_min);
-                span = 1;
-            }
-        }
-        if (!BIG) {
-            // A_b / A'_b (maps a global target into its tile's fixed point).  Only the staged tiles' ratios are needed, so the
-            // IEEE division runs in the one or two waves that hold those entries, off the path to the first barrier; an
-            // output tile spanning more than three source tiles (iid resampling, degenerate weights) publishes all of them.
-            if (span <= kStageTiles) {
-#pragma unroll
-                for (int e = 0; e < NE; ++e) {
-                    if (e * NT < a.Bpow2) {
-                        const int j = e * NT + tid;
-#pragma unroll
-                        for (int sl = 0; sl < kStageTiles; ++sl) {
-                            const int bs = bb_min + sl < a.B ? bb_min + sl : a.B - 1;
-                            if (j == bs) lds_R3[sl] = A2[e] / ApL2[e];
-                        }
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int e = 0; e < NE; ++e) {
-                    if (e * NT < a.Bpow2) {
-                        const int j = e * NT + tid;
-                        if (j < a.Bpow2) lds_R[j] = (j < a.B) ? A2[e] / ApL2[e] : 0.0;
-                    }
-                }
-                __syncthreads();
-            }
-        }
-        if (span <= kStageTiles) {
-            // a uniform base (scalar registers) plus a 32-bit lane offset: no 64-bit address arithmetic per lane
-            const unsigned char* src = reinterpret_cast<const unsigned char*>(cdf_r + (size_t)(bb_min - a.win_tile0) * TILE);
-            const uint32_t lane_off = (uint32_t)tid * 16u;
-#pragma unroll
-            for (int k = 0; k < NK; ++k) stg0[k] = *reinterpret_cast<const double2*>(src + (lane_off + (uint32_t)(k * NT * 16)));
-            if (span >= 2) {
-#pragma unroll
-                for (int k = 0; k < NK; ++k) stg1[k] = *reinterpret_cast<const double2*>(src + (lane_off + (uint32_t)(TILE * 8 + k * NT * 16)));
-            }
-            if (span >= 3) {
-#pragma unroll
-                for (int k = 0; k < NK; ++k) stg2[k] = *reinterpret_cast<const double2*>(src + (lane_off + (uint32_t)(2 * TILE * 8 + k * NT * 16)));
-            }
-        }
+        clamp_to_window(a.win_flag, a.win_tile0, a.win_tiles, a.B, bb_min, span);
+        if (!BIG) publish_ratios<NT>(A2, ApL2, a.B, a.Bpow2, bb_min, span, lds_R3, lds_R);
+        stg.load(cdf_r + (size_t)(bb_min - a.win_tile0) * TILE, span);
     }
     STAMP(a, 3);
     PRIO_AT(3);
 
     // --- exponential spacings of the multinomial resampler (liu_west_filter.h:105-139), exact tile scan;
     //     this arithmetic hides the latency of the tile loads ---
-    double le[NK][2], se = 1.0;
+    double tau[NK][2];                    // integer resampling targets in [0, S']
     uint32_t nw0[NK], nw1[NK];            // words 0-1 of each pair's Philox output: the propagation normals (below)
     if (!resampled) __syncthreads();      // the log table is in LDS (the resampling path has passed a barrier already)
-#pragma unroll
-    for (int k = 0; k < NK; ++k) {
+    auto pair_draw = [&](int k) {
         const u32x4 o = pair_words((uint32_t)(b * (TILE / 2) + k * NT + tid), (uint32_t)a.t, rep, key0, key1);
         nw0[k] = o.v0; nw1[k] = o.v1;
-        if (multinomial) {
-            const int i0 = i_first + (k * NT + tid) * 2;
-            double e0, e1;
-            if (ABL(a, 1)) { e0 = 1.0 + 1e-6 * (double)(i0 & 1023); e1 = 1.0; }
-            else pair_spacings(o, lds_dtab.log, &e0, &e1);
-            le[k][0] = __builtin_rint(e0 * 34359738368.0 /* 2^35 */);
-            le[k][1] = __builtin_rint(e1 * 34359738368.0);
-            if (ragged) {                 // only the last tile of a filter whose N is not a multiple of the tile: a uniform branch
-                asm volatile("");         // (kept a branch: as selects these masks cost every tile 12 instructions per particle pair)
-                if (!(i0 < a.N)) le[k][0] = 0.0;
-                if (!(i0 + 1 < a.N)) le[k][1] = 0.0;
-            }
-        }
-    }
+        return o;
+    };
     if (multinomial) {
-        double qe[NK][2];
+        multinomial_targets<NT, NK, TILE>([&](int k, double& e0, double& e1) {
+            const u32x4 o = pair_draw(k);
+            if (ABL(a, 1)) { e0 = 1.0 + 1e-6 * (double)((i_first + (k * NT + tid) * 2) & 1023); e1 = 1.0; }
+            else pair_spacings(o, lds_dtab.log, &e0, &e1);
+        }, i_first, a.N, gam, pgam, t_scale, lds_seg_a, tau);
+    } else {
 #pragma unroll
-        for (int k = 0; k < NK; ++k) { qe[k][0] = le[k][0]; qe[k][1] = le[k][1]; }
-        block_scan_f64<NT, NK>(qe, le, se, lds_seg_a);
+        for (int k = 0; k < NK; ++k) pair_draw(k);
     }
     STAMP(a, 4);
     PRIO_AT(4);
@@ -1013,56 +1141,38 @@ __global__ __launch_bounds__(NT) void k_filter_step(const StepArgs a) {
             if constexpr (DX > 1) { srcv[k][0] = i_first + (k * NT + tid) * 2; srcv[k][1] = srcv[k][0] + 1; }
         }
     } else {
-        // --- integer resampling targets in [0, S'] ---
-        double tau[NK][2];
-        const double ratio = gam / se;                  // per tile: Gamma_b * E_j / sum_tile(E)
+        // --- the other resamplers' targets ---
+        if (rsm != RESAMP_MULTINOMIAL) {
 #pragma unroll
-        for (int k = 0; k < NK; ++k) {
-            const int i0 = i_first + (k * NT + tid) * 2;
-            if (rsm == RESAMP_MULTINOMIAL) {
-#pragma unroll
-                for (int c = 0; c < 2; ++c) {
-                    const double t1 = ratio * le[k][c];
-                    const double t2 = pgam + t1;
-                    tau[k][c] = __builtin_ceil(t2 * t_scale);
-                }
-            } else if (rsm == RESAMP_SYSTEMATIC) {
-                tau[k][0] = __builtin_ceil(((double)i0 + u0) * t_scale);
-                tau[k][1] = __builtin_ceil(((double)(i0 + 1) + u0) * t_scale);
-            } else {
-                const u32x4 o = philox4x32_10((uint32_t)(i0 >> 1), (uint32_t)a.t, rep, STREAM_RESAMP, key0, key1);
-                const double v0 = u01_co(o.v0, o.v1), v1 = u01_co(o.v2, o.v3);
-                if (rsm == RESAMP_STRATIFIED) {
-                    tau[k][0] = __builtin_ceil(((double)i0 + v0) * t_scale);
-                    tau[k][1] = __builtin_ceil(((double)(i0 + 1) + v1) * t_scale);
+            for (int k = 0; k < NK; ++k) {
+                const int i0 = i_first + (k * NT + tid) * 2;
+                if (rsm == RESAMP_SYSTEMATIC) {
+                    tau[k][0] = __builtin_ceil(((double)i0 + u0) * t_scale);
+                    tau[k][1] = __builtin_ceil(((double)(i0 + 1) + u0) * t_scale);
                 } else {
-                    tau[k][0] = __builtin_ceil(v0 * S);
-                    tau[k][1] = __builtin_ceil(v1 * S);
+                    const u32x4 o = philox4x32_10((uint32_t)(i0 >> 1), (uint32_t)a.t, rep, STREAM_RESAMP, key0, key1);
+                    const double v0 = u01_co(o.v0, o.v1), v1 = u01_co(o.v2, o.v3);
+                    if (rsm == RESAMP_STRATIFIED) {
+                        tau[k][0] = __builtin_ceil(((double)i0 + v0) * t_scale);
+                        tau[k][1] = __builtin_ceil(((double)(i0 + 1) + v1) * t_scale);
+                    } else {
+                        tau[k][0] = __builtin_ceil(v0 * S);
+                        tau[k][1] = __builtin_ceil(v1 * S);
+                    }
                 }
             }
         }
 
+        auto Tof = [&](int j) -> double { return BIG ? l2Tg(j) : lds_T[j]; };                              // j < B
+        auto Tinf = [&](int j) -> double { return BIG ? (j < a.B ? l2Tg(j) : dinf()) : lds_T[j]; };        // lds_T holds +inf beyond B
         if (span <= kStageTiles) {
             // --- staged tiles -> LDS, then count-search in LDS ---
-            {
-                double* dst = lds_stage + tid * 2;
-#pragma unroll
-                for (int k = 0; k < NK; ++k) *reinterpret_cast<double2*>(dst + k * NT * 2) = stg0[k];
-                if (span >= 2) {
-#pragma unroll
-                    for (int k = 0; k < NK; ++k) *reinterpret_cast<double2*>(dst + TILE + k * NT * 2) = stg1[k];
-                }
-                if (span >= 3) {
-#pragma unroll
-                    for (int k = 0; k < NK; ++k) *reinterpret_cast<double2*>(dst + 2 * TILE + k * NT * 2) = stg2[k];
-                }
-            }
-            const int b1 = bb_min + 1 < a.B ? bb_min + 1 : a.B - 1, b2 = bb_min + 2 < a.B ? bb_min + 2 : a.B - 1;
-            const double T0 = BIG ? l2Tg(bb_min) : lds_T[bb_min];
-            const double T1 = (bb_min + 1 < a.B) ? (BIG ? l2Tg(bb_min + 1) : lds_T[bb_min + 1]) : dinf();
-            const double Pm = bb_min ? (BIG ? l2Tg(bb_min - 1) : lds_T[bb_min - 1]) : 0.0;
+            stg.store(lds_stage, span);
+            double Pm, T0, T1, R0, R1, R2;
+            staged_prefixes(Tof, bb_min, a.B, Pm, T0, T1);
             __syncthreads();
-            const double R0 = BIG ? l2R[bb_min] : lds_R3[0], R1 = BIG ? l2R[b1] : lds_R3[1], R2 = BIG ? l2R[b2] : lds_R3[2];
+            if (BIG) staged_ratios([&](int j) { return l2R[j]; }, bb_min, a.B, R0, R1, R2);
+            else { R0 = lds_R3[0]; R1 = lds_R3[1]; R2 = lds_R3[2]; }
             STAMP(a, 5);
             PRIO_AT(5);
             // all 2 NK count-searches of the thread descend together (staged_search)
@@ -1092,15 +1202,8 @@ __global__ __launch_bounds__(NT) void k_filter_step(const StepArgs a) {
             for (int k = 0; k < NK; ++k) {
 #pragma unroll
                 for (int c = 0; c < 2; ++c) {
-                    const double target = tau[k][c];
-                    int bb = count_less_pow2(a.Bpow2, target, [&](int j) { return BIG ? (j < a.B ? l2Tg(j) : dinf()) : lds_T[j]; });
-                    bb = bb < a.B - 1 ? bb : a.B - 1;
-                    const double Pb = bb ? (BIG ? l2Tg(bb - 1) : lds_T[bb - 1]) : 0.0;
-                    const double tloc = __builtin_ceil((target - Pb) * (BIG ? l2R[bb] : lds_R[bb]));
-                    const double* tile = cdf_r + (size_t)(bb - a.win_tile0) * TILE;
-                    const int j = count_less_pow2(TILE, tloc, [&](int q) { return tile[q]; });
-                    int anc = bb * TILE + j;
-                    anc = anc < a.N - 1 ? anc : a.N - 1;
+                    const int anc = probe_ancestor(tau[k][c], Tinf, [&](int j) { return BIG ? l2R[j] : lds_R[j]; }, cdf_r, a.B, a.Bpow2, TILE,
+                                                   a.win_tile0, a.N);
                     const int i = i_first + (k * NT + tid) * 2 + c;
                     if (anc_p && i < a.N) anc_p[rowoff + i - out0] = (uint32_t)anc;
                     xin[k][c] = xin_r[anc - win0];
@@ -1279,16 +1382,7 @@ __global__ __launch_bounds__(NT) void k_filter_step(const StepArgs a) {
                 }
                 level2_scan<NT>(A2, M2, a.B, a.rshift, m2, Ap2, Tinc2, S2, lds_d1, lds_seg_l2, lds_etab);
                 if (tid == 0) {
-                    FilterScalars* sc = a.scal + r;
-                    const bool resample_now = ((a.t + 1) % a.resamp_sched == 0);
-                    const double Sd = (S2 > 0.0) ? dldexp(S2, -a.rshift) : dnan();
-                    const double lse = m2 + dlog(Sd);
-                    const double ll = lse - sc->prev;
-                    sc->m = m2;
-                    sc->S = S2;
-                    sc->last_ll = ll;
-                    sc->loglik = sc->loglik + ll;
-                    sc->prev = resample_now ? a.logN : lse;
+                    const double ll = account_step(a.scal + r, m2, S2, a.rshift, (a.t + 1) % a.resamp_sched == 0, a.logN);
                     if (a.per_step) a.per_step[(size_t)r * a.Tcap + a.t] = ll;
                     if (gridDim.x > 1) __hip_atomic_store(a.ticket + r, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // next launch (kernel boundary orders it)
                     if (a.ll_host) a.ll_host[r] = ll;
@@ -1316,16 +1410,7 @@ __global__ __launch_bounds__(kThreads) void kf_finalize(const StepArgs a) {
     level2_load<kThreads>(a.tsum_in + (size_t)r * a.Bs, a.tmax_in + (size_t)r * a.Bs, a.B, A2, M2);
     level2_scan<kThreads>(A2, M2, a.B, a.rshift, m, Ap, Tinc, S, lds_d, lds_seg, kExpTable);
     if (tid == 0) {
-        FilterScalars* sc = a.scal + r;
-        const bool resample_now = ((a.t + 1) % a.resamp_sched == 0);
-        const double Sd = (S > 0.0) ? dldexp(S, -a.rshift) : dnan();
-        const double lse = m + dlog(Sd);
-        const double ll = lse - sc->prev;
-        sc->m = m;
-        sc->S = S;
-        sc->last_ll = ll;
-        sc->loglik = sc->loglik + ll;
-        sc->prev = resample_now ? a.logN : lse;
+        const double ll = account_step(a.scal + r, m, S, a.rshift, (a.t + 1) % a.resamp_sched == 0, a.logN);
         if (a.per_step) a.per_step[(size_t)r * a.Tcap + a.t] = ll;
         if (a.ll_host) a.ll_host[r] = ll;
     }
@@ -1366,12 +1451,9 @@ __global__ __launch_bounds__(1024) void k_level2_plan(const StepArgs a, int plan
         if (j < a.B) { Areg[k] = ts[j]; Mreg[k] = tm[j]; }
     }
     // global max of the tile maxima, NaN propagating
-    double mx = -dinf();
-    bool nan = false;
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k) {
-        if (k * NT + tid < a.B) { const double v = Mreg[k]; nan = nan || (v != v); mx = (v > mx) ? v : mx; }
-    }
+    double mx;
+    bool nan;
+    reg_max_nanflag<NT, KMAX>(Mreg, a.B, mx, nan);
     const double m = block_max_nanprop<NT>(mx, nan, lds_d);
     // rescaled tile sums and their exact inclusive scan, 1024 tiles per round
     double carry = 0.0;
@@ -1389,11 +1471,7 @@ __global__ __launch_bounds__(1024) void k_level2_plan(const StepArgs a, int plan
             __syncthreads();                                     // lds_seg of the previous round has been read
             if (lane == 63) lds_seg[wave] = inc;
             __syncthreads();
-            double sv = (lane & 15) < NW ? lds_seg[lane & 15] : 0.0;
-            sv = sv + dpp_f64_zero<0x111, 0xF>(sv);
-            sv = sv + dpp_f64_zero<0x112, 0xF>(sv);
-            sv = sv + dpp_f64_zero<0x114, 0xF>(sv);
-            sv = sv + dpp_f64_zero<0x118, 0xF>(sv);
+            const double sv = row16_incl_scan((lane & 15) < NW ? lds_seg[lane & 15] : 0.0);
             const double pre = wave ? readlane_f64(sv, wave - 1) : 0.0;
             const double T = (carry + pre) + inc;
             carry = carry + readlane_f64(sv, 15);
@@ -1404,14 +1482,9 @@ __global__ __launch_bounds__(1024) void k_level2_plan(const StepArgs a, int plan
     const double S = carry;
     __syncthreads();
     if (plan_ranges && resampled && a.resampler != RESAMP_MULTINOMIAL_IID) {
-        const uint32_t key0 = a.keyp[0], key1 = a.keyp[1];
-        double G = 1.0, u0 = 0.0;
+        double G, u0;
+        draw_consts(a, a.resampler, r, rep, G, u0);
         const size_t g0 = ((size_t)a.gi * a.R + r) * a.B;
-        if (a.resampler == RESAMP_MULTINOMIAL) G = a.gtot[(size_t)a.gi * a.R + r];
-        else if (a.resampler == RESAMP_SYSTEMATIC) {
-            const u32x4 ox = philox4x32_10(0u, (uint32_t)a.t, rep, STREAM_RESAMP_EXTRA, key0, key1);
-            u0 = u01_co(ox.v0, ox.v1);
-        }
         // The source-tile range [lo, hi] of every output tile.  The bounds grow with the tile index (t_lo(b) <= t_hi(b),
         // t_lo(b) <= t_lo(b + 1)), so a thread takes CONSECUTIVE tiles and every count after its first starts where the
         // last one ended: a short gallop instead of a log2(B)-level descent (this phase is bound by the LDS traffic of one
@@ -1452,19 +1525,12 @@ __global__ __launch_bounds__(1024) void k_level2_plan(const StepArgs a, int plan
         }
     }
     if (tid == 0) {
-        FilterScalars* sc = a.scal + r;
-        sc->m = m;
-        sc->S = S;
+        // (m, S) of the weights this step starts from: k_filter_step<.., true> and the forecast read them
         if (a.finalize_prev) {
-            const double Sdd = (S > 0.0) ? dldexp(S, -a.rshift) : dnan();
-            const double lse = m + dlog(Sdd);
-            const double ll = lse - sc->prev;
-            sc->last_ll = ll;
-            sc->loglik = sc->loglik + ll;
-            sc->prev = resampled ? a.logN : lse;
+            const double ll = account_step(a.scal + r, m, S, a.rshift, resampled, a.logN);
             if (a.per_step) a.per_step[(size_t)r * a.Tcap + (a.t - 1)] = ll;
             if (a.ll_host) a.ll_host[r] = ll;
-        }
+        } else { a.scal[r].m = m; a.scal[r].S = S; }
     }
 }
 
@@ -1496,23 +1562,16 @@ __global__ __launch_bounds__(1024) void k_l2_scan_blocks(const StepArgs a) {
     const int jo = blk * NT + tid;
     const double A = (jo < a.B) ? ts[jo] : 0.0;
     const double Mo = (jo < a.B) ? tm[jo] : 0.0;
-    double mx = -dinf();
-    bool nan = false;
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k) {
-        if (k * NT + tid < a.B) { const double v = Mreg[k]; nan = nan || (v != v); mx = (v > mx) ? v : mx; }
-    }
+    double mx;
+    bool nan;
+    reg_max_nanflag<NT, KMAX>(Mreg, a.B, mx, nan);
     const double m = block_max_nanprop<NT>(mx, nan, lds_d);
     double Ap = 0.0;
     if (jo < a.B) Ap = __builtin_rint(A * dexp_scaled_t(Mo - m, a.rshift - kTileShift, kExpTable));
     const double inc = wave_incl_scan_f64(Ap);
     if (lane == 63) lds_seg[wave] = inc;
     __syncthreads();
-    double sv = (lane & 15) < NW ? lds_seg[lane & 15] : 0.0;
-    sv = sv + dpp_f64_zero<0x111, 0xF>(sv);
-    sv = sv + dpp_f64_zero<0x112, 0xF>(sv);
-    sv = sv + dpp_f64_zero<0x114, 0xF>(sv);
-    sv = sv + dpp_f64_zero<0x118, 0xF>(sv);
+    const double sv = row16_incl_scan((lane & 15) < NW ? lds_seg[lane & 15] : 0.0);
     const double pre = wave ? readlane_f64(sv, wave - 1) : 0.0;
     double* Tloc = a.l2_work + (size_t)r * a.Bs;
     double* blkv = a.l2_work + (size_t)a.R * a.Bs + (size_t)r * kL2Scratch;
@@ -1540,30 +1599,19 @@ __global__ __launch_bounds__(1024) void k_l2_scan_blocks(const StepArgs a) {
         arrived = __builtin_amdgcn_readfirstlane(arrived);
         if (arrived == nblk - 1) {
             const double v = (lane < nblk) ? __hip_atomic_load(&blkv[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
-            double tinc = v;
-            tinc = tinc + dpp_f64_zero<0x111, 0xF>(tinc);
-            tinc = tinc + dpp_f64_zero<0x112, 0xF>(tinc);
-            tinc = tinc + dpp_f64_zero<0x114, 0xF>(tinc);
-            tinc = tinc + dpp_f64_zero<0x118, 0xF>(tinc);
+            const double tinc = row16_incl_scan(v);
             const double S = readlane_f64(tinc, 15);
             double* off = blkv + kL2Offsets;
             if (lane <= KMAX) off[lane] = (lane < KMAX) ? tinc - v : S;       // exclusive offset of block k (k >= nblk: S')
             if (lane == 0) {
                 __hip_atomic_store(a.l2_ticket + r, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 const bool resampled = (a.t % a.resamp_sched == 0);
-                FilterScalars* sc = a.scal + r;
-                sc->m = m;
-                sc->S = S;
+                // (m, S) of the weights this step starts from: k_filter_step<.., true> and the forecast read them
                 if (a.finalize_prev) {
-                    const double Sdd = (S > 0.0) ? dldexp(S, -a.rshift) : dnan();
-                    const double lse = m + dlog(Sdd);
-                    const double ll = lse - sc->prev;
-                    sc->last_ll = ll;
-                    sc->loglik = sc->loglik + ll;
-                    sc->prev = resampled ? a.logN : lse;
+                    const double ll = account_step(a.scal + r, m, S, a.rshift, resampled, a.logN);
                     if (a.per_step) a.per_step[(size_t)r * a.Tcap + (a.t - 1)] = ll;
                     if (a.ll_host) a.ll_host[r] = ll;
-                }
+                } else { a.scal[r].m = m; a.scal[r].S = S; }
             }
         }
     }
@@ -1605,16 +1653,10 @@ __global__ __launch_bounds__(1024) void k_l2_ranges(const StepArgs a, int plan_r
     __syncthreads();
     const int b = blk * NT + tid;
     if (plan_ranges && resampled && a.resampler != RESAMP_MULTINOMIAL_IID && b < a.B) {
-        const uint32_t key0 = a.keyp[0], key1 = a.keyp[1];
-        double G = 1.0, u0 = 0.0, pg = 0.0, pgn = 0.0;
+        double G, u0, pg = 0.0, pgn = 0.0;
+        draw_consts(a, a.resampler, r, rep, G, u0);
         const size_t g0 = ((size_t)a.gi * a.R + r) * a.B;
-        if (a.resampler == RESAMP_MULTINOMIAL) {
-            G = a.gtot[(size_t)a.gi * a.R + r];
-            pg = a.pgam[g0 + b]; pgn = (b + 1 < a.B) ? a.pgam[g0 + b + 1] : G;
-        } else if (a.resampler == RESAMP_SYSTEMATIC) {
-            const u32x4 ox = philox4x32_10(0u, (uint32_t)a.t, rep, STREAM_RESAMP_EXTRA, key0, key1);
-            u0 = u01_co(ox.v0, ox.v1);
-        }
+        if (a.resampler == RESAMP_MULTINOMIAL) { pg = a.pgam[g0 + b]; pgn = (b + 1 < a.B) ? a.pgam[g0 + b + 1] : G; }
         const int i_first = b * a.tile;
         const int nvalid = (a.N - i_first) < a.tile ? (a.N - i_first) : a.tile;
         double ts_, t_lo, t_hi;
@@ -1628,19 +1670,12 @@ __global__ __launch_bounds__(1024) void k_l2_ranges(const StepArgs a, int plan_r
         a.l2_hi[(size_t)r * a.Bs + b] = hi < a.B - 1 ? hi : a.B - 1;
     }
     if (blk == 0 && tid == 0) {
-        FilterScalars* sc = a.scal + r;
-        sc->m = m;
-        sc->S = S;
+        // (m, S) of the weights this step starts from: k_filter_step<.., true> and the forecast read them
         if (a.finalize_prev) {
-            const double Sdd = (S > 0.0) ? dldexp(S, -a.rshift) : dnan();
-            const double lse = m + dlog(Sdd);
-            const double ll = lse - sc->prev;
-            sc->last_ll = ll;
-            sc->loglik = sc->loglik + ll;
-            sc->prev = resampled ? a.logN : lse;
+            const double ll = account_step(a.scal + r, m, S, a.rshift, resampled, a.logN);
             if (a.per_step) a.per_step[(size_t)r * a.Tcap + (a.t - 1)] = ll;
             if (a.ll_host) a.ll_host[r] = ll;
-        }
+        } else { a.scal[r].m = m; a.scal[r].S = S; }
     }
 }
 
@@ -1670,16 +1705,12 @@ __global__ __launch_bounds__(512) void k_shard_plan(const StepArgs a, int world,
         const int bF = tid * Bl, bL = bF + Bl - 1 < a.B - 1 ? bF + Bl - 1 : a.B - 1;      // Bl = ceil(B / world): the last rank may own fewer
         int lo = 0, hi = a.B - 1;
         if (a.resampler != RESAMP_MULTINOMIAL_IID) {
-            const uint32_t key0 = a.keyp[0], key1 = a.keyp[1];
-            double G = 1.0, pgF = 0.0, pgFn = 0.0, pgL = 0.0, pgLn = 0.0, u0 = 0.0;
+            double G, u0, pgF = 0.0, pgFn = 0.0, pgL = 0.0, pgLn = 0.0;
+            draw_consts(a, a.resampler, 0, a.first_filter, G, u0);          // R = 1
             if (a.resampler == RESAMP_MULTINOMIAL) {
-                const size_t g0 = (size_t)a.gi * a.B;                       // R = 1
-                G = a.gtot[a.gi];
+                const size_t g0 = (size_t)a.gi * a.B;
                 pgF = a.pgam[g0 + bF]; pgFn = (bF + 1 < a.B) ? a.pgam[g0 + bF + 1] : G;
                 pgL = a.pgam[g0 + bL]; pgLn = (bL + 1 < a.B) ? a.pgam[g0 + bL + 1] : G;
-            } else if (a.resampler == RESAMP_SYSTEMATIC) {
-                const u32x4 ox = philox4x32_10(0u, (uint32_t)a.t, a.first_filter, STREAM_RESAMP_EXTRA, key0, key1);
-                u0 = u01_co(ox.v0, ox.v1);
             }
             const int iF = bF * a.tile, iL = bL * a.tile;
             const int nvF = (a.N - iF) < a.tile ? (a.N - iF) : a.tile, nvL = (a.N - iL) < a.tile ? (a.N - iL) : a.tile;

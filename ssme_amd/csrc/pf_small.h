@@ -45,9 +45,7 @@ __device__ __forceinline__ void series_accounting(const StepArgs& a, int r, int 
                                                   double A_prev, double mb_prev) {
     const int tid = threadIdx.x;
     for (int t = tid; t < T; t += NT) {
-        const double m = ms[2 * t], S = ms[2 * t + 1];
-        const double Sd = (S > 0.0) ? dldexp(S, -a.rshift) : dnan();
-        ms[2 * t] = m + dlog(Sd);                     // lse_t
+        ms[2 * t] = lse_of(ms[2 * t], ms[2 * t + 1], a.rshift);      // (m_t, S_t) -> lse_t
     }
     __syncthreads();
     if (tid < 64) {
@@ -174,10 +172,7 @@ __global__ __launch_bounds__(NT) void k_filter_series_small(const StepArgs a, co
             if (a.resampler == RESAMP_MULTINOMIAL) t_scale = S / G;
             else {
                 t_scale = S / (double)a.N;
-                if (a.resampler == RESAMP_SYSTEMATIC) {
-                    const u32x4 ox = philox4x32_10(0u, (uint32_t)t, rep, STREAM_RESAMP_EXTRA, key0, key1);
-                    u0 = u01_co(ox.v0, ox.v1);
-                }
+                if (a.resampler == RESAMP_SYSTEMATIC) u0 = systematic_u0((uint32_t)t, rep, key0, key1);
             }
             const double ratio = gam / se;
 #pragma unroll
@@ -303,11 +298,7 @@ __device__ __forceinline__ void block_scan1_f64(double v, double& incl, double& 
     if constexpr (NSEG == 1) { incl = inc; total = readlane_f64(inc, 63); return; }
     if (lane == 63) lds_seg[wave] = inc;
     __syncthreads();
-    double sv = (lane & 15) < NSEG ? lds_seg[lane & 15] : 0.0;
-    sv = sv + dpp_f64_zero<0x111, 0xF>(sv);
-    sv = sv + dpp_f64_zero<0x112, 0xF>(sv);
-    sv = sv + dpp_f64_zero<0x114, 0xF>(sv);
-    sv = sv + dpp_f64_zero<0x118, 0xF>(sv);
+    const double sv = row16_incl_scan((lane & 15) < NSEG ? lds_seg[lane & 15] : 0.0);
     total = readlane_f64(sv, 15);
     const double pre = wave ? readlane_f64(sv, wave - 1) : 0.0;
     incl = pre + inc;
@@ -324,11 +315,9 @@ __device__ __forceinline__ void block_scan2_f64(double v, double& incl, double& 
     if constexpr (NSEG == 1) { incl = inc; total = readlane_f64(inc, 63); incl_u = incu; total_u = readlane_f64(incu, 63); return; }
     if (lane == 63) { lds_seg[wave] = inc; lds_seg_u[wave] = incu; }
     __syncthreads();
-    double sv = (lane & 15) < NSEG ? lds_seg[lane & 15] : 0.0, su = (lane & 15) < NSEG ? lds_seg_u[lane & 15] : 0.0;
-    sv = sv + dpp_f64_zero<0x111, 0xF>(sv); su = su + dpp_f64_zero<0x111, 0xF>(su);
-    sv = sv + dpp_f64_zero<0x112, 0xF>(sv); su = su + dpp_f64_zero<0x112, 0xF>(su);
-    sv = sv + dpp_f64_zero<0x114, 0xF>(sv); su = su + dpp_f64_zero<0x114, 0xF>(su);
-    sv = sv + dpp_f64_zero<0x118, 0xF>(sv); su = su + dpp_f64_zero<0x118, 0xF>(su);
+    // (two independent chains: the compiler interleaves their DPP steps)
+    const double sv = row16_incl_scan((lane & 15) < NSEG ? lds_seg[lane & 15] : 0.0);
+    const double su = row16_incl_scan((lane & 15) < NSEG ? lds_seg_u[lane & 15] : 0.0);
     total = readlane_f64(sv, 15); total_u = readlane_f64(su, 15);
     incl = (wave ? readlane_f64(sv, wave - 1) : 0.0) + inc;
     incl_u = (wave ? readlane_f64(su, wave - 1) : 0.0) + incu;
@@ -440,8 +429,7 @@ __global__ __launch_bounds__(NT) void k_filter_series_lane(const StepArgs a, con
                 tau = __builtin_ceil(t2 * t_scale);
             } else if (a.resampler == RESAMP_SYSTEMATIC) {
                 const double t_scale = S / (double)a.N;
-                const u32x4 ox = philox4x32_10(0u, (uint32_t)t, rep, STREAM_RESAMP_EXTRA, key0, key1);
-                const double u0 = u01_co(ox.v0, ox.v1);
+                const double u0 = systematic_u0((uint32_t)t, rep, key0, key1);
                 tau = __builtin_ceil(((double)tid + u0) * t_scale);
             } else {
                 const double t_scale = S / (double)a.N;

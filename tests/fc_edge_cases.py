@@ -16,7 +16,7 @@ a NaN tile maximum, every log-weight -inf, carried NaN weights); every other pai
 the number of distinct start ancestors there (the cloud that kept a handful of weights after the 1e3 observation).
 `ratio_nonfinite` = the step after which A / A' holds an inf or NaN (zero-tile on routes of more than one tile).
 
-Liu-West.  Every case of lw_edge_cases.cases() (23 x both forms) in lock-step with oracle.LWFilter, a forecast after every step
+Liu-West.  Every case of lw_edge_cases.cases() (25 x both forms) in lock-step with oracle.LWFilter, a forecast after every step
 (H = 2); mid-path and split-path (587 and 1026 tiles: the first shapes at which k_lw_mom_totals sums many tiles of the forecast's
 own partials, and the split level-2 policy of the filter) after the last step only, H = 1; and nan-y-R3 again with
 first_filter_id = 5.  lw_expect(case): `dead` steps as above; `L_zero` = tril(L) of the forecast's proposal is exactly 0 at every

@@ -40,8 +40,13 @@ def base_cases():
     c.append(_c("one-dim-point", lo_d={1: 0.0}, hi_d={1: 0.0}, expect=dict(nan_steps=(), L_zero_diag=(1,))))
     c.append(_c("mid-path", n=586 * TILE + 1, T=3, y_set={1: 3.0}, z_lag=True, expect=dict(nan_steps=(), path="mid")))
     c.append(_c("split-path", n=1025 * TILE + 1, T=3, y_set={1: 3.0}, z_lag=True, expect=dict(nan_steps=(), path="split")))
+    # an output tile whose sources span more than the three staged tiles, so that lw_select takes the probe search (probe_ancestor)
+    # instead of the staged one: after y = 10 a few dozen particles carry the weight.  wide_span: per form, the draw (k indices of
+    # stage 2 / ancestors of stage 1) and the step at which the oracle's indices prove it
+    c.append(_c("wide-span", n=5 * TILE + 1, T=3, y_set={1: 10.0}, z_lag=True,
+                expect=dict(nan_steps=(), wide_span={0: ("kidx", 1), 1: ("anc", 2)})))
     by = {k["name"]: k for k in c}
-    for name in ("nan-y", "huge-y", "point-prior", "n3"):
+    for name in ("nan-y", "huge-y", "point-prior", "n3", "wide-span"):
         c.append(dict(by[name], name=name + "-forced-split", split=True, same_as=name))
     # per-filter scalars must not leak into each other: the oracle is rep = 0, 1, 2
     c.append(dict(by["nan-y"], name="nan-y-R3", R=3))

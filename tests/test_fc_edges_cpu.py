@@ -98,7 +98,7 @@ def test_the_bootstrap_list_covers_the_issue():
     assert fc.forecast_steps(fc.BENIGN, bc.routes()[4]) == [(t, 2) for t in range(6)]
     assert [fc.last_obs_expect(1, v, 1) for v in fc.LAST_OBS] == ["as-none", "as-none", "finite", "nonfinite", "nonfinite", "nonfinite", "nonfinite"]
     assert {fc.last_obs_expect(0, v, r) for v in fc.LAST_OBS for r in range(3)} == {"as-none"}
-    assert len(LW_CASES) == 2 * 23 + 2 and sum(c["first"] == 5 for c in LW_CASES) == 2
+    assert len(LW_CASES) == 2 * 25 + 2 and sum(c["first"] == 5 for c in LW_CASES) == 2
 
 
 # ---- the Liu-West list --------------------------------------------------------------------------------------------------------------

@@ -5,6 +5,7 @@ oracle's bits on the same list."""
 import numpy as np
 import pytest
 
+import bs_edge_cases as bc
 import lw_edge_cases as lc
 import lw_moments_ref as mr
 
@@ -30,7 +31,7 @@ def test_the_two_large_shapes_lie_in_their_tile_ranges():
     for Bt, fused in ((585, True), (586, False)):
         bpow2 = 1 << (Bt - 1).bit_length()
         assert (Bt * 14 * 8 <= (3 * lc.TILE + 2 * bpow2) * 8) == fused
-    for name in ("nan-y", "huge-y", "point-prior", "n3"):
+    for name in ("nan-y", "huge-y", "point-prior", "n3", "wide-span"):
         assert lc.moment_path(by[name]) == "fused" and lc.moment_path(by[name + "-forced-split"]) == "split"
     lo, hi = lc.POINT, lc.POINT
     assert 0.0 < lo[0] < 1.0 and lo[2] > 0.0 and -1.0 < lo[3] < 1.0 and lo == hi         # inside logit, log and twice-Fisher supports
@@ -77,6 +78,9 @@ def test_case_reaches_its_path_and_the_exact_reference_agrees(oracle, case):
     if "collapsed_after" in exp:
         st = run[exp["collapsed_after"] + 1][1][0]
         assert np.unique(st["anc"]).size == 1 and lc.zero_denominator(run[exp["collapsed_after"]][1][0])
+    if "wide_span" in exp:
+        key, t = exp["wide_span"][case["form"]]
+        assert bc.source_span(run[t][1][0][key], lc.TILE).max() > bc.STAGE_TILES, (key, t)      # the kernel's own span is at least this
     if "distinct_at" in exp:
         t, lo, hi = exp["distinct_at"]
         assert lo <= np.unique(run[t][1][0]["anc"]).size <= hi
