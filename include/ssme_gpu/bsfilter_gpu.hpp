@@ -208,6 +208,78 @@ private:
     std::vector<double> expectations_;
 };
 
+// ---- a model of the user's own WITH COVARIATES (model_api.h: dim_cov) ---------------------------------------------------------------
+// The counterpart of pf::filters::BSFilterWC<nparts, dimx, dimy, dimcov, resampT, float_t> (pswarm_filter.h:309-352): the header
+// compiled into the linked library declares dim_cov = dimcov, and z_t reaches fSamp, logGEv, the first step (q1Samp, logMuEv, logQ1Ev,
+// when the header declares first / first_logw), gSamp and the functionals.  filter(y_t, z_t, fs): fs are functions h(x_t, z_t) of the
+// whole state and the step's covariates, evaluated on the host over the downloaded particles and weights as user_bs_gpu does;
+// functions the header declares are summed on the device: getModelExpectations().  dimx / dimy / dimcov must be the model's.
+template <std::size_t nparts, std::size_t dimx, std::size_t dimy, std::size_t dimcov, typename float_t = double>
+class user_bswc_gpu {
+public:
+    using float_type = float_t;
+    using state_vector = std::array<double, dimx>;
+    using cov_vector = std::array<double, dimcov>;
+    using func = std::function<double(const state_vector&, const cov_vector&)>;
+    explicit user_bswc_gpu(const std::vector<double>& theta, gpu_options o = gpu_options(), unsigned filter_id = auto_filter_id) {
+        std::int32_t dx = 0, dy = 0;
+        check(ssme_pf_user_model_dims(&dx, &dy));                      // SSME_ERR_UNSUPPORTED: the stock library was linked
+        if (dx != (std::int32_t)dimx || dy != (std::int32_t)dimy) throw std::invalid_argument("user_bswc_gpu: dimx / dimy are not the compiled-in model's");
+        if (ssme_pf_user_model_dim_cov() != (int)dimcov) throw std::invalid_argument("user_bswc_gpu: dimcov is not the compiled-in model's dim_cov");
+        h_ = handle(SSME_MODEL_USER0, (int)nparts, 1, o.seed, o.resampler, o.resamp_sched, o.device, detail::resolve_filter_id(filter_id));
+        check(ssme_pf_set_params(h_.get(), theta.data(), (std::int32_t)theta.size(), 1), h_.get());
+    }
+    // filter(obs, cov) / filter(obs, cov, fs): obs[j], j < dimy; cov[j], j < dimcov (an Eigen vector, a std::array, ...)
+    template <typename Osv, typename Csv>
+    void filter(const Osv& yt, const Csv& zt, const std::vector<func>& fs = std::vector<func>()) {
+        double y[dimy];
+        cov_vector z;
+        for (std::size_t j = 0; j < dimy; ++j) y[j] = (double)yt[j];
+        for (std::size_t j = 0; j < dimcov; ++j) z[j] = (double)zt[j];
+        double out = 0.0;
+        check(ssme_pf_step(h_.get(), y, z.data(), &out), h_.get());
+        last_ = (float_t)out;
+        expectations_.assign(fs.size(), 0.0);
+        if (!fs.empty()) {
+            std::vector<double> x(dimx * nparts), w(nparts);
+            check(ssme_pf_download_weights(h_.get(), 0, x.data(), w.data()), h_.get());
+            std::vector<double> num(fs.size(), 0.0);
+            double den = 0.0;
+            for (std::size_t i = 0; i < nparts; ++i) {
+                state_vector xi;
+                for (std::size_t d = 0; d < dimx; ++d) xi[d] = x[d * nparts + i];
+                for (std::size_t k = 0; k < fs.size(); ++k) num[k] += fs[k](xi, z) * w[i];
+                den += w[i];
+            }
+            for (std::size_t k = 0; k < fs.size(); ++k) expectations_[k] = num[k] / den;
+        }
+    }
+    float_t getLogCondLike() const { return last_; }
+    const std::vector<double>& getExpectations() const { return expectations_; }
+    // the n_h functionals the header declares, h(x_t, z_t), after the last filter(), summed on the device
+    std::vector<double> getModelExpectations() const {
+        const int n = ssme_pf_user_model_n_h();
+        if (n < 1) check(SSME_ERR_UNSUPPORTED, h_.get());
+        std::vector<double> out((std::size_t)n);
+        check(ssme_pf_get_user_expectations(h_.get(), out.data()), h_.get());
+        return out;
+    }
+    // sim_future_obs with the exogenous covariates of the horizons, future_covs[k * dimcov + j] (ssme_pf_sim_future_obs_cov):
+    // y[time][component][particle], row-major.  Throws std::invalid_argument when future_covs is not num_steps * dimcov long.
+    std::vector<double> sim_future_obs(unsigned num_steps, const std::vector<double>& future_covs) {
+        if (future_covs.size() != (std::size_t)num_steps * dimcov) throw std::invalid_argument("user_bswc_gpu::sim_future_obs: num_steps * dimcov covariates");
+        std::vector<double> y((std::size_t)num_steps * dimy * nparts);
+        check(ssme_pf_sim_future_obs_cov(h_.get(), (std::int32_t)num_steps, future_covs.data(), y.data(), nullptr, nullptr), h_.get());
+        return y;
+    }
+    ssme_pf_handle native() const { return h_.get(); }
+
+private:
+    handle h_;
+    float_t last_ = 0;
+    std::vector<double> expectations_;
+};
+
 // ---- expectations of host-side functionals ---------------------------------------------------------------------
 // Shared by the swarm-member models below.  h: any callable Mat(const Ssv&) (the covariate, if any, already bound).
 namespace detail {

@@ -119,6 +119,17 @@ int ssme_pf_user_model_dims(int32_t* dim_x, int32_t* dim_y);
 /* 1 when the compiled-in user model declares its observation draw (gsamp, or gsamp_vec for a vector model: ssme_amd/csrc/model_api.h)
  * and SSME_MODEL_USER0 handles can therefore be forecast; 0 for the stock library and for a header without the draw.  Needs no device. */
 int ssme_pf_user_model_has_gsamp(void);
+/* Covariates of SSME_MODEL_USER0 (BSFilterWC<nparts, dimx, dimy, dimcov, ...>): dim_cov of the compiled-in header (1 .. 4;
+ * ssme_amd/csrc/model_api.h), or 0 for the stock library and for a header without dim_cov.  Needs no device.  With dim_cov = K > 0
+ * every z argument of this interface is K values per time step -- ssme_pf_step: K values; ssme_pf_run_series /
+ * ssme_pf_profile_series: z[t * K + j]; NULL means zeros in both -- and every callback of the header (prop, logg, gsamp, their
+ * vector forms, first / first_logw, h) receives the K covariates of its step.  One z_t serves all filters of the handle.  Such a
+ * model is forecast with future covariates (ssme_pf_sim_future_obs_cov; ssme_pf_sim_future_obs is SSME_ERR_UNSUPPORTED) and is
+ * unsharded (ssme_pf_shard_create: SSME_ERR_UNSUPPORTED).  SSME_F32 handles round all K values to float on entry. */
+int ssme_pf_user_model_dim_cov(void);
+/* 1 when the compiled-in header declares a first step of its own (first and first_logw: q1Samp(y1, z1) and
+ * logMuEv(x1, z1) - logQ1Ev(x1, y1, z1) of the reference), 0 otherwise.  Needs no device. */
+int ssme_pf_user_model_has_first(void);
 
 /* UNTRANSFORMED parameters, as the reference's model ctors receive them from
  * pack::get_untrans_params (univ_svol_bootstrap_filter.h:55-61).  theta is
@@ -133,7 +144,8 @@ int ssme_pf_set_seed(ssme_pf_handle h, uint64_t seed);
 int ssme_pf_reset(ssme_pf_handle h);
 
 /* One filter() call on every filter of the handle: BSFilter::filter(y_t) /
- * BSFilterWC::filter(y_t, z_t).  y: 1 value; z: 1 value or NULL.  logcondlike_out (R
+ * BSFilterWC::filter(y_t, z_t).  y: 1 value; z: 1 value or NULL (dim_cov values for a user model
+ * that declares them, ssme_pf_user_model_dim_cov).  logcondlike_out (R
  * values, nullable) receives getLogCondLike() of each filter.  With logcondlike_out = NULL the
  * step is only queued on the handle's stream (the swarm classes: ssme_pf_swarm_aggregate, which
  * follows, hands the data back); every later call on the handle is ordered behind it. */
@@ -238,8 +250,8 @@ int ssme_pf_last_elapsed_ms(ssme_pf_handle h, float* ms);
  * SSME_MODEL_USER0 whose header declares the observation draw (ssme_pf_user_model_has_gsamp; gsamp / gsamp_vec of
  * ssme_amd/csrc/model_api.h): the same start draw gathers all dim_x state planes, then  x <- prop / prop_vec(x, zs, zcov = y_prev[0]),
  * y <- gsamp / gsamp_vec(x, zo),  y_prev <- y: the covariate of a simulated step is component 0 of the previous simulated
- * observation (last_obs at the first horizon), the built-in leverage model's convention; a model with an exogenous covariate cannot
- * be forecast.  Layouts: y_out[((r * num_steps + k) * dim_y + j) * N + i], x_out[((r * num_steps + k) * dim_x + d) * N + i],
+ * observation (last_obs at the first horizon), the built-in leverage model's convention; a header with dim_cov has exogenous
+ * covariates and is forecast by ssme_pf_sim_future_obs_cov (here: SSME_ERR_UNSUPPORTED).  Layouts: y_out[((r * num_steps + k) * dim_y + j) * N + i], x_out[((r * num_steps + k) * dim_x + d) * N + i],
  * start_out[R][N]; with dim = 1 these are the layouts above, and a scalar user model consumes the random numbers a built-in one does.
  * Arguments are validated before any HIP call: NULL handle or y_out, num_steps < 1 or > 65535: SSME_ERR_INVALID_ARG; sharded handles,
  * and SSME_MODEL_USER0 when the compiled-in header declares no observation draw: SSME_ERR_UNSUPPORTED; before the first step:
@@ -247,6 +259,16 @@ int ssme_pf_last_elapsed_ms(ssme_pf_handle h, float* ms);
 int ssme_pf_sim_future_obs(ssme_pf_handle h, int32_t num_steps, const double* last_obs /*R or NULL*/,
                            double* y_out /*[R][num_steps][dim_y][N]*/, double* x_out /*[R][num_steps][dim_x][N] or NULL*/,
                            uint32_t* start_out /*[R][N] or NULL*/);
+/* The forecast of a SSME_MODEL_USER0 handle whose header declares dim_cov = K (ssme_pf_user_model_dim_cov) and the observation
+ * draw: the covariates of horizon k are z_future[k * K + j], exogenous and the same for every filter and particle, and reach both
+ * calls:  x <- prop / prop_vec(x, zs, z_k),  y <- gsamp / gsamp_vec(x, zo, z_k).  The previous simulated observation is not a
+ * covariate here.  Start draw, Philox counters, layouts of y_out / x_out / start_out, the NaN rule, the ordering and "changes nothing
+ * a later call returns" are those of ssme_pf_sim_future_obs.  SSME_F32 handles round z_future on entry.  Validated before any HIP call:
+ * NULL handle, y_out or z_future, num_steps < 1 or > 65535: SSME_ERR_INVALID_ARG; a model without dim_cov, a header without the
+ * draw, a sharded handle: SSME_ERR_UNSUPPORTED; before the first step: SSME_ERR_STATE. */
+int ssme_pf_sim_future_obs_cov(ssme_pf_handle h, int32_t num_steps, const double* z_future /*[num_steps][K]*/,
+                               double* y_out /*[R][num_steps][dim_y][N]*/, double* x_out /*[R][num_steps][dim_x][N] or NULL*/,
+                               uint32_t* start_out /*[R][N] or NULL*/);
 /* HIP-event times (ms) of the last ssme_pf_sim_future_obs: the horizon kernel alone, and the whole call without the download. */
 int ssme_pf_forecast_elapsed_ms(ssme_pf_handle h, float* horizon_kernel_ms, float* call_ms);
 

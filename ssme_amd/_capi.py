@@ -19,12 +19,12 @@ F64, F32 = 0, 1
 H_X, H_X2, H_VOL, H_CONST42 = 0, 1, 2, 3
 
 EXPORTS = [
-    "ssme_pf_create", "ssme_pf_destroy", "ssme_pf_default_tile", "ssme_pf_user_model_n_theta", "ssme_pf_user_model_dims", "ssme_pf_user_model_n_h", "ssme_pf_user_model_has_gsamp", "ssme_pf_get_user_expectations", "ssme_pf_swarm_aggregate_user", "ssme_pf_set_params", "ssme_pf_reset", "ssme_pf_set_seed", "ssme_pf_set_small_series", "ssme_pf_shard_create", "ssme_pf_set_stream",
+    "ssme_pf_create", "ssme_pf_destroy", "ssme_pf_default_tile", "ssme_pf_user_model_n_theta", "ssme_pf_user_model_dims", "ssme_pf_user_model_n_h", "ssme_pf_user_model_has_gsamp", "ssme_pf_user_model_dim_cov", "ssme_pf_user_model_has_first", "ssme_pf_get_user_expectations", "ssme_pf_swarm_aggregate_user", "ssme_pf_set_params", "ssme_pf_reset", "ssme_pf_set_seed", "ssme_pf_set_small_series", "ssme_pf_shard_create", "ssme_pf_set_stream",
     "ssme_pf_shard_prepare", "ssme_shard_comm_get_unique_id", "ssme_shard_comm_init", "ssme_shard_comm_destroy", "ssme_pf_shard_run_series",
     "ssme_pf_shard_download", "ssme_pf_shard_stats", "ssme_pf_shard_layout", "ssme_pf_shard_plan", "ssme_pf_shard_step", "ssme_pf_shard_finalize", "ssme_pf_step",
     "ssme_pf_run_series", "ssme_pf_get_per_step", "ssme_pf_get_loglik", "ssme_pf_get_expectations", "ssme_pf_get_expectations_multi", "ssme_pf_swarm_aggregate", "ssme_pf_swarm_aggregate_threads", "ssme_pf_download_weights", "ssme_pf_get_layout",
     "ssme_pf_log_mean_exp", "ssme_pf_download_state", "ssme_pf_download_scalars", "ssme_pf_set_debug",
-    "ssme_pf_set_graph_mode", "ssme_pf_set_tuning", "ssme_pf_last_elapsed_ms", "ssme_pf_sim_future_obs", "ssme_pf_forecast_elapsed_ms", "ssme_pf_profile_series", "ssme_pf_test_math",
+    "ssme_pf_set_graph_mode", "ssme_pf_set_tuning", "ssme_pf_last_elapsed_ms", "ssme_pf_sim_future_obs", "ssme_pf_sim_future_obs_cov", "ssme_pf_forecast_elapsed_ms", "ssme_pf_profile_series", "ssme_pf_test_math",
     "ssme_pf_test_philox", "ssme_pf_test_quantize", "ssme_pf_test_rescale", "ssme_pf_test_block_scan",
     "ssme_pf_test_copy", "ssme_pf_test_gamma",
     "ssme_pf_strerror", "ssme_pf_last_error",
@@ -105,6 +105,8 @@ def lib():
         L.ssme_pf_user_model_dims.argtypes = [i32p, i32p]
         L.ssme_pf_user_model_n_h.argtypes = []
         L.ssme_pf_user_model_has_gsamp.argtypes = []
+        L.ssme_pf_user_model_dim_cov.argtypes = []
+        L.ssme_pf_user_model_has_first.argtypes = []
         L.ssme_pf_get_user_expectations.argtypes = [H, dp]
         L.ssme_pf_swarm_aggregate_user.argtypes = [H, C.c_int32, dp, dp]
         L.ssme_pf_download_state.argtypes = [H, C.c_int32, dp, dp, u64p, u32p]
@@ -114,6 +116,7 @@ def lib():
         L.ssme_pf_set_tuning.argtypes = [H, C.c_int32]
         L.ssme_pf_last_elapsed_ms.argtypes = [H, C.POINTER(C.c_float)]
         L.ssme_pf_sim_future_obs.argtypes = [H, C.c_int32, dp, dp, dp, u32p]
+        L.ssme_pf_sim_future_obs_cov.argtypes = [H, C.c_int32, dp, dp, dp, u32p]
         L.ssme_pf_forecast_elapsed_ms.argtypes = [H, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         L.ssme_pf_profile_series.argtypes = [H, dp, dp, C.c_int32, dp, i32p]
         L.ssme_pf_test_math.argtypes = [C.c_int32, C.c_int32, dp, dp, C.c_int64]

@@ -53,6 +53,7 @@ struct FcCommon {
 struct FcArgs : FcCommon {
     const ModelConst* mc;      // [R]
     const double* gscale;      // [R] scale of the observation draw: beta (SVOL), 1 (leverage), tau (linear Gaussian)
+    const double* z_future;    // [H][dim_cov] exogenous covariates of the horizons (user models with dim_cov), or null
     int32_t tile;
 };
 
@@ -193,6 +194,8 @@ __global__ __launch_bounds__(kFcNT) void k_fc_horizon(const FcArgs a) {
 // (zs[2c], zo[2c]) and words 2-3 (zs[2c + 1], zo[2c + 1]) by pair_normals.  Only what max(DX, DY) components need is evaluated;
 // members past DX (state) or DY (observation) are dropped, so a scalar model consumes what k_fc_horizon does.
 //   x <- prop_vec(x, zs, y_prev[0]);  y <- gsamp_vec(x, zo);  y_prev <- y.
+// A dim_cov model instead takes the K exogenous covariates of horizon k, z_future[k K + j] (uniform loads), into both calls:
+//   x <- prop_vec(x, zs, z_k);  y <- gsamp_vec(x, zo, z_k);  y_prev is not read.
 // Outputs: y[(r H + k) DY + j][Ns], x[(r H + k) DX + d][Ns], rows of Ns = N rounded up to even doubles, one aligned double2 store
 // per lane, component and horizon; the pad column of an odd N is computed from a zero state and never copied out.  State, y_prev,
 // the model constants and the key stay in registers across the run-time loop (constant indices only: nothing in scratch).
@@ -200,7 +203,7 @@ __global__ __launch_bounds__(kFcNT) void k_fc_horizon(const FcArgs a) {
 // ---------------------------------------------------------------------------------------
 template <class M, int DX, int DY>
 __global__ __launch_bounds__(kFcNT) void k_fc_horizon_user(const FcArgs a, const size_t xplane) {
-    constexpr int DM = DX > DY ? DX : DY;
+    constexpr int DM = DX > DY ? DX : DY, KC = user_cov<M>::k;
     __shared__ __attribute__((aligned(16))) DrawTabs lds_dtab;
     __shared__ __attribute__((aligned(16))) ExpTabEntry lds_etab[SSME_EXP_TABLE_SIZE];
     fc_load_tables(&lds_dtab, lds_etab);
@@ -217,6 +220,11 @@ __global__ __launch_bounds__(kFcNT) void k_fc_horizon_user(const FcArgs a, const
     for (int k = 0; k < a.H; ++k) {
         const uint32_t kk = (uint32_t)k << 8;
         double y[DY][2];
+        CovVals<KC> zc;
+        if constexpr (KC > 0) {
+#pragma unroll
+            for (int j = 0; j < KC; ++j) zc.v[j] = a.z_future[(size_t)k * KC + j];
+        }
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
             double zs[4], zo[4];
@@ -233,8 +241,13 @@ __global__ __launch_bounds__(kFcNT) void k_fc_horizon_user(const FcArgs a, const
             double xi[DX], xn[DX], yv[DY];
 #pragma unroll
             for (int d = 0; d < DX; ++d) xi[d] = x[d][c];
-            user_calls<M>::prop_vec(mc, xi, zs, yp[c], xn, lds_etab);
-            user_calls<M>::gsamp_vec(mc, xn, zo, yv, lds_etab);
+            if constexpr (KC > 0) {
+                user_calls<M>::prop_vec(mc, xi, zs, zc.v, xn, lds_etab);
+                user_calls<M>::gsamp_vec(mc, xn, zo, zc.v, yv, lds_etab);
+            } else {
+                user_calls<M>::prop_vec(mc, xi, zs, yp[c], xn, lds_etab);
+                user_calls<M>::gsamp_vec(mc, xn, zo, yv, lds_etab);
+            }
 #pragma unroll
             for (int d = 0; d < DX; ++d) x[d][c] = xn[d];
 #pragma unroll

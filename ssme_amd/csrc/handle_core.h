@@ -163,11 +163,11 @@ static void release_core(HandleCore* h) {
     if (h->own_stream) hipStreamDestroy(h->own_stream);
 }
 
-// observations (dy values per time index, and z) and per-step terms for T time indices; *moved = true if a buffer moved
-static int ensure_series_buffers(HandleCore* h, int T, int dy, bool* moved) {
+// observations (dy values per time index, and kz covariates) and per-step terms for T time indices; *moved = true if a buffer moved
+static int ensure_series_buffers(HandleCore* h, int T, int dy, bool* moved, int kz = 1) {
     if (T > h->ycap) {
         HIPCHK(own_alloc(h, h->ybuf, sizeof(double) * T * dy));
-        HIPCHK(own_alloc(h, h->zbuf, sizeof(double) * T, Mem::zeroed));
+        HIPCHK(own_alloc(h, h->zbuf, sizeof(double) * T * kz, Mem::zeroed));
         h->ycap = T; *moved = true;
     }
     if (T > h->tcap) {

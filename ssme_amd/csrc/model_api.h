@@ -63,9 +63,43 @@
 // What is excluded is libm (exp, log, pow, sin ...), whose results differ between the two.
 // A simulated step is x <- prop / prop_vec(c, x, zs, zcov = y_prev[0]), y <- gsamp / gsamp_vec(c, x, zo): the covariate of a
 // simulated step is component 0 of the previous simulated observation (fSamp(x, y_prev) of the reference, the built-in leverage
-// model's convention).  A model whose covariate is exogenous cannot be forecast without future covariates; that is not offered.
+// model's convention).  A model whose covariates are exogenous declares dim_cov and is forecast with future covariates (below).
 // A header without the draw compiles and behaves as before (ssme_pf_user_model_has_gsamp reads 0, a forecast is
 // SSME_ERR_UNSUPPORTED).  tests/models/svol_leverage_user.h, svol_two_factor_g.h, lin_gauss_3d_g.h, lin_gauss_4d_g.h declare it.
+//
+// COVARIATES (optional; pf::filters::BSFilterWC<nparts, dimx, dimy, dimcov, ...> of the reference, pswarm_filter.h:309-352: z_t enters
+// fSamp, logGEv, q1Samp, logMuEv, logQ1Ev and the functionals).  A header that declares
+//     static constexpr int dim_cov = K;                            // 1 .. 4 covariates per step
+// opts in: its callbacks keep their names and receive ALL K covariates of the step as `const double* zcov` (constant indices only,
+// like y and x), in every callback, not only in prop:
+//                  without dim_cov                                  with dim_cov
+//     scalar       prop(c, x, zn, double zcov, etab)                prop(c, x, zn, const double* zcov, etab)
+//                  logg(c, y, x, etab)                              logg(c, y, x, const double* zcov, etab)
+//                  gsamp(c, x, zo, etab)                            gsamp(c, x, zo, const double* zcov, etab)
+//     vector       prop_vec(c, x, zn, double zcov, xn, etab)        prop_vec(c, x, zn, const double* zcov, xn, etab)
+//                  logg_vec(c, y, x, etab)                          logg_vec(c, y, x, const double* zcov, etab)
+//                  gsamp_vec(c, x, zo, y, etab)                     gsamp_vec(c, x, zo, const double* zcov, y, etab)
+//     functionals  h(c, x, double zcov, etab, out)                  h(c, x, const double* zcov, etab, out)
+// filter(y_t, z_t) uses the same z_t for fSamp into x_t and for logGEv of y_t, as BSFilterWC::filter does; one z_t serves all filters
+// of a handle; z = NULL means zeros.  Callers pass K values per step (ssme_pf_step) or z[t * K + j] (ssme_pf_run_series); h receives
+// the covariates of the last step.  A scalar dim_cov model of at most 2048 particles still runs the whole series in one launch.
+// FIRST STEP of its own (optional, dim_cov headers only; both or neither -- one without the other is a static_assert):
+//     static __device__ void first(const ssme::ModelConst& c, const double* zn /*dim_x*/, const double* y /*dim_y*/,
+//                                  const double* zcov, double* x0 /*dim_x*/, const ssme::ExpTabEntry* etab);           // q1Samp(y1, z1)
+//     static __device__ double first_logw(const ssme::ModelConst& c, const double* y, const double* x0, const double* zcov,
+//                                         const ssme::ExpTabEntry* etab);                  // logMuEv(x1, z1) - logQ1Ev(x1, y1, z1)
+// At t = 0 the particle is first(...) and its log-weight first_logw(...) + logg(...) (-inf for a `bad` filter, as ever); a2 and
+// init_vec are then not read at t = 0.  The normals are those the first step draws anyway: component 0 the pair's Box-Muller draw,
+// component d >= 1 from stream STREAM_XDIM + d -- no Philox counter changes and every step consumes the random numbers it did.
+// Scalar models use the pointer forms with one element.  A model WITHOUT covariates that wants its own first step declares
+// dim_cov = 1, is run with z = NULL and reads zcov[0] == 0.
+// FORECAST of a dim_cov model: its covariates are exogenous, so the caller supplies those of the horizons
+// (ssme_pf_sim_future_obs_cov: z_future[k * K + j]) and a simulated step is x <- prop / prop_vec(c, x, zs, z_k),
+// y <- gsamp / gsamp_vec(c, x, zo, z_k); the previous simulated observation is NOT a covariate of such a model, and
+// ssme_pf_sim_future_obs is SSME_ERR_UNSUPPORTED for it.  Start draw and counters are those of every forecast.
+// Such models are unsharded.  ssme_pf_user_model_dim_cov / ssme_pf_user_model_has_first report what the header declares;
+// user_bswc_gpu (bsfilter_gpu.hpp) is the BSFilterWC-shaped caller.  tests/models/svol_reg_cov.h (K = 3, first, gsamp, n_h = 3),
+// svol_reg_cov_nofirst.h, svol_leverage_cov1.h (K = 1) and svol_two_factor_cov.h ((dim_x, dim_y, K) = (2, 2, 4)) are the test models.
 #pragma once
 #include <type_traits>
 #include "ssme_math.h"
@@ -118,10 +152,30 @@ template <class M> struct user_gsamp {
                   "a scalar user model declares its observation draw as gsamp, not gsamp_vec");
     static constexpr bool has = vec ? declares_gsamp_vec<M>::value : declares_gsamp<M>::value;
 };
+// COVARIATES (dim_cov above): how many a user model declares, 0 for a header without them
+constexpr int kMaxCov = 4;
+template <class M, class = void> struct user_cov { static constexpr int k = 0; };
+template <class M> struct user_cov<M, std::void_t<decltype(M::dim_cov)>> {
+    static constexpr int k = M::dim_cov;
+    static_assert(k >= 1 && k <= kMaxCov, "dim_cov of a user model: 1 .. 4");
+};
+// does a dim_cov header declare a first step of its own (first AND first_logw above)?
+template <class M, class = void> struct declares_first : std::false_type {};
+template <class M> struct declares_first<M, std::void_t<decltype(&M::first)>> : std::true_type {};
+template <class M, class = void> struct declares_first_logw : std::false_type {};
+template <class M> struct declares_first_logw<M, std::void_t<decltype(&M::first_logw)>> : std::true_type {};
+template <class M> struct user_first {
+    static_assert(declares_first<M>::value == declares_first_logw<M>::value,
+                  "a user model declares both first and first_logw, or neither");
+    static_assert(!declares_first<M>::value || user_cov<M>::k > 0,
+                  "first / first_logw belong to a header that declares dim_cov (dim_cov = 1 for a model without covariates)");
+    static constexpr bool has = declares_first<M>::value && declares_first_logw<M>::value;
+};
 // what the kernels call: a scalar model through its prop / logg, a vector model through its *_vec functions (the other set is a
-// stub that no launch reaches: vector models never run the scalar kernels and the other way round)
-template <class M, bool VEC = (user_dims<M>::dx > 1 || user_dims<M>::dy > 1)> struct user_calls;
-template <class M> struct user_calls<M, false> {
+// stub that no launch reaches: vector models never run the scalar kernels and the other way round).  COV selects the grammar: a
+// header without dim_cov takes one scalar covariate into prop only, one with dim_cov takes `const double* zcov` everywhere.
+template <class M, bool VEC = (user_dims<M>::dx > 1 || user_dims<M>::dy > 1), bool COV = (user_cov<M>::k > 0)> struct user_calls;
+template <class M> struct user_calls<M, false, false> {
     static __device__ __forceinline__ double prop(const ModelConst& c, double x, double zn, double zcov, const ExpTabEntry* etab) { return M::prop(c, x, zn, zcov, etab); }
     static __device__ __forceinline__ double logg(const ModelConst& c, double y, double x, const ExpTabEntry* etab) { return M::logg(c, y, x, etab); }
     static __device__ __forceinline__ void init_vec(const ModelConst& c, const double* zn, double* x0) { x0[0] = zn[0] * c.a2; }
@@ -129,7 +183,7 @@ template <class M> struct user_calls<M, false> {
     static __device__ __forceinline__ double logg_vec(const ModelConst& c, const double* y, const double* x, const ExpTabEntry* etab) { return M::logg(c, y[0], x[0], etab); }
     static __device__ __forceinline__ void gsamp_vec(const ModelConst& c, const double* x, const double* zo, double* y, const ExpTabEntry* etab) { y[0] = M::gsamp(c, x[0], zo[0], etab); }
 };
-template <class M> struct user_calls<M, true> {
+template <class M> struct user_calls<M, true, false> {
     static __device__ __forceinline__ double prop(const ModelConst&, double, double, double, const ExpTabEntry*) { return 0.0; }
     static __device__ __forceinline__ double logg(const ModelConst&, double, double, const ExpTabEntry*) { return 0.0; }
     static __device__ __forceinline__ void init_vec(const ModelConst& c, const double* zn, double* x0) { M::init_vec(c, zn, x0); }
@@ -137,11 +191,57 @@ template <class M> struct user_calls<M, true> {
     static __device__ __forceinline__ double logg_vec(const ModelConst& c, const double* y, const double* x, const ExpTabEntry* etab) { return M::logg_vec(c, y, x, etab); }
     static __device__ __forceinline__ void gsamp_vec(const ModelConst& c, const double* x, const double* zo, double* y, const ExpTabEntry* etab) { M::gsamp_vec(c, x, zo, y, etab); }
 };
+// dim_cov headers: the kernels reach them through the vector forms alone (cov_step / cov_sim below); the scalar-covariate
+// entry points of the other grammar are stubs that no launch of such a model reaches
+template <class M> struct user_calls<M, false, true> {
+    static __device__ __forceinline__ double prop(const ModelConst&, double, double, double, const ExpTabEntry*) { return 0.0; }
+    static __device__ __forceinline__ double logg(const ModelConst&, double, double, const ExpTabEntry*) { return 0.0; }
+    static __device__ __forceinline__ void init_vec(const ModelConst& c, const double* zn, double* x0) { x0[0] = zn[0] * c.a2; }
+    static __device__ __forceinline__ void prop_vec(const ModelConst& c, const double* x, const double* zn, const double* zcov, double* xn, const ExpTabEntry* etab) { xn[0] = M::prop(c, x[0], zn[0], zcov, etab); }
+    static __device__ __forceinline__ double logg_vec(const ModelConst& c, const double* y, const double* x, const double* zcov, const ExpTabEntry* etab) { return M::logg(c, y[0], x[0], zcov, etab); }
+    static __device__ __forceinline__ void gsamp_vec(const ModelConst& c, const double* x, const double* zo, const double* zcov, double* y, const ExpTabEntry* etab) { y[0] = M::gsamp(c, x[0], zo[0], zcov, etab); }
+};
+template <class M> struct user_calls<M, true, true> {
+    static __device__ __forceinline__ double prop(const ModelConst&, double, double, double, const ExpTabEntry*) { return 0.0; }
+    static __device__ __forceinline__ double logg(const ModelConst&, double, double, const ExpTabEntry*) { return 0.0; }
+    static __device__ __forceinline__ void init_vec(const ModelConst& c, const double* zn, double* x0) { M::init_vec(c, zn, x0); }
+    static __device__ __forceinline__ void prop_vec(const ModelConst& c, const double* x, const double* zn, const double* zcov, double* xn, const ExpTabEntry* etab) { M::prop_vec(c, x, zn, zcov, xn, etab); }
+    static __device__ __forceinline__ double logg_vec(const ModelConst& c, const double* y, const double* x, const double* zcov, const ExpTabEntry* etab) { return M::logg_vec(c, y, x, zcov, etab); }
+    static __device__ __forceinline__ void gsamp_vec(const ModelConst& c, const double* x, const double* zo, const double* zcov, double* y, const ExpTabEntry* etab) { M::gsamp_vec(c, x, zo, zcov, y, etab); }
+};
+// One filter step of one particle of a dim_cov model: xn <- first (t = 0, when declared; init_vec / a2 * zn otherwise) or prop,
+// and the increment of its log-weight: [first_logw +] logg, -inf for a `bad` filter.  x, zn, xn: dim_x values; y: dim_y; zcov: dim_cov.
+template <class M>
+__device__ __forceinline__ double cov_step(const ModelConst& c, bool first_step, const double* x, const double* zn, const double* y,
+                                           const double* zcov, double* xn, const ExpTabEntry* etab) {
+    using UC = user_calls<M>;
+    double g;
+    if (first_step) {
+        if constexpr (user_first<M>::has) {
+            M::first(c, zn, y, zcov, xn, etab);
+            g = M::first_logw(c, y, xn, zcov, etab) + UC::logg_vec(c, y, xn, zcov, etab);
+        } else {
+            UC::init_vec(c, zn, xn);
+            g = UC::logg_vec(c, y, xn, zcov, etab);
+        }
+    } else {
+        UC::prop_vec(c, x, zn, zcov, xn, etab);
+        g = UC::logg_vec(c, y, xn, zcov, etab);
+    }
+    return c.bad ? -dinf() : g;
+}
 #if SSME_HAS_USER_MODEL
 template <int MODEL> constexpr int model_dx() { return MODEL == MODEL_USER0 ? user_dims<ssme_user_model0>::dx : 1; }
 template <int MODEL> constexpr int model_dy() { return MODEL == MODEL_USER0 ? user_dims<ssme_user_model0>::dy : 1; }
+template <int MODEL> constexpr int model_kcov() { return MODEL == MODEL_USER0 ? user_cov<ssme_user_model0>::k : 0; }
+// the user model as a type that depends on the kernel's MODEL, so that a discarded `if constexpr` branch is not checked against
+// the other covariate grammar
+template <int MODEL> struct user_model_of { using type = ssme_user_model0; };
 #else
 template <int MODEL> constexpr int model_dx() { return 1; }
 template <int MODEL> constexpr int model_dy() { return 1; }
+template <int MODEL> constexpr int model_kcov() { return 0; }
 #endif
+// the covariates of one step as the kernels hold them: K uniform values (one slot when K = 0, never read)
+template <int K> struct CovVals { double v[K > 0 ? K : 1]; };
 }  // namespace ssme

@@ -42,7 +42,9 @@ struct ssme_pf_s : HandleCore {
     int num_cus;             // compute units of the device (priority schedule of the step kernel)
     int small_series;        // 1: one-tile filters run the whole series in one launch (k_filter_series_small)
     double y_step_v[3];      // step API: components 1 .. of this call's vector observation
+    double z_step_v[3];      // ... and covariates 1 .. of a user model with dim_cov > 1
     int dx, dy;              // state / observation dimension: 1, or the user model's dim_x / dim_y (model_api.h)
+    int kcov, kz;            // dim_cov of the user model (0: none declared) and the covariates per time row of z / zbuf: max(kcov, 1)
     int nt;                  // threads per 2048-particle tile of k_filter_step (256, 512, 1024)
     // C++ shard driver (ssme_pf_shard_run_series): halo buffers [margin | own tiles | margin] x 2048 doubles, ping-pong;
     // this rank's tile sums / maxima, their gathered forms; exact-path window buffers
@@ -58,6 +60,9 @@ struct ssme_pf_s : HandleCore {
     double* wscratch;            // [Npad] weights of one filter (host-side functionals), allocated on first use
     double *uexp_part, *uexp_out;    // the user model's own functionals (user_expect.h): [R][Bs][n_h] per-tile numerators, [n_h][R] values; allocated on first use
     double last_z;               // covariate of the last step (0 when it had none): what the user model's h receives
+    double last_zv[kMaxCov];     // ... all of them, for a header with dim_cov (zeros when the step had none)
+    double* fc_zfut;             // [fc_zfut_cap] future covariates of ssme_pf_sim_future_obs_cov on the device
+    size_t fc_zfut_cap;
     double *gam, *pgam, *gtot;   // Gamma tables of the multinomial resampler, gcap time rows
     uint32_t* anc;
     FilterScalars* scal;
@@ -168,6 +173,14 @@ static void dims_of(int model, int* dx, int* dy) {
 #if SSME_HAS_USER_MODEL
     if (model == SSME_MODEL_USER0) { *dx = user_dims<ssme_user_model0>::dx; *dy = user_dims<ssme_user_model0>::dy; }
 #endif
+}
+// covariates per step a model's callbacks receive as a vector: dim_cov of a compiled-in user model that declares it, else 0
+static int kcov_of(int model) {
+#if SSME_HAS_USER_MODEL
+    if (model == SSME_MODEL_USER0) return user_cov<ssme_user_model0>::k;
+#endif
+    (void)model;
+    return 0;
 }
 static int n_theta_of(int model) {
 #if SSME_HAS_USER_MODEL
@@ -375,6 +388,7 @@ static void enqueue_step(ssme_pf_handle h, int t, int yi, int gi, bool has_z, bo
     if (from_step_staging) {
         a.by_value = 1; a.y_now = h->pin[PinLayout::yz]; a.z_now = has_z ? h->pin[PinLayout::yz + 1] : 0.0;
         for (int d = 1; d < h->dy; ++d) a.y_now_v[d - 1] = h->y_step_v[d - 1];
+        for (int j = 1; j < h->kcov; ++j) a.z_now_v[j - 1] = has_z ? h->z_step_v[j - 1] : 0.0;
         if (!h->split_l2) { a.ticket = h->ticket; a.ll_host = results_to_host ? h->pin_dev + PinLayout::results : nullptr; }     // accounting inside the step kernel (its last workgroup)
     }
     a.per_step = record_per_step ? h->per_step : nullptr;
@@ -427,7 +441,7 @@ static int ensure_gamma_capacity(ssme_pf_handle h, int T) {
 static int ensure_series_capacity(ssme_pf_handle h, int T) {
     const bool grow_small = T > h->tcap && h->B == 1;
     bool moved = false;
-    int rc = ensure_series_buffers(h, T, h->dy, &moved);
+    int rc = ensure_series_buffers(h, T, h->dy, &moved, h->kz);
     if (rc == SSME_OK) rc = ensure_gamma_capacity(h, T);
     if (rc != SSME_OK) return rc;
     if (grow_small) HIPCHK(own_alloc(h, h->small_ms, sizeof(double) * (size_t)T * h->R * 2));
@@ -471,8 +485,10 @@ static int enqueue_user_expectations(ssme_pf_handle h) {
             HIPCHK(own_alloc(h, h->uexp_part, sizeof(double) * (size_t)h->R * h->Bs * NH));
             HIPCHK(own_alloc(h, h->uexp_out, sizeof(double) * (size_t)NH * h->R));
         }
+        CovVals<user_cov<M>::k> zc{};
+        for (int j = 0; j < user_cov<M>::k; ++j) zc.v[j] = h->last_zv[j];
         hipLaunchKernelGGL(k_user_expect_partials<M>, dim3(h->B, h->R), dim3(kThreads), 0, h->stream, (const double*)h->x[h->cur],
-                           (size_t)h->R * h->Npad, (const double*)h->cdf[h->cur], (const ModelConst*)h->mc, h->last_z, h->N, h->Npad, h->Bs,
+                           (size_t)h->R * h->Npad, (const double*)h->cdf[h->cur], (const ModelConst*)h->mc, h->last_z, zc, h->N, h->Npad, h->Bs,
                            h->tile, h->uexp_part);
         hipLaunchKernelGGL(k_user_expect_final<NH>, dim3(h->R), dim3(kThreads), 0, h->stream, (const double*)h->uexp_part,
                            (const double*)h->tsum[h->cur], (const double*)h->tmax[h->cur], h->B, h->Bs, h->R, h->uexp_out);
@@ -562,6 +578,7 @@ static int create_impl(const ssme_pf_config* cfg, int shard_rank, int shard_worl
         int dx = 1, dy = 1;
         dims_of(cfg->model, &dx, &dy);
         if ((dx > 1 || dy > 1) && (shard_world > 0 || cfg->dtype == SSME_F32)) return SSME_ERR_UNSUPPORTED;   // vector models: unsharded, fp64 boundary
+        if (kcov_of(cfg->model) > 0 && shard_world > 0) return SSME_ERR_UNSUPPORTED;                            // dim_cov models: unsharded
     }
     if (cfg->tile_particles != 0 && cfg->tile_particles != kTile && cfg->tile_particles != kTileSmall && cfg->tile_particles != kTileMid) return SSME_ERR_INVALID_ARG;
     if (cfg->n_filters_total < 0 || (cfg->n_filters_total > 0 && cfg->n_filters_total < cfg->n_filters)) return SSME_ERR_INVALID_ARG;
@@ -575,6 +592,8 @@ static int create_impl(const ssme_pf_config* cfg, int shard_rank, int shard_worl
     h->graph_mode = 1;
     h->small_series = 1;
     dims_of(cfg->model, &h->dx, &h->dy);
+    h->kcov = kcov_of(cfg->model);
+    h->kz = h->kcov > 0 ? h->kcov : 1;
     if (h->dx > 1 || h->dy > 1) h->small_series = 0;             // vector models run the tiled step kernel at every N
     with_model(cfg->model, [&](auto m) { h->kern = step_kernels<decltype(m)::value>(tile); });
     h->nt = h->kern.nt;
@@ -661,6 +680,14 @@ int ssme_pf_user_model_n_h(void) {
 #endif
 }
 int ssme_pf_user_model_has_gsamp(void) { return kUserHasGsamp ? 1 : 0; }
+int ssme_pf_user_model_dim_cov(void) { return kcov_of(SSME_MODEL_USER0); }
+int ssme_pf_user_model_has_first(void) {
+#if SSME_HAS_USER_MODEL
+    return user_first<ssme_user_model0>::has ? 1 : 0;
+#else
+    return 0;
+#endif
+}
 int ssme_pf_default_tile(int32_t n_particles, int32_t bank_filters) { return default_tile(n_particles, bank_filters < 1 ? 1 : bank_filters); }
 
 // ---- particle-sharded filter: one filter of cfg->n_particles particles over `world` GPUs ------------------------------
@@ -690,7 +717,7 @@ int ssme_pf_shard_prepare(ssme_pf_handle h, const double* y, const double* z, in
     int rc = ensure_series_capacity(h, T);
     if (rc != SSME_OK) return rc;
     HIPCHK(hipMemcpyAsync(h->ybuf, y, sizeof(double) * T * h->dy, hipMemcpyHostToDevice, h->stream));
-    if (z) HIPCHK(hipMemcpyAsync(h->zbuf, z, sizeof(double) * T, hipMemcpyHostToDevice, h->stream));
+    if (z) HIPCHK(hipMemcpyAsync(h->zbuf, z, sizeof(double) * T * h->kz, hipMemcpyHostToDevice, h->stream));
     h->g_has_z = z != nullptr;
     rc = do_reset(h);
     if (rc != SSME_OK) return rc;
@@ -1036,8 +1063,14 @@ int ssme_pf_step(ssme_pf_handle h, const double* y, const double* z, double* out
     double* const yz = h->pin + PinLayout::yz;
     yz[0] = *y; yz[1] = z ? *z : 0.0;
     for (int d = 1; d < h->dy; ++d) h->y_step_v[d - 1] = y[d];
-    if (h->cfg.dtype == SSME_F32) { yz[0] = f32r(yz[0]); yz[1] = f32r(yz[1]); }
+    for (int j = 1; j < h->kcov; ++j) h->z_step_v[j - 1] = z ? z[j] : 0.0;
+    if (h->cfg.dtype == SSME_F32) {
+        yz[0] = f32r(yz[0]); yz[1] = f32r(yz[1]);
+        for (int j = 1; j < h->kcov; ++j) h->z_step_v[j - 1] = f32r(h->z_step_v[j - 1]);
+    }
     h->last_z = yz[1];
+    h->last_zv[0] = yz[1];
+    for (int j = 1; j < kMaxCov; ++j) h->last_zv[j] = j < h->kcov ? h->z_step_v[j - 1] : 0.0;
     const int gi = h->cfg.resampler == SSME_RESAMP_MULTINOMIAL ? step_gamma_row(h, launch_gamma) : 0;
     // out == NULL (the swarm classes: the aggregation that follows hands the data back): the step is only queued -- no result
     // slots, no wait; anything that reads the handle afterwards is ordered behind it on the stream
@@ -1052,6 +1085,12 @@ int ssme_pf_step(ssme_pf_handle h, const double* y, const double* z, double* out
     if (out) for (int r = 0; r < h->R; ++r) out[r] = res[r];
     round_out(h, out, h->R);
     return SSME_OK;
+}
+
+// the covariates of row T - 1 of a series (kz per row; null: zeros) are what the user model's functionals receive afterwards
+static void set_last_z(ssme_pf_handle h, const double* z, int T) {
+    for (int j = 0; j < kMaxCov; ++j) h->last_zv[j] = (z && j < h->kz) ? z[(size_t)(T - 1) * h->kz + j] : 0.0;
+    h->last_z = h->last_zv[0];
 }
 
 static void enqueue_series(ssme_pf_handle h, int T, bool has_z) {
@@ -1073,11 +1112,11 @@ int ssme_pf_run_series(ssme_pf_handle h, const double* y, const double* z, int32
         y32.resize(T);
         for (int t = 0; t < T; ++t) y32[t] = f32r(y[t]);
         y = y32.data();
-        if (z) { z32.resize(T); for (int t = 0; t < T; ++t) z32[t] = f32r(z[t]); z = z32.data(); }
+        if (z) { z32.resize((size_t)T * h->kz); for (size_t i = 0; i < z32.size(); ++i) z32[i] = f32r(z[i]); z = z32.data(); }
     }
     HIPCHK(hipMemcpyAsync(h->ybuf, y, sizeof(double) * T * h->dy, hipMemcpyHostToDevice, h->stream));
-    if (z) HIPCHK(hipMemcpyAsync(h->zbuf, z, sizeof(double) * T, hipMemcpyHostToDevice, h->stream));
-    h->last_z = z ? z[T - 1] : 0.0;
+    if (z) HIPCHK(hipMemcpyAsync(h->zbuf, z, sizeof(double) * T * h->kz, hipMemcpyHostToDevice, h->stream));
+    set_last_z(h, z, T);
     if (h->cfg.dtype == SSME_F32) HIPCHK(hipStreamSynchronize(h->stream));      // the staging vectors go out of scope
     rc = do_reset(h);
     if (rc != SSME_OK) return rc;
@@ -1324,11 +1363,14 @@ int ssme_pf_get_layout(ssme_pf_handle h, int32_t* tile_particles, int32_t* n_til
 }
 
 // ---- forecast: simulated future observations (forecast.h) -------------------------------------------
-int ssme_pf_sim_future_obs(ssme_pf_handle h, int32_t num_steps, const double* last_obs, double* y_out, double* x_out,
-                           uint32_t* start_out) {
-    if (!h || !y_out || num_steps < 1 || num_steps > kFcMaxSteps) return SSME_ERR_INVALID_ARG;
+// z_future: null (ssme_pf_sim_future_obs: y_prev is the covariate) or [num_steps][dim_cov] exogenous covariates (.._cov)
+static int sim_future_obs_impl(ssme_pf_handle h, int32_t num_steps, const double* last_obs, const double* z_future, bool cov,
+                               double* y_out, double* x_out, uint32_t* start_out) {
+    if (!h || !y_out || num_steps < 1 || num_steps > kFcMaxSteps || (cov && !z_future)) return SSME_ERR_INVALID_ARG;
     if (h->shard_world > 0) { h->err = "forecasts of particle-sharded filters are not implemented"; return SSME_ERR_UNSUPPORTED; }
     const bool user = h->cfg.model == SSME_MODEL_USER0;
+    if (cov && h->kcov == 0) { h->err = "sim_future_obs_cov needs a user model that declares dim_cov (model_api.h)"; return SSME_ERR_UNSUPPORTED; }
+    if (!cov && h->kcov > 0) { h->err = "a dim_cov model is forecast with future covariates: ssme_pf_sim_future_obs_cov"; return SSME_ERR_UNSUPPORTED; }
     if (user && !kUserHasGsamp) { h->err = "this user model declares no observation draw (gsamp / gsamp_vec, model_api.h)"; return SSME_ERR_UNSUPPORTED; }
     if (!h->params_set || h->t < 1) { h->err = "sim_future_obs before the first step"; return SSME_ERR_STATE; }
     const int H = num_steps, R = h->R, N = h->N;
@@ -1340,6 +1382,14 @@ int ssme_pf_sim_future_obs(ssme_pf_handle h, int32_t num_steps, const double* la
     if (rc != SSME_OK) return rc;
     if (!h->fc_gscale) HIPCHK(own_alloc(h, h->fc_gscale, sizeof(double) * R));
     HIPCHK(hipMemcpyAsync(h->fc_gscale, h->h_gscale.data(), sizeof(double) * R, hipMemcpyHostToDevice, h->stream));
+    std::vector<double> zf;                                  // lives until forecast_finish has waited for the stream
+    if (cov) {
+        const size_t nz = (size_t)H * h->kcov;               // what k_fc_horizon_user reads: z_future[k * dim_cov + j], k < H
+        if (nz > h->fc_zfut_cap) { HIPCHK(own_alloc(h, h->fc_zfut, sizeof(double) * nz)); h->fc_zfut_cap = nz; }
+        zf.assign(z_future, z_future + nz);
+        if (h->cfg.dtype == SSME_F32) for (double& v : zf) v = f32r(v);
+        HIPCHK(hipMemcpyAsync(h->fc_zfut, zf.data(), sizeof(double) * nz, hipMemcpyHostToDevice, h->stream));
+    }
     {
         // level-2 of the last step's weights (the weights ssme_pf_get_expectations uses): step_args reads buffers `cur`
         StepArgs p = step_args(h);
@@ -1348,7 +1398,7 @@ int ssme_pf_sim_future_obs(ssme_pf_handle h, int32_t num_steps, const double* la
     }
     FcArgs a{};
     a.x = h->x[h->cur]; a.cdf = h->cdf[h->cur]; a.l2_T = h->fc.T; a.l2_R = h->fc.R; a.scal = h->fc.scal; a.mc = h->mc;
-    a.gscale = h->fc_gscale; a.last_obs = h->fc.last; a.x0 = h->fc.x0; a.start = h->fc.start;
+    a.gscale = h->fc_gscale; a.z_future = cov ? h->fc_zfut : nullptr; a.last_obs = h->fc.last; a.x0 = h->fc.x0; a.start = h->fc.start;
     a.y_out = h->fc.y; a.x_out = x_out ? h->fc.x : nullptr;
     a.keyp = h->keybuf; a.first_filter = h->cfg.first_filter_id;
     a.N = N; a.Npad = h->Npad; a.Ns = (int)Ns; a.B = h->B; a.Bs = h->Bs; a.Bpow2 = h->Bpow2; a.tile = h->tile; a.t0 = h->t; a.H = H;
@@ -1367,6 +1417,16 @@ int ssme_pf_sim_future_obs(ssme_pf_handle h, int32_t num_steps, const double* la
     return SSME_OK;
 }
 
+int ssme_pf_sim_future_obs(ssme_pf_handle h, int32_t num_steps, const double* last_obs, double* y_out, double* x_out,
+                           uint32_t* start_out) {
+    return sim_future_obs_impl(h, num_steps, last_obs, nullptr, false, y_out, x_out, start_out);
+}
+
+int ssme_pf_sim_future_obs_cov(ssme_pf_handle h, int32_t num_steps, const double* z_future, double* y_out, double* x_out,
+                               uint32_t* start_out) {
+    return sim_future_obs_impl(h, num_steps, nullptr, z_future, true, y_out, x_out, start_out);
+}
+
 int ssme_pf_forecast_elapsed_ms(ssme_pf_handle h, float* horizon_kernel_ms, float* call_ms) { return forecast_elapsed(h, horizon_kernel_ms, call_ms); }
 
 int ssme_pf_last_elapsed_ms(ssme_pf_handle h, float* ms) { return elapsed_ms(h, ms); }
@@ -1381,10 +1441,10 @@ int ssme_pf_profile_series(ssme_pf_handle h, const double* y, const double* z, i
     int rc = ensure_series_capacity(h, T);
     if (rc != SSME_OK) return rc;
     HIPCHK(hipMemcpyAsync(h->ybuf, y, sizeof(double) * T * h->dy, hipMemcpyHostToDevice, h->stream));
-    if (z) HIPCHK(hipMemcpyAsync(h->zbuf, z, sizeof(double) * T, hipMemcpyHostToDevice, h->stream));
+    if (z) HIPCHK(hipMemcpyAsync(h->zbuf, z, sizeof(double) * T * h->kz, hipMemcpyHostToDevice, h->stream));
     rc = do_reset(h);
     if (rc != SSME_OK) return rc;
-    h->last_z = z ? z[T - 1] : 0.0;
+    set_last_z(h, z, T);
     // one event every kGroup launches: an event pair around a single 20-us kernel adds ~3 us of its own
     const int kGroup = 32;
     const int nev = (T + kGroup - 1) / kGroup + 1;

@@ -85,6 +85,7 @@ struct StepArgs {
     const double* z;           // [T] or null
     double y_now, z_now;       // step API: the observation and covariate of THIS call travel in the kernel arguments (by_value = 1)
     double y_now_v[3];         // ... components 1 .. 3 of a vector observation (user models with dim_y > 1, model_api.h)
+    double z_now_v[3];         // ... covariates 1 .. 3 of a user model with dim_cov > 1
     size_t xplane;             // user models with dim_x > 1: component d of the particles lives at x_in / x_out + d * xplane
     int32_t by_value;          // 1: use y_now / z_now instead of y[yi] / z[yi] (no upload, no memory read)
     double* ll_host;           // step API: host-mapped buffer that receives the R log conditional likelihoods from the accounting kernel, or null
@@ -929,6 +930,13 @@ __global__ __launch_bounds__(NT) void k_filter_step(const StepArgs a) {
     constexpr bool VEC = DX > 1 || DY > 1;
     const double y = a.by_value ? a.y_now : a.y[(size_t)a.yi * DY];
     const double zcov = a.by_value ? a.z_now : (a.z ? a.z[a.yi] : 0.0);
+    constexpr int KC = model_kcov<MODEL>();                                 // covariates of a dim_cov user model, 0 otherwise
+    CovVals<KC> zc;
+    if constexpr (KC > 0) {
+#pragma unroll
+        for (int j = 0; j < KC; ++j)
+            zc.v[j] = a.by_value ? (j ? a.z_now_v[j > 0 ? j - 1 : 0] : a.z_now) : (a.z ? a.z[(size_t)a.yi * KC + j] : 0.0);
+    }
     const int rsm = HOT ? RS : a.resampler;
     const bool first_step = !HOT && a.t == 0;
     const bool resampled = HOT ? true : ((a.t > 0) && (a.t % a.resamp_sched == 0));
@@ -1259,9 +1267,14 @@ __global__ __launch_bounds__(NT) void k_filter_step(const StepArgs a) {
                 for (int d = 1; d < DX; ++d) xv[d] = first_step ? 0.0 : a.x_in[(size_t)d * a.xplane + rowoff + (size_t)srcv[k][c]];
 #pragma unroll
                 for (int d = 0; d < DX; ++d) zv[d] = znd[d][c];
-                if (first_step) user_calls<ssme_user_model0>::init_vec(mc, zv, xn);
-                else user_calls<ssme_user_model0>::prop_vec(mc, xv, zv, zcov, xn, lds_etab);
-                const double gv = mc.bad ? -dinf() : user_calls<ssme_user_model0>::logg_vec(mc, yv, xn, lds_etab);
+                double gv;
+                if constexpr (KC > 0) gv = cov_step<typename user_model_of<MODEL>::type>(mc, first_step, xv, zv, yv, zc.v, xn, lds_etab);
+                else {
+                    using UC = user_calls<typename user_model_of<MODEL>::type>;
+                    if (first_step) UC::init_vec(mc, zv, xn);
+                    else UC::prop_vec(mc, xv, zv, zcov, xn, lds_etab);
+                    gv = mc.bad ? -dinf() : UC::logg_vec(mc, yv, xn, lds_etab);
+                }
                 xo[c] = xn[0];
 #pragma unroll
                 for (int d = 1; d < DX; ++d) xov[d][c] = xn[d];
@@ -1271,10 +1284,19 @@ __global__ __launch_bounds__(NT) void k_filter_step(const StepArgs a) {
         } else {
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
+            if constexpr (KC > 0) {
+#if SSME_HAS_USER_MODEL
+                double xn;
+                const double gv = cov_step<typename user_model_of<MODEL>::type>(mc, first_step, &xin[k][c], &zn[k][c], &y, zc.v, &xn, lds_etab);
+                xo[c] = xn;
+                lg[k][c] = lw_old[k][c] + gv;
+#endif
+            } else {
             const double xn = first_step ? zn[k][c] * mc.a2 : model_prop<MODEL>(mc, xin[k][c], zn[k][c], zcov, lds_etab);
             const double l = lw_old[k][c] + (ABL(a, 3) ? -0.5 * xn * xn : model_logg<MODEL>(mc, y, xn, lds_etab));
             xo[c] = xn;
             lg[k][c] = l;
+            }
         }
         }
         if (ragged) {                     // particles beyond N: state 0, log-weight -inf (weight 0, no part in the maximum)

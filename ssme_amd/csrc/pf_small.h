@@ -107,14 +107,29 @@ __global__ __launch_bounds__(NT) void k_filter_series_small(const StepArgs a, co
 
     // next step's inputs are requested one step ahead (uniform scalar loads)
     double y_n = a.y[0], z_n = a.z ? a.z[0] : 0.0;
+    constexpr int KC = model_kcov<MODEL>();          // dim_cov user model: K covariates per step, prefetched like the scalar one
+    CovVals<KC> zc_n;
+    if constexpr (KC > 0) {
+#pragma unroll
+        for (int j = 0; j < KC; ++j) zc_n.v[j] = a.z ? a.z[j] : 0.0;
+    }
     double gam_n = 0.0, pgam_n = 0.0, G_n = 1.0;
 
     for (int t = 0; t < T; ++t) {
         const double y = y_n, zcov = z_n;
+        CovVals<KC> zc;
+        if constexpr (KC > 0) zc = zc_n;
         const double gam = gam_n, pgam = pgam_n, G = G_n;
         if (t + 1 < T) {
             y_n = a.y[t + 1];
-            if (a.z) z_n = a.z[t + 1];
+            if constexpr (KC > 0) {
+                if (a.z) {
+#pragma unroll
+                    for (int j = 0; j < KC; ++j) zc_n.v[j] = a.z[(size_t)(t + 1) * KC + j];
+                }
+            } else {
+                if (a.z) z_n = a.z[t + 1];
+            }
             if (multinomial_kind && ((t + 1) % a.resamp_sched == 0)) {
                 const size_t gidx = ((size_t)(t + 1) * a.R + r) * a.B;          // B = 1, tile 0
                 gam_n = a.gam[gidx]; pgam_n = a.pgam[gidx]; G_n = a.gtot[(size_t)(t + 1) * a.R + r];
@@ -222,8 +237,15 @@ __global__ __launch_bounds__(NT) void k_filter_series_small(const StepArgs a, co
             const int i0 = (k * NT + tid) * 2;
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
-                const double xn = (t == 0) ? zn[k][c] * mc.a2 : model_prop<MODEL>(mc, xin[k][c], zn[k][c], zcov, lds_etab);
-                const double l = lw_old[k][c] + model_logg<MODEL>(mc, y, xn, lds_etab);
+                double xn, l;
+                if constexpr (KC > 0) {
+#if SSME_HAS_USER_MODEL
+                    l = lw_old[k][c] + cov_step<typename user_model_of<MODEL>::type>(mc, t == 0, &xin[k][c], &zn[k][c], &y, zc.v, &xn, lds_etab);
+#endif
+                } else {
+                    xn = (t == 0) ? zn[k][c] * mc.a2 : model_prop<MODEL>(mc, xin[k][c], zn[k][c], zcov, lds_etab);
+                    l = lw_old[k][c] + model_logg<MODEL>(mc, y, xn, lds_etab);
+                }
                 const bool valid = (i0 + c) < a.N;
                 xcur[k][c] = valid ? xn : 0.0;
                 lg[k][c] = valid ? l : -dinf();
@@ -368,6 +390,12 @@ __global__ __launch_bounds__(NT) void k_filter_series_lane(const StepArgs a, con
     double xcur = 0.0, lwcur = 0.0;
     double A_prev = 0.0, mb_prev = 0.0;
     double y_n = a.y[0], z_n = a.z ? a.z[0] : 0.0;
+    constexpr int KC = model_kcov<MODEL>();          // dim_cov user model: K covariates per step, prefetched like the scalar one
+    CovVals<KC> zc_n;
+    if constexpr (KC > 0) {
+#pragma unroll
+        for (int j = 0; j < KC; ++j) zc_n.v[j] = a.z ? a.z[j] : 0.0;
+    }
     double gam_n = 0.0, pgam_n = 0.0, G_n = 1.0;
 
     // The draws of a step do not depend on the filter's state, and at one or two waves per SIMD the step is a chain of dependent
@@ -389,11 +417,20 @@ __global__ __launch_bounds__(NT) void k_filter_series_lane(const StepArgs a, con
 
     for (int t = 0; t < T; ++t) {
         const double y = y_n, zcov = z_n;
+        CovVals<KC> zc;
+        if constexpr (KC > 0) zc = zc_n;
         const double gam = gam_n, pgam = pgam_n, G = G_n;
         const double zn = zn_n, le = le_n, se = se_n;
         if (t + 1 < T) {
             y_n = a.y[t + 1];
-            if (a.z) z_n = a.z[t + 1];
+            if constexpr (KC > 0) {
+                if (a.z) {
+#pragma unroll
+                    for (int j = 0; j < KC; ++j) zc_n.v[j] = a.z[(size_t)(t + 1) * KC + j];
+                }
+            } else {
+                if (a.z) z_n = a.z[t + 1];
+            }
             if (multinomial_kind && ((t + 1) % a.resamp_sched == 0)) {
                 const size_t gidx = ((size_t)(t + 1) * a.R + r) * a.B;
                 gam_n = a.gam[gidx]; pgam_n = a.pgam[gidx]; G_n = a.gtot[(size_t)(t + 1) * a.R + r];
@@ -446,8 +483,15 @@ __global__ __launch_bounds__(NT) void k_filter_series_lane(const StepArgs a, con
         }
 
         // --- fSamp / q1Samp, logGEv, tile max ---
-        const double xn = (t == 0) ? zn * mc.a2 : model_prop<MODEL>(mc, xin, zn, zcov, lds_etab);
-        const double l = lw_old + model_logg<MODEL>(mc, y, xn, lds_etab);
+        double xn, l;
+        if constexpr (KC > 0) {
+#if SSME_HAS_USER_MODEL
+            l = lw_old + cov_step<typename user_model_of<MODEL>::type>(mc, t == 0, &xin, &zn, &y, zc.v, &xn, lds_etab);
+#endif
+        } else {
+            xn = (t == 0) ? zn * mc.a2 : model_prop<MODEL>(mc, xin, zn, zcov, lds_etab);
+            l = lw_old + model_logg<MODEL>(mc, y, xn, lds_etab);
+        }
         xcur = valid ? xn : 0.0;
         const double lg = valid ? l : -dinf();
         lwcur = lg;

@@ -21,9 +21,10 @@ namespace ssme {
 
 template <class M>
 __global__ __launch_bounds__(kThreads) void k_user_expect_partials(const double* x, size_t xplane, const double* cdf, const ModelConst* mcs,
-                                                                   double zcov, int N, int Npad, int Bs, int tile,
+                                                                   double zcov, const CovVals<user_cov<M>::k> zc /*dim_cov headers*/,
+                                                                   int N, int Npad, int Bs, int tile,
                                                                    double* part /*[R][Bs][n_h]*/) {
-    constexpr int NH = user_nh<M>::n, DX = user_dims<M>::dx;
+    constexpr int NH = user_nh<M>::n, DX = user_dims<M>::dx, KC = user_cov<M>::k;
     __shared__ ExpTabEntry lds_etab[SSME_EXP_TABLE_SIZE];
     __shared__ double lds[NH][4];
     const int tid = threadIdx.x, b = blockIdx.x, r = blockIdx.y;
@@ -51,14 +52,16 @@ __global__ __launch_bounds__(kThreads) void k_user_expect_partials(const double*
         if (j < nvalid) {
 #pragma unroll
             for (int d = 0; d < DX; ++d) xs[d] = xv[d].x;
-            M::h(mc, xs, zcov, lds_etab, hv);
+            if constexpr (KC > 0) M::h(mc, xs, zc.v, lds_etab, hv);
+            else M::h(mc, xs, zcov, lds_etab, hv);
 #pragma unroll
             for (int k = 0; k < NH; ++k) num[k] = num[k] + hv[k] * q0;
         }
         if (j + 1 < nvalid) {
 #pragma unroll
             for (int d = 0; d < DX; ++d) xs[d] = xv[d].y;
-            M::h(mc, xs, zcov, lds_etab, hv);
+            if constexpr (KC > 0) M::h(mc, xs, zc.v, lds_etab, hv);
+            else M::h(mc, xs, zcov, lds_etab, hv);
 #pragma unroll
             for (int k = 0; k < NH; ++k) num[k] = num[k] + hv[k] * q1;
         }

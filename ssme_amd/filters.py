@@ -16,7 +16,7 @@ from . import _capi as capi
 from ._capi import (MODEL_LIN_GAUSS, MODEL_SVOL, MODEL_SVOL_LEVERAGE, MODEL_USER0, RESAMP_MULTINOMIAL, RESAMP_MULTINOMIAL_IID,
                     RESAMP_STRATIFIED, RESAMP_SYSTEMATIC, SsmeError)
 
-__all__ = ["default_tile", "user_model_has_gsamp", "ParticleFilterBank", "svol_bs", "svol_leverage", "lin_gauss_bs", "log_like_eval", "svol_lw_1_par", "svol_lw_2_par", "SwarmWithCovs", "Swarm", "svol_swarm_1",
+__all__ = ["default_tile", "user_model_has_gsamp", "user_model_dim_cov", "ParticleFilterBank", "svol_bs", "svol_leverage", "lin_gauss_bs", "log_like_eval", "svol_lw_1_par", "svol_lw_2_par", "SwarmWithCovs", "Swarm", "svol_swarm_1",
            "TR_NULL", "TR_TWICE_FISHER", "TR_LOGIT", "TR_LOG",
            "MODEL_SVOL", "MODEL_SVOL_LEVERAGE", "MODEL_LIN_GAUSS", "MODEL_USER0", "RESAMP_MULTINOMIAL", "RESAMP_SYSTEMATIC",
            "RESAMP_STRATIFIED", "RESAMP_MULTINOMIAL_IID", "SsmeError"]
@@ -31,6 +31,12 @@ def user_model_has_gsamp():
     """Does the loaded library's user model declare its observation draw (csrc/model_api.h: gsamp / gsamp_vec), so that
     MODEL_USER0 filters can be forecast (sim_future_obs)?  False for the stock library.  Needs no device."""
     return bool(capi.lib().ssme_pf_user_model_has_gsamp())
+
+
+def user_model_dim_cov():
+    """dim_cov of the loaded library's user model (csrc/model_api.h): the covariates per step that MODEL_USER0 filters take as z
+    (step: K values; run_series: [T, K]) and hand to every callback; 0 for the stock library and headers without it.  Needs no device."""
+    return int(capi.lib().ssme_pf_user_model_dim_cov())
 
 
 def _forecast(chk, fn, h, r, n, H, last_obs, dx=1, dy=1, states=False, start=False, prop=None):
@@ -131,21 +137,37 @@ class ParticleFilterBank:
                 self._dxy = (dx.value, dy.value)
         return self._dxy
 
+    def _kz(self):
+        """Covariates per step: dim_cov of a user model that declares it (user_model_dim_cov), else 1."""
+        if getattr(self, "_kcov", None) is None:
+            self._kcov = user_model_dim_cov() if self.model == capi.MODEL_USER0 else 0
+        return max(self._kcov, 1)
+
+    def _zrows(self, z, T):
+        """z of a series as T rows of _kz() values (None stays None: zeros)."""
+        if z is None:
+            return None
+        zv = capi.as_f64(z)
+        assert zv.size == T * self._kz(), "z: %d values per step for %d steps" % (self._kz(), T)
+        return zv
+
     def step(self, y, z=None):
-        """One filter(y[, z]) on every filter; returns the R log conditional likelihoods.  y: dim_y values."""
+        """One filter(y[, z]) on every filter; returns the R log conditional likelihoods.  y: dim_y values; z: one value, or
+        dim_cov values for a user model that declares them."""
         yv = np.ascontiguousarray(np.ravel(y), dtype=np.float64)
         assert yv.size == self._dims()[1]
-        zv = None if z is None else np.array([z], dtype=np.float64)
+        zv = self._zrows(None if z is None else np.ravel(z), 1)
         out = np.empty(self.r)
         self._chk(capi.lib().ssme_pf_step(self._h, capi.dptr(yv), capi.dptr(zv), capi.dptr(out)))
         return out
 
     def run_series(self, y, z=None):
-        """The log_like_eval loop for all R filters; returns R log-likelihoods.  y: [T], or [T, dim_y] for a vector observation."""
+        """The log_like_eval loop for all R filters; returns R log-likelihoods.  y: [T], or [T, dim_y] for a vector observation;
+        z: [T], or [T, dim_cov] for a user model that declares covariates."""
         yv = capi.as_f64(y)
-        zv = None if z is None else capi.as_f64(z)
         T = yv.size // self._dims()[1]
         assert T * self._dims()[1] == yv.size
+        zv = self._zrows(z, T)
         out = np.empty(self.r)
         self._chk(capi.lib().ssme_pf_run_series(self._h, capi.dptr(yv), capi.dptr(zv), T, capi.dptr(out)))
         self._last_T = T
@@ -205,14 +227,21 @@ class ParticleFilterBank:
         self._chk(capi.lib().ssme_pf_swarm_aggregate_user(self._h, int(num_threads), capi.dptr(ll), capi.dptr(ex)))
         return float(ll[0]), ex
 
-    def sim_future_obs(self, H, last_obs=None, states=False, start=False):
+    def sim_future_obs(self, H, last_obs=None, states=False, start=False, z_future=None):
         """Simulated future observations y[R, H, N] of every filter, on the device (ssme_pf_sim_future_obs: sim_future_obs of the
         reference's *FutureSimulator add-ons; layout "param, time, then state particle", pswarm_filter.h:49-50).  last_obs: the
         last observation, a scalar or one value per filter (the covariate of the first simulated step: read by the leverage model
         and by user models whose prop reads its covariate).  states / start: also return the simulated states x[R, H, N] / the
         ancestors [R, N] of the start draw: y, or (y[, x][, start]).  A user model that declares its observation draw
-        (user_model_has_gsamp) with a vector observation / state returns y[R, H, dim_y, N] / x[R, H, dim_x, N]."""
+        (user_model_has_gsamp) with a vector observation / state returns y[R, H, dim_y, N] / x[R, H, dim_x, N].
+        z_future: [H, dim_cov] exogenous covariates of the horizons, for a user model that declares dim_cov
+        (ssme_pf_sim_future_obs_cov; last_obs is then not read)."""
         dx, dy = self._dims()
+        if z_future is not None:
+            zf = capi.as_f64(z_future)
+            assert zf.size == int(H) * self._kz()
+            fn = lambda h, hh, lo, y, x, st: capi.lib().ssme_pf_sim_future_obs_cov(h, hh, capi.dptr(zf), y, x, st)
+            return _forecast(self._chk, fn, self._h, self.r, self.n, H, None, dx, dy, states, start)
         return _forecast(self._chk, capi.lib().ssme_pf_sim_future_obs, self._h, self.r, self.n, H, last_obs, dx, dy, states, start)
 
     def forecast_elapsed_ms(self):
@@ -251,7 +280,7 @@ class ParticleFilterBank:
     def profile_series(self, y, z=None):
         """Mean launch duration (us) of the step kernel, HIP events on the handle's stream."""
         yv = capi.as_f64(y)
-        zv = None if z is None else capi.as_f64(z)
+        zv = self._zrows(z, yv.size)
         us = np.empty(1)
         cnt = np.zeros(1, dtype=np.int32)
         self._chk(capi.lib().ssme_pf_profile_series(self._h, capi.dptr(yv), capi.dptr(zv), yv.size, capi.dptr(us),
