@@ -254,9 +254,11 @@ class UserModelFilter:
 class UserVectorModelFilter:
     """The same for a user model with a VECTOR state / observation (model_api.h: dim_x, dim_y <= 4).  Callbacks on numpy views:
     init(zn[dx]) -> x0[dx];  prop(x[dx], zn[dx], zcov) -> x'[dx];  logg(y[dy], x[dx]) -> log g.  Component 0 of the normals is the
-    pair's draw of the scalar filter, component d >= 1 one more Philox call per pair on counter stream 96 + d."""
+    pair's draw of the scalar filter, component d >= 1 one more Philox call per pair on counter stream 96 + d.
+    raw = True: the callbacks get the C double pointers themselves (index them; no numpy view per call) and write their result:
+    init(zn, x0), prop(x, zn, zcov, xn), logg(y, x) -> log g -- for tests that make millions of calls."""
 
-    def __init__(self, n, seed, dx, dy, init, prop, logg, rep=0, resampler=RESAMP_MULTINOMIAL, resamp_sched=1, tile=None, bad=False):
+    def __init__(self, n, seed, dx, dy, init, prop, logg, rep=0, resampler=RESAMP_MULTINOMIAL, resamp_sched=1, tile=None, bad=False, raw=False):
         self.n, self.dx, self.dy = int(n), int(dx), int(dy)
         self.tile = default_tile(self.n) if tile is None else int(tile)
         self.nt = (self.n + self.tile - 1) // self.tile
@@ -273,6 +275,8 @@ class UserVectorModelFilter:
         def _logg(y, x):
             return float(logg(arr(y, self.dy), arr(x, self.dx)))
 
+        if raw:
+            _init, _prop, _logg = init, prop, logg
         self._cb = (C.CFUNCTYPE(None, dp, dp)(_init), C.CFUNCTYPE(None, dp, dp, C.c_double, dp)(_prop), C.CFUNCTYPE(C.c_double, dp, dp)(_logg))
         L.orc_pf_create_user_vec.restype = C.c_void_p
         L.orc_pf_create_user_vec.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.c_int,
@@ -280,6 +284,8 @@ class UserVectorModelFilter:
         L.orc_pf_run_series_vec.restype = C.c_double
         L.orc_pf_run_series_vec.argtypes = [C.c_void_p, dp, dp, C.c_int, dp]
         L.orc_pf_state_dim.argtypes = [C.c_void_p, C.c_int, dp]
+        L.orc_pf_step_vec.restype = C.c_double
+        L.orc_pf_step_vec.argtypes = [C.c_void_p, dp, C.c_double]
         self._h = L.orc_pf_create_user_vec(self.n, resampler, resamp_sched, seed, rep, self.dx, self.dy, int(bool(bad)),
                                            C.cast(self._cb[0], C.c_void_p), C.cast(self._cb[1], C.c_void_p), C.cast(self._cb[2], C.c_void_p),
                                            self.tile)
@@ -296,6 +302,19 @@ class UserVectorModelFilter:
         per = np.empty(T)
         ll = lib().orc_pf_run_series_vec(self._h, _dp(y), _dp(z), T, _dp(per))
         return ll, per
+
+    def step(self, y, z=0.0):
+        """One step (y: dy values), continuing from the last; reset() starts over.  For tests that compare the state after every step."""
+        y = np.ascontiguousarray(np.ravel(y), dtype=np.float64)
+        assert y.size == self.dy
+        return lib().orc_pf_step_vec(self._h, _dp(y), float(z))
+
+    def reset(self):
+        lib().orc_pf_reset(self._h)
+
+    @property
+    def loglik(self):
+        return lib().orc_pf_loglik(self._h)
 
     def state(self):
         """x: [dx, n] (component 0 first), cdf, ancestors, ... as Filter.state()."""

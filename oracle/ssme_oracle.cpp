@@ -1243,6 +1243,8 @@ double orc_pf_run_series_vec(void* h, const double* y, const double* z, int T, d
     for (int t = 0; t < T; ++t) { const double l = f->step_vec(y + (size_t)t * f->mc.dy, z ? z[t] : 0.0); if (per_step) per_step[t] = l; }
     return f->loglik;
 }
+// one step of the same filter (y: dy values), for callers that look at the state after every step; orc_pf_reset starts over
+double orc_pf_step_vec(void* h, const double* y, double z) { return ((Filter*)h)->step_vec(y, z); }
 // component d (1 .. dx-1) of the particles after the last step (component 0: orc_pf_state)
 void orc_pf_state_dim(void* h, int d, double* x) { Filter* f = (Filter*)h; std::memcpy(x, f->xv[d].data(), sizeof(double) * f->N); }
 void orc_pf_destroy(void* h) { delete (Filter*)h; }
