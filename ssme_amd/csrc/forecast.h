@@ -221,10 +221,7 @@ __global__ __launch_bounds__(kFcNT) void k_fc_horizon_user(const FcArgs a, const
         const uint32_t kk = (uint32_t)k << 8;
         double y[DY][2];
         CovVals<KC> zc;
-        if constexpr (KC > 0) {
-#pragma unroll
-            for (int j = 0; j < KC; ++j) zc.v[j] = a.z_future[(size_t)k * KC + j];
-        }
+        if constexpr (KC > 0) zc.load(a.z_future, (size_t)k);
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
             double zs[4], zo[4];

@@ -242,6 +242,13 @@ template <int MODEL> constexpr int model_dx() { return 1; }
 template <int MODEL> constexpr int model_dy() { return 1; }
 template <int MODEL> constexpr int model_kcov() { return 0; }
 #endif
-// the covariates of one step as the kernels hold them: K uniform values (one slot when K = 0, never read)
-template <int K> struct CovVals { double v[K > 0 ? K : 1]; };
+// the covariates of one step as the kernels hold them: KC uniform values (one slot when KC = 0, never read)
+template <int KC> struct CovVals {
+    double v[KC > 0 ? KC : 1];
+    // row `row` of the covariates z[rows][KC] of a series
+    __device__ __forceinline__ void load(const double* z, size_t row) {
+#pragma unroll
+        for (int j = 0; j < KC; ++j) v[j] = z[row * KC + j];
+    }
+};
 }  // namespace ssme

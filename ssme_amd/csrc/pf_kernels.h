@@ -329,6 +329,24 @@ __device__ __forceinline__ double model_logg(const ModelConst& c, double y, doub
     return v;
 }
 
+// One filter step of one scalar particle: *xn <- a2 * zn at the first step (a dim_cov user model: its own first / init), else the
+// proposal from x; returns log g(y | *xn), the increment of the particle's log-weight.  zcov: the scalar covariate of the step,
+// zc: the KC covariates of a dim_cov user model (the model reads one of the two).
+template <int MODEL>
+__device__ __forceinline__ double scalar_step(const ModelConst& c, bool first_step, double x, double zn, double y, double zcov,
+                                              const CovVals<model_kcov<MODEL>()>& zc, double* xn, const ExpTabEntry* etab) {
+    if constexpr (model_kcov<MODEL>() > 0) {
+#if SSME_HAS_USER_MODEL
+        return cov_step<typename user_model_of<MODEL>::type>(c, first_step, &x, &zn, &y, zc.v, xn, etab);
+#else
+        return 0.0;      // no model has covariates of its own without a user model: never instantiated
+#endif
+    } else {
+        *xn = first_step ? zn * c.a2 : model_prop<MODEL>(c, x, zn, zcov, etab);
+        return model_logg<MODEL>(c, y, *xn, etab);
+    }
+}
+
 // two standard normals for the pair `pair` at time t (Box-Muller)
 __device__ __forceinline__ void normal_pair(uint32_t pair, uint32_t t, uint32_t rep, uint32_t k0, uint32_t k1,
                                             double* z0, double* z1) {
@@ -1284,19 +1302,13 @@ __global__ __launch_bounds__(NT) void k_filter_step(const StepArgs a) {
         } else {
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
-            if constexpr (KC > 0) {
-#if SSME_HAS_USER_MODEL
-                double xn;
-                const double gv = cov_step<typename user_model_of<MODEL>::type>(mc, first_step, &xin[k][c], &zn[k][c], &y, zc.v, &xn, lds_etab);
-                xo[c] = xn;
-                lg[k][c] = lw_old[k][c] + gv;
-#endif
-            } else {
-            const double xn = first_step ? zn[k][c] * mc.a2 : model_prop<MODEL>(mc, xin[k][c], zn[k][c], zcov, lds_etab);
-            const double l = lw_old[k][c] + (ABL(a, 3) ? -0.5 * xn * xn : model_logg<MODEL>(mc, y, xn, lds_etab));
+            double xn, gv;
+            if (KC == 0 && ABL(a, 3)) {       // diagnostic build: the proposal alone and a stand-in for log g
+                xn = first_step ? zn[k][c] * mc.a2 : model_prop<MODEL>(mc, xin[k][c], zn[k][c], zcov, lds_etab);
+                gv = -0.5 * xn * xn;
+            } else gv = scalar_step<MODEL>(mc, first_step, xin[k][c], zn[k][c], y, zcov, zc, &xn, lds_etab);
             xo[c] = xn;
-            lg[k][c] = l;
-            }
+            lg[k][c] = lw_old[k][c] + gv;
         }
         }
         if (ragged) {                     // particles beyond N: state 0, log-weight -inf (weight 0, no part in the maximum)

@@ -9,47 +9,154 @@
 // paths are bit-identical (tests/test_parity_gpu.py::test_small_series_kernel_*); the oracle does not
 // distinguish them.  Used by ssme_pf_run_series when the filter has one tile (the shipped example's
 // N = 500, example/main.cpp:9) -- the step API and multi-tile filters use k_filter_step.
+//
+// Two kernels, one particle pair per lane (k_filter_series_small) and one particle per lane (k_filter_series_lane), built
+// from the same pieces: a step is prefetch (SeriesInputs), level-2 (one_tile_level2), draws, targets (target_of), search
+// (count_less_radix8) and gather, model step (scalar_step), maximum, weights and scan, publish; after the loop
+// series_accounting and hand_over_state.
 #pragma once
 #include "pf_kernels.h"
 
 namespace ssme {
 
-// min(#{ j < P : tile[j] < target }, P-1) for two targets at once by a radix-8 descent: the probes of one level are
-// independent loads, so a search costs log8(P) dependent LDS round trips instead of log2(P) -- this kernel runs one
-// wave per SIMD and is bound by dependent latency, not by issue slots.  Same count as count_less_pow2 (monotone tile).
-template <int P>
-__device__ __forceinline__ void count_less_radix8_x2(const double* tile, double t0, double t1, int& j0, int& j1) {
-    int p0 = 0, p1 = 0;
+// The inputs of a step that do not depend on the filter's state, requested one step ahead (uniform scalar loads).
+template <int KC>
+struct SeriesInputs {
+    double y, z;                 // observation; scalar covariate (0 without one)
+    CovVals<KC> zc;              // dim_cov user model: its KC covariates take the scalar one's place
+    double gam, pgam, G;         // sorted-multinomial resampling steps: Gamma of tile 0, the prefix before it, the total (B = 1)
+
+    __device__ __forceinline__ void load_row(const StepArgs& a, int r, int row) {
+        y = a.y[row];
+        if (a.z) {                   // a series without covariates keeps the zeros of load_first
+            if constexpr (KC > 0) zc.load(a.z, (size_t)row);
+            else z = a.z[row];
+        }
+        if (a.resampler == RESAMP_MULTINOMIAL && row > 0 && row % a.resamp_sched == 0) {
+            const size_t g = (size_t)row * a.R + r;
+            gam = a.gam[g * a.B]; pgam = a.pgam[g * a.B]; G = a.gtot[g];
+        }
+    }
+    __device__ __forceinline__ void load_first(const StepArgs& a, int r) {
+        z = 0.0; gam = 0.0; pgam = 0.0; G = 1.0;
+#pragma unroll
+        for (int j = 0; j < KC; ++j) zc.v[j] = 0.0;
+        load_row(a, r, 0);
+    }
+    // Row `row` of a series of T, requested by the step before it.  (The step copies the struct and then calls this: a
+    // member that returned the copy cost the lane kernel 11 VGPRs and a wave per SIMD.)
+    __device__ __forceinline__ void request(const StepArgs& a, int r, int row, int T) {
+        if (row < T) load_row(a, r, row);
+    }
+};
+
+// Level-2 of a filter of one tile (level2_scan for B = 1) from the previous step's tile sum and maximum: m, S = A' and
+// R0 = A / A'.  Thread 0 records (m, S) at ms_t; the logarithm is taken after the loop (series_accounting).
+// One tile: m_b - m is +0 unless the max is NaN or infinite, and the shift is 0 (Npad = 2048); exp(0) 2^0 = 1 exactly
+// (dexp_scaled_t: n = 0, r = 0, table entry (1, 0)), so the shortcut gives the bits of the full form wherever it is taken.
+struct Level2 { double m, S, R0; };
+__device__ __forceinline__ Level2 one_tile_level2(double A_prev, double mb_prev, int rshift, const ExpTabEntry* etab, double* ms_t) {
+    Level2 l;
+    l.m = (mb_prev != mb_prev) ? dnan() : mb_prev;
+    const double dm = mb_prev - l.m;
+    const int sh = rshift - kTileShift;
+    l.S = (dm == 0.0 && sh == 0) ? __builtin_rint(A_prev) : __builtin_rint(A_prev * dexp_scaled_t(dm, sh, etab));
+    l.R0 = A_prev / l.S;
+    if (threadIdx.x == 0) { ms_t[0] = l.m; ms_t[1] = l.S; }
+    return l;
+}
+
+// Integer resampling target of particle i under the systematic, stratified and iid-multinomial resamplers (the sorted
+// multinomial one comes from the scanned spacings).  u0: the step's systematic offset; v: the particle's own uniform
+// (stratified, iid), drawn by the caller; t_scale = S / N.  k_filter_step forms the same targets pair by pair.
+__device__ __forceinline__ double target_of(int resampler, int i, double v, double u0, double t_scale, double S) {
+    if (resampler == RESAMP_SYSTEMATIC) return __builtin_ceil(((double)i + u0) * t_scale);
+    if (resampler == RESAMP_STRATIFIED) return __builtin_ceil(((double)i + v) * t_scale);
+    return __builtin_ceil(v * S);
+}
+
+// j[q] = min(#{ i < P : tile[i] < target[q] }, P-1) for NQ targets at once by a radix-8 descent: the probes of one level, of
+// all queries, are independent loads, so a search costs log8(P) dependent LDS round trips instead of log2(P) -- these kernels
+// run one or two waves per SIMD and are bound by dependent latency, not by issue slots.  Same count as count_less_pow2
+// (monotone tile).
+template <int P, int NQ>
+__device__ __forceinline__ void count_less_radix8(const double* tile, const double (&target)[NQ], int (&j)[NQ]) {
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) j[q] = 0;
 #pragma unroll
     for (int w = P; w > 1;) {
         const int radix = (w >= 8) ? 8 : w;          // P is a power of two: the last level may be radix 2 or 4
         const int s = w / radix;
-        int c0 = 0, c1 = 0;
+        int c[NQ];
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) c[q] = 0;
 #pragma unroll
         for (int k = 1; k < radix; ++k) {
-            c0 += (tile[p0 + k * s - 1] < t0) ? 1 : 0;
-            c1 += (tile[p1 + k * s - 1] < t1) ? 1 : 0;
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) c[q] += (tile[j[q] + k * s - 1] < target[q]) ? 1 : 0;
         }
-        p0 += c0 * s; p1 += c1 * s;
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) j[q] += c[q] * s;
         w = s;
     }
-    j0 = p0; j1 = p1;
 }
 
-// Log conditional likelihoods of a whole series outside the time loop (both one-tile kernels): the loop only records
-// (m_t, S_t) (thread 0, ms[2t], ms[2t+1]); here the T logarithms are evaluated in parallel and one wave replays the
-// sequential accounting (ll_t = lse_t - prev_t, loglik += ll_t) in loop order, 64 steps per load.  Same arithmetic and
-// order as kf_finalize step by step, so the same bits.  Called by every thread after a barrier that follows the last record.
+// NOPS independent block scans of one value per lane behind ONE barrier (their DPP chains interleave):
+// v[o] -> (incl[o], total[o]).  lds_seg: 16 doubles per operand, private to this call (no trailing barrier).
+template <int NT, int NOPS>
+__device__ __forceinline__ void block_scan_lanes_f64(const double (&v)[NOPS], double (&incl)[NOPS], double (&total)[NOPS],
+                                                     double (*lds_seg)[16]) {
+    constexpr int NSEG = NT / 64;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    double inc[NOPS];
+#pragma unroll
+    for (int o = 0; o < NOPS; ++o) inc[o] = wave_incl_scan_f64(v[o]);
+    if constexpr (NSEG == 1) {
+#pragma unroll
+        for (int o = 0; o < NOPS; ++o) { incl[o] = inc[o]; total[o] = readlane_f64(inc[o], 63); }
+        return;
+    }
+    if (lane == 63) {
+#pragma unroll
+        for (int o = 0; o < NOPS; ++o) lds_seg[o][wave] = inc[o];
+    }
+    __syncthreads();
+    double sv[NOPS];
+#pragma unroll
+    for (int o = 0; o < NOPS; ++o) sv[o] = row16_incl_scan((lane & 15) < NSEG ? lds_seg[o][lane & 15] : 0.0);
+#pragma unroll
+    for (int o = 0; o < NOPS; ++o) {
+        total[o] = readlane_f64(sv[o], 15);
+        incl[o] = (wave ? readlane_f64(sv[o], wave - 1) : 0.0) + inc[o];
+    }
+}
+
+// The PPT consecutive slots a lane owns, as one store (PPT = 2: p is 16-byte aligned)
+template <int PPT>
+__device__ __forceinline__ void store_slots(double* p, const double* v) {
+    static_assert(PPT == 1 || PPT == 2, "one particle or one pair per lane");
+    if constexpr (PPT == 2) *reinterpret_cast<double2*>(p) = make_double2(v[0], v[1]);
+    else *p = v[0];
+}
+
+// The end of a series, called by every thread after the last step's closing barrier.
+// Log conditional likelihoods outside the time loop: the loop only records (m_t, S_t) of the step before (one_tile_level2);
+// here the last step's pair joins them, the T logarithms are evaluated in parallel and one wave replays the sequential
+// accounting (ll_t = lse_t - prev_t, loglik += ll_t) in loop order, 64 steps per load.  Same arithmetic and order as
+// kf_finalize step by step, so the same bits.
 template <int NT>
-__device__ __forceinline__ void series_accounting(const StepArgs& a, int r, int T, double* ms, double m_last, double S_last,
-                                                  double A_prev, double mb_prev) {
+__device__ __forceinline__ void series_accounting(const StepArgs& a, int r, int T, double* ms, double A_prev, double mb_prev,
+                                                  const ExpTabEntry* etab) {
     const int tid = threadIdx.x;
+    const Level2 last = one_tile_level2(A_prev, mb_prev, a.rshift, etab, ms + 2 * (T - 1));
+    __syncthreads();
     for (int t = tid; t < T; t += NT) {
         ms[2 * t] = lse_of(ms[2 * t], ms[2 * t + 1], a.rshift);      // (m_t, S_t) -> lse_t
     }
     __syncthreads();
     if (tid < 64) {
-        double prev = a.scal[r].prev, loglik = a.scal[r].loglik, last = 0.0;
+        double prev = a.scal[r].prev, loglik = a.scal[r].loglik, last_ll = 0.0;
         for (int t0 = 0; t0 < T; t0 += 64) {
             const int t = t0 + tid;
             const double lse = (t < T) ? ms[2 * t] : 0.0;
@@ -60,23 +167,46 @@ __device__ __forceinline__ void series_accounting(const StepArgs& a, int r, int 
                 const double ll = lj - prev;
                 loglik = loglik + ll;
                 prev = (((t0 + j + 1) % a.resamp_sched) == 0) ? a.logN : lj;
-                last = ll;
+                last_ll = ll;
                 if (tid == j) mine = ll;
             }
             if (t < T && a.per_step) a.per_step[(size_t)r * a.Tcap + t] = mine;
         }
         if (tid == 0) {
             FilterScalars* o = a.scal + r;
-            o->m = m_last; o->S = S_last; o->prev = prev; o->loglik = loglik; o->last_ll = last;
+            o->m = last.m; o->S = last.S; o->prev = prev; o->loglik = loglik; o->last_ll = last_ll;
             a.tsum_out[(size_t)r * a.Bs] = A_prev;
             a.tmax_out[(size_t)r * a.Bs] = mb_prev;
         }
     }
 }
 
+// State hand-over after the series, as k_filter_step leaves it: a lane's NK runs of PPT slots (x, lw: [NK][PPT], slot
+// (k NT + tid) PPT), the cdf from LDS, and beyond P = NT NK PPT: x = 0, cdf flat at the tile sum, log-weight -inf.
+template <int NT, int NK, int PPT>
+__device__ __forceinline__ void hand_over_state(const StepArgs& a, size_t rowoff, const double* x, const double* lw,
+                                                const double* lds_cdf, double A_prev) {
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < NK; ++k) {
+        const int i = (k * NT + tid) * PPT;
+        store_slots<PPT>(a.x_out + rowoff + i, x + k * PPT);
+        store_slots<PPT>(a.cdf_out + rowoff + i, lds_cdf + i);
+        if (a.logw) store_slots<PPT>(a.logw + rowoff + i, lw + k * PPT);
+    }
+    const double zero[2] = {0.0, 0.0}, flat[2] = {A_prev, A_prev}, ninf[2] = {-dinf(), -dinf()};
+    for (int i = (NT * NK + tid) * PPT; i < kTile; i += NT * PPT) {
+        store_slots<PPT>(a.x_out + rowoff + i, zero);
+        store_slots<PPT>(a.cdf_out + rowoff + i, flat);
+        if (a.logw) store_slots<PPT>(a.logw + rowoff + i, ninf);
+    }
+}
+
+// One particle PAIR per lane.
 // grid = (R filters), block = NT, covers P = 2*NT*NK >= N particle slots (P a power of two, 256 .. 2048).
 // a.x_out / cdf_out / tsum_out / tmax_out / logw receive the state after the last step (as k_filter_step
 // leaves it), a.scal the accumulated log-likelihood; a.t / yi / gi are ignored (t = yi = gi = 0 .. T-1).
+// a.small_ms: [R][Tcap][2] scratch.
 template <int MODEL, int NT, int NK>
 __global__ __launch_bounds__(NT) void k_filter_series_small(const StepArgs a, const int T) {
     constexpr int P = 2 * NT * NK;
@@ -97,59 +227,24 @@ __global__ __launch_bounds__(NT) void k_filter_series_small(const StepArgs a, co
     const uint32_t key0 = a.keyp[0], key1 = a.keyp[1];
     const size_t rowoff = (size_t)r * a.Npad;
     const ModelConst mc = a.mc[r];
-    const bool multinomial_kind = a.resampler == RESAMP_MULTINOMIAL;
 
     double* ms = a.small_ms + (size_t)r * a.Tcap * 2;
     double xcur[NK][2], lwcur[NK][2];
 #pragma unroll
     for (int k = 0; k < NK; ++k) { xcur[k][0] = 0.0; xcur[k][1] = 0.0; lwcur[k][0] = 0.0; lwcur[k][1] = 0.0; }
     double A_prev = 0.0, mb_prev = 0.0;
-
-    // next step's inputs are requested one step ahead (uniform scalar loads)
-    double y_n = a.y[0], z_n = a.z ? a.z[0] : 0.0;
-    constexpr int KC = model_kcov<MODEL>();          // dim_cov user model: K covariates per step, prefetched like the scalar one
-    CovVals<KC> zc_n;
-    if constexpr (KC > 0) {
-#pragma unroll
-        for (int j = 0; j < KC; ++j) zc_n.v[j] = a.z ? a.z[j] : 0.0;
-    }
-    double gam_n = 0.0, pgam_n = 0.0, G_n = 1.0;
+    SeriesInputs<model_kcov<MODEL>()> in_n;
+    in_n.load_first(a, r);
 
     for (int t = 0; t < T; ++t) {
-        const double y = y_n, zcov = z_n;
-        CovVals<KC> zc;
-        if constexpr (KC > 0) zc = zc_n;
-        const double gam = gam_n, pgam = pgam_n, G = G_n;
-        if (t + 1 < T) {
-            y_n = a.y[t + 1];
-            if constexpr (KC > 0) {
-                if (a.z) {
-#pragma unroll
-                    for (int j = 0; j < KC; ++j) zc_n.v[j] = a.z[(size_t)(t + 1) * KC + j];
-                }
-            } else {
-                if (a.z) z_n = a.z[t + 1];
-            }
-            if (multinomial_kind && ((t + 1) % a.resamp_sched == 0)) {
-                const size_t gidx = ((size_t)(t + 1) * a.R + r) * a.B;          // B = 1, tile 0
-                gam_n = a.gam[gidx]; pgam_n = a.pgam[gidx]; G_n = a.gtot[(size_t)(t + 1) * a.R + r];
-            }
-        }
+        const auto in = in_n;
+        in_n.request(a, r, t + 1, T);
         const bool resampled = (t > 0) && (t % a.resamp_sched == 0);
-        const bool multinomial = resampled && multinomial_kind;
+        const bool multinomial = resampled && a.resampler == RESAMP_MULTINOMIAL;
 
-        // --- level-2 with one tile (level2_scan for B = 1) and the log conditional likelihood of step t-1 ---
-        double S = 0.0, R0 = 0.0;
-        if (t > 0) {
-            const double m = (mb_prev != mb_prev) ? dnan() : mb_prev;
-            // one tile: m_b - m is +0 unless the max is NaN or infinite, and the shift is 0 (Npad = 2048); exp(0) 2^0 = 1 exactly
-            const double dm = mb_prev - m;
-            const int sh = a.rshift - kTileShift;
-            const double Ap = (dm == 0.0 && sh == 0) ? __builtin_rint(A_prev) : __builtin_rint(A_prev * dexp_scaled_t(dm, sh, lds_etab));
-            S = Ap;
-            R0 = A_prev / Ap;
-            if (tid == 0) { ms[2 * (t - 1)] = m; ms[2 * (t - 1) + 1] = S; }       // its logarithm is taken after the loop
-        }
+        // --- level-2 of step t-1 ---
+        Level2 l2 = {0.0, 0.0, 0.0};
+        if (t > 0) l2 = one_tile_level2(A_prev, mb_prev, a.rshift, lds_etab, ms + 2 * (t - 1));
 
         // --- standard normals of this step: independent of the resampling chain, issued next to the spacings so that the
         //     two instruction streams interleave ---
@@ -183,13 +278,14 @@ __global__ __launch_bounds__(NT) void k_filter_series_small(const StepArgs a, co
 #pragma unroll
             for (int k = 0; k < NK; ++k) { xin[k][0] = xcur[k][0]; xin[k][1] = xcur[k][1]; lw_old[k][0] = lwcur[k][0]; lw_old[k][1] = lwcur[k][1]; }
         } else {
+            // --- targets, search in the cdf, gather ---
             double t_scale, u0 = 0.0;
-            if (a.resampler == RESAMP_MULTINOMIAL) t_scale = S / G;
+            if (a.resampler == RESAMP_MULTINOMIAL) t_scale = l2.S / in.G;
             else {
-                t_scale = S / (double)a.N;
+                t_scale = l2.S / (double)a.N;
                 if (a.resampler == RESAMP_SYSTEMATIC) u0 = systematic_u0((uint32_t)t, rep, key0, key1);
             }
-            const double ratio = gam / se;
+            const double ratio = in.gam / se;
 #pragma unroll
             for (int k = 0; k < NK; ++k) {
                 const int i0 = (k * NT + tid) * 2;
@@ -198,26 +294,21 @@ __global__ __launch_bounds__(NT) void k_filter_series_small(const StepArgs a, co
 #pragma unroll
                     for (int c = 0; c < 2; ++c) {
                         const double t1 = ratio * le[k][c];
-                        const double t2 = pgam + t1;
+                        const double t2 = in.pgam + t1;
                         tau[c] = __builtin_ceil(t2 * t_scale);
                     }
-                } else if (a.resampler == RESAMP_SYSTEMATIC) {
-                    tau[0] = __builtin_ceil(((double)i0 + u0) * t_scale);
-                    tau[1] = __builtin_ceil(((double)(i0 + 1) + u0) * t_scale);
                 } else {
-                    const u32x4 o = philox4x32_10((uint32_t)(i0 >> 1), (uint32_t)t, rep, STREAM_RESAMP, key0, key1);
-                    const double v0 = u01_co(o.v0, o.v1), v1 = u01_co(o.v2, o.v3);
-                    if (a.resampler == RESAMP_STRATIFIED) {
-                        tau[0] = __builtin_ceil(((double)i0 + v0) * t_scale);
-                        tau[1] = __builtin_ceil(((double)(i0 + 1) + v1) * t_scale);
-                    } else {
-                        tau[0] = __builtin_ceil(v0 * S);
-                        tau[1] = __builtin_ceil(v1 * S);
+                    double v[2] = {0.0, 0.0};
+                    if (a.resampler != RESAMP_SYSTEMATIC) {
+                        const u32x4 o = philox4x32_10((uint32_t)(i0 >> 1), (uint32_t)t, rep, STREAM_RESAMP, key0, key1);
+                        v[0] = u01_co(o.v0, o.v1); v[1] = u01_co(o.v2, o.v3);
                     }
+#pragma unroll
+                    for (int c = 0; c < 2; ++c) tau[c] = target_of(a.resampler, i0 + c, v[c], u0, t_scale, l2.S);
                 }
-                const double tl0 = __builtin_ceil((tau[0] - 0.0) * R0), tl1 = __builtin_ceil((tau[1] - 0.0) * R0);
+                const double tl[2] = {__builtin_ceil((tau[0] - 0.0) * l2.R0), __builtin_ceil((tau[1] - 0.0) * l2.R0)};
                 int jj[2];
-                count_less_radix8_x2<P>(lds_cdf, tl0, tl1, jj[0], jj[1]);
+                count_less_radix8<P, 2>(lds_cdf, tl, jj);
 #pragma unroll
                 for (int c = 0; c < 2; ++c) {
                     const int anc = jj[c] < a.N - 1 ? jj[c] : a.N - 1;
@@ -228,7 +319,7 @@ __global__ __launch_bounds__(NT) void k_filter_series_small(const StepArgs a, co
             }
         }
 
-        // --- standard normals, fSamp / q1Samp, logGEv, tile max ---
+        // --- fSamp / q1Samp, logGEv, tile max ---
         double lg[NK][2];
         double mx = -dinf();
         bool nan = false;
@@ -237,15 +328,8 @@ __global__ __launch_bounds__(NT) void k_filter_series_small(const StepArgs a, co
             const int i0 = (k * NT + tid) * 2;
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
-                double xn, l;
-                if constexpr (KC > 0) {
-#if SSME_HAS_USER_MODEL
-                    l = lw_old[k][c] + cov_step<typename user_model_of<MODEL>::type>(mc, t == 0, &xin[k][c], &zn[k][c], &y, zc.v, &xn, lds_etab);
-#endif
-                } else {
-                    xn = (t == 0) ? zn[k][c] * mc.a2 : model_prop<MODEL>(mc, xin[k][c], zn[k][c], zcov, lds_etab);
-                    l = lw_old[k][c] + model_logg<MODEL>(mc, y, xn, lds_etab);
-                }
+                double xn;
+                const double l = lw_old[k][c] + scalar_step<MODEL>(mc, t == 0, xin[k][c], zn[k][c], in.y, in.z, in.zc, &xn, lds_etab);
                 const bool valid = (i0 + c) < a.N;
                 xcur[k][c] = valid ? xn : 0.0;
                 lg[k][c] = valid ? l : -dinf();
@@ -267,108 +351,31 @@ __global__ __launch_bounds__(NT) void k_filter_series_small(const StepArgs a, co
 #pragma unroll
         for (int k = 0; k < NK; ++k) {
             const int i0 = (k * NT + tid) * 2;
-            *reinterpret_cast<double2*>(lds_cdf + i0) = make_double2(inc[k][0], inc[k][1]);
-            *reinterpret_cast<double2*>(lds_x + i0) = make_double2(xcur[k][0], xcur[k][1]);
+            store_slots<2>(lds_cdf + i0, inc[k]);
+            store_slots<2>(lds_x + i0, xcur[k]);
         }
         A_prev = total;
         mb_prev = mb;
         __syncthreads();                                              // cdf / x of step t visible to step t+1
     }
 
-    // --- the last step's (m, S), then the accounting of the whole series (series_accounting) and the state hand-over ---
-    {
-        const double m_last = (mb_prev != mb_prev) ? dnan() : mb_prev;
-        const double S_last = __builtin_rint(A_prev * dexp_scaled_t(mb_prev - m_last, a.rshift - kTileShift, lds_etab));
-        if (tid == 0) { ms[2 * (T - 1)] = m_last; ms[2 * (T - 1) + 1] = S_last; }
-        __syncthreads();
-        series_accounting<NT>(a, r, T, ms, m_last, S_last, A_prev, mb_prev);
-    }
-#pragma unroll
-    for (int k = 0; k < NK; ++k) {
-        const int i0 = (k * NT + tid) * 2;
-        *reinterpret_cast<double2*>(a.x_out + rowoff + i0) = make_double2(xcur[k][0], xcur[k][1]);
-        *reinterpret_cast<double2*>(a.cdf_out + rowoff + i0) = *reinterpret_cast<const double2*>(lds_cdf + i0);
-        if (a.logw) *reinterpret_cast<double2*>(a.logw + rowoff + i0) = make_double2(lwcur[k][0], lwcur[k][1]);
-    }
-    if (P < kTile) {
-        // slots beyond P: x = 0, cdf flat at the tile sum, log-weight -inf -- what k_filter_step writes there
-        for (int i = P + tid * 2; i < kTile; i += NT * 2) {
-            *reinterpret_cast<double2*>(a.x_out + rowoff + i) = make_double2(0.0, 0.0);
-            *reinterpret_cast<double2*>(a.cdf_out + rowoff + i) = make_double2(A_prev, A_prev);
-            if (a.logw) *reinterpret_cast<double2*>(a.logw + rowoff + i) = make_double2(-dinf(), -dinf());
-        }
-    }
+    series_accounting<NT>(a, r, T, ms, A_prev, mb_prev, lds_etab);
+    hand_over_state<NT, NK, 2>(a, rowoff, &xcur[0][0], &lwcur[0][0], lds_cdf, A_prev);
 }
-
 
 // ---------------------------------------------------------------------------------------------------------------------
 // One particle per lane (N <= 512; measured slower than the pair kernel at 1024).  The pair kernel above runs one wave per SIMD, each carrying the ~1000-instruction
 // chain of a particle PAIR, and is bound by dependent-instruction latency.  Here a lane owns ONE particle: the two lanes
 // of a pair both evaluate the pair's Philox call and Box-Muller (lanes are free, instructions are not) and each keeps
 // its own half, so a wave's chain per step is ~55 % of the pair kernel's and twice as many waves share a SIMD.
-// The log conditional likelihoods leave the time loop altogether: a step only records (m_t, S_t) (thread 0, 16 bytes);
-// after the loop the T logarithms are evaluated in parallel and one wave replays the sequential accounting
-// (ll_t = lse_t - prev_t, loglik += ll_t) in the order of the loop, 64 steps per load.  Same arithmetic, same bits.
 // grid = (R), block = NT = P particle slots (64 .. 512); a.small_ms: [R][Tcap][2] scratch.
 // ---------------------------------------------------------------------------------------------------------------------
-template <int NT>
-__device__ __forceinline__ void block_scan1_f64(double v, double& incl, double& total, double* lds_seg) {
-    constexpr int NSEG = NT / 64;
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const double inc = wave_incl_scan_f64(v);
-    if constexpr (NSEG == 1) { incl = inc; total = readlane_f64(inc, 63); return; }
-    if (lane == 63) lds_seg[wave] = inc;
-    __syncthreads();
-    const double sv = row16_incl_scan((lane & 15) < NSEG ? lds_seg[lane & 15] : 0.0);
-    total = readlane_f64(sv, 15);
-    const double pre = wave ? readlane_f64(sv, wave - 1) : 0.0;
-    incl = pre + inc;
-}
-
-// two independent block scans behind ONE barrier (their DPP steps interleave): v -> (incl, total), u -> (incl_u, total_u)
-template <int NT>
-__device__ __forceinline__ void block_scan2_f64(double v, double& incl, double& total, double* lds_seg, double u, double& incl_u,
-                                                double& total_u, double* lds_seg_u) {
-    constexpr int NSEG = NT / 64;
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const double inc = wave_incl_scan_f64(v), incu = wave_incl_scan_f64(u);
-    if constexpr (NSEG == 1) { incl = inc; total = readlane_f64(inc, 63); incl_u = incu; total_u = readlane_f64(incu, 63); return; }
-    if (lane == 63) { lds_seg[wave] = inc; lds_seg_u[wave] = incu; }
-    __syncthreads();
-    // (two independent chains: the compiler interleaves their DPP steps)
-    const double sv = row16_incl_scan((lane & 15) < NSEG ? lds_seg[lane & 15] : 0.0);
-    const double su = row16_incl_scan((lane & 15) < NSEG ? lds_seg_u[lane & 15] : 0.0);
-    total = readlane_f64(sv, 15); total_u = readlane_f64(su, 15);
-    incl = (wave ? readlane_f64(sv, wave - 1) : 0.0) + inc;
-    incl_u = (wave ? readlane_f64(su, wave - 1) : 0.0) + incu;
-}
-
-// min(#{ j < P : tile[j] < target }, P-1) by a radix-8 descent (see count_less_radix8_x2)
-template <int P>
-__device__ __forceinline__ int count_less_radix8(const double* tile, double t0) {
-    int p0 = 0;
-#pragma unroll
-    for (int w = P; w > 1;) {
-        const int radix = (w >= 8) ? 8 : w;
-        const int s = w / radix;
-        int c0 = 0;
-#pragma unroll
-        for (int k = 1; k < radix; ++k) c0 += (tile[p0 + k * s - 1] < t0) ? 1 : 0;
-        p0 += c0 * s;
-        w = s;
-    }
-    return p0;
-}
-
 template <int MODEL, int NT>
 __global__ __launch_bounds__(NT) void k_filter_series_lane(const StepArgs a, const int T) {
     constexpr int P = NT;
     __shared__ double lds_x[P];
     __shared__ double lds_cdf[P];
-    __shared__ double lds_seg_a[16];
-    __shared__ double lds_seg_c[16];
+    __shared__ double lds_seg[2][16];                 // the weights' scan and the spacings' scan, behind one barrier
     __shared__ double lds_d2[16];
     __shared__ __attribute__((aligned(16))) DrawTabs lds_dtab;
     __shared__ __attribute__((aligned(16))) ExpTabEntry lds_etab[SSME_EXP_TABLE_SIZE];
@@ -389,19 +396,13 @@ __global__ __launch_bounds__(NT) void k_filter_series_lane(const StepArgs a, con
 
     double xcur = 0.0, lwcur = 0.0;
     double A_prev = 0.0, mb_prev = 0.0;
-    double y_n = a.y[0], z_n = a.z ? a.z[0] : 0.0;
-    constexpr int KC = model_kcov<MODEL>();          // dim_cov user model: K covariates per step, prefetched like the scalar one
-    CovVals<KC> zc_n;
-    if constexpr (KC > 0) {
-#pragma unroll
-        for (int j = 0; j < KC; ++j) zc_n.v[j] = a.z ? a.z[j] : 0.0;
-    }
-    double gam_n = 0.0, pgam_n = 0.0, G_n = 1.0;
+    SeriesInputs<model_kcov<MODEL>()> in_n;
+    in_n.load_first(a, r);
 
     // The draws of a step do not depend on the filter's state, and at one or two waves per SIMD the step is a chain of dependent
     // instructions: the Philox call, the Box-Muller pair and the spacing of step t + 1 are therefore computed DURING step t, in the
     // block that waits for the search's LDS reads, and the spacings' block scan shares the barrier of the weights' scan
-    // (block_scan2_f64).  Carried to the next iteration: the normal, the spacing's inclusive sum and the total.  Same arithmetic.
+    // (block_scan_lanes_f64).  Carried to the next iteration: the normal, the spacing's inclusive sum and the total.  Same arithmetic.
     double zn_n = 0.0, le_n = 0.0, se_n = 1.0, qe_n = 0.0;
     auto draw_for = [&](int tn) {
         // the pair's Philox call: words 0-1 -> Box-Muller (this lane keeps cos or sin), words 2 / 3 -> this lane's spacing
@@ -416,29 +417,13 @@ __global__ __launch_bounds__(NT) void k_filter_series_lane(const StepArgs a, con
     draw_for(0);
 
     for (int t = 0; t < T; ++t) {
-        const double y = y_n, zcov = z_n;
-        CovVals<KC> zc;
-        if constexpr (KC > 0) zc = zc_n;
-        const double gam = gam_n, pgam = pgam_n, G = G_n;
+        const auto in = in_n;
+        in_n.request(a, r, t + 1, T);
         const double zn = zn_n, le = le_n, se = se_n;
-        if (t + 1 < T) {
-            y_n = a.y[t + 1];
-            if constexpr (KC > 0) {
-                if (a.z) {
-#pragma unroll
-                    for (int j = 0; j < KC; ++j) zc_n.v[j] = a.z[(size_t)(t + 1) * KC + j];
-                }
-            } else {
-                if (a.z) z_n = a.z[t + 1];
-            }
-            if (multinomial_kind && ((t + 1) % a.resamp_sched == 0)) {
-                const size_t gidx = ((size_t)(t + 1) * a.R + r) * a.B;
-                gam_n = a.gam[gidx]; pgam_n = a.pgam[gidx]; G_n = a.gtot[(size_t)(t + 1) * a.R + r];
-            }
-        }
         const bool resampled = (t > 0) && (t % a.resamp_sched == 0);
 
-        // --- level-2 with one tile; (m, S) of step t-1 go to the scratch, their logarithm is taken after the loop ---
+        // --- level-2 of step t-1: one_tile_level2's text, written out.  Called as the function (struct or reference results) this
+        //     kernel took 0.03 to 0.06 us per step longer at N = 500 (profiles/small_series_refactor.txt, section 4) ---
         double S = 0.0, R0 = 0.0;
         if (t > 0) {
             const double m = (mb_prev != mb_prev) ? dnan() : mb_prev;
@@ -457,41 +442,37 @@ __global__ __launch_bounds__(NT) void k_filter_series_lane(const StepArgs a, con
             xin = xcur; lw_old = lwcur;
             draw_for(t + 1);
         } else {
+            // --- target, search in the cdf, gather ---
             double tau;
             if (a.resampler == RESAMP_MULTINOMIAL) {
-                const double t_scale = S / G;
-                const double ratio = gam / se;
+                const double t_scale = S / in.G;
+                const double ratio = in.gam / se;
                 const double t1 = ratio * le;
-                const double t2 = pgam + t1;
+                const double t2 = in.pgam + t1;
                 tau = __builtin_ceil(t2 * t_scale);
-            } else if (a.resampler == RESAMP_SYSTEMATIC) {
-                const double t_scale = S / (double)a.N;
-                const double u0 = systematic_u0((uint32_t)t, rep, key0, key1);
-                tau = __builtin_ceil(((double)tid + u0) * t_scale);
             } else {
+                // the division ahead of the draw, and the draw in the branch that needs it: with both draws joined before one
+                // call of target_of the step took 0.08 us longer
                 const double t_scale = S / (double)a.N;
-                const u32x4 o = philox4x32_10((uint32_t)(tid >> 1), (uint32_t)t, rep, STREAM_RESAMP, key0, key1);
-                const double v = c ? u01_co(o.v2, o.v3) : u01_co(o.v0, o.v1);
-                tau = (a.resampler == RESAMP_STRATIFIED) ? __builtin_ceil(((double)tid + v) * t_scale) : __builtin_ceil(v * S);
+                if (a.resampler == RESAMP_SYSTEMATIC) {
+                    tau = target_of(RESAMP_SYSTEMATIC, tid, 0.0, systematic_u0((uint32_t)t, rep, key0, key1), t_scale, S);
+                } else {      // the pair's Philox call; this lane keeps its half
+                    const u32x4 o = philox4x32_10((uint32_t)(tid >> 1), (uint32_t)t, rep, STREAM_RESAMP, key0, key1);
+                    tau = target_of(a.resampler, tid, c ? u01_co(o.v2, o.v3) : u01_co(o.v0, o.v1), 0.0, t_scale, S);
+                }
             }
-            const double tl = __builtin_ceil((tau - 0.0) * R0);
-            const int jj = count_less_radix8<P>(lds_cdf, tl);
+            const double tl[1] = {__builtin_ceil((tau - 0.0) * R0)};
+            int jj[1];
+            count_less_radix8<P, 1>(lds_cdf, tl, jj);
             draw_for(t + 1);                                   // fills the waits of the descent's LDS reads and of the gather
-            const int anc = jj < a.N - 1 ? jj : a.N - 1;
+            const int anc = jj[0] < a.N - 1 ? jj[0] : a.N - 1;
             if (a.anc && valid) a.anc[rowoff + tid] = (uint32_t)anc;
             xin = lds_x[anc];
         }
 
         // --- fSamp / q1Samp, logGEv, tile max ---
-        double xn, l;
-        if constexpr (KC > 0) {
-#if SSME_HAS_USER_MODEL
-            l = lw_old + cov_step<typename user_model_of<MODEL>::type>(mc, t == 0, &xin, &zn, &y, zc.v, &xn, lds_etab);
-#endif
-        } else {
-            xn = (t == 0) ? zn * mc.a2 : model_prop<MODEL>(mc, xin, zn, zcov, lds_etab);
-            l = lw_old + model_logg<MODEL>(mc, y, xn, lds_etab);
-        }
+        double xn;
+        const double l = lw_old + scalar_step<MODEL>(mc, t == 0, xin, zn, in.y, in.z, in.zc, &xn, lds_etab);
         xcur = valid ? xn : 0.0;
         const double lg = valid ? l : -dinf();
         lwcur = lg;
@@ -500,31 +481,19 @@ __global__ __launch_bounds__(NT) void k_filter_series_lane(const StepArgs a, con
         const double mb = block_max_nanprop<NT>(mx, nan, lds_d2);    // barrier: every search / gather of this step is done
 
         // --- tile-local fixed-point weights, exact scan -> the next step's cdf (LDS); the next step's spacings ride along ---
-        const double q = valid ? __builtin_rint(dexp_scaled_t(lg - mb, kTileShift, lds_etab)) : 0.0;
-        double inc, total;
-        block_scan2_f64<NT>(q, inc, total, lds_seg_c, qe_n, le_n, se_n, lds_seg_a);
-        lds_cdf[tid] = inc;
+        const double sv[2] = {valid ? __builtin_rint(dexp_scaled_t(lg - mb, kTileShift, lds_etab)) : 0.0, qe_n};
+        double sinc[2], stot[2];
+        block_scan_lanes_f64<NT, 2>(sv, sinc, stot, lds_seg);
+        le_n = sinc[1]; se_n = stot[1];
+        lds_cdf[tid] = sinc[0];
         lds_x[tid] = xcur;
-        A_prev = total;
+        A_prev = stot[0];
         mb_prev = mb;
         __syncthreads();                                              // cdf / x of step t visible to step t+1
     }
 
-    // --- the last step's (m, S); then every log conditional likelihood: logarithms in parallel, accounting in loop order ---
-    const double m_last = (mb_prev != mb_prev) ? dnan() : mb_prev;
-    const double S_last = __builtin_rint(A_prev * dexp_scaled_t(mb_prev - m_last, a.rshift - kTileShift, lds_etab));
-    if (tid == 0) { ms[2 * (T - 1)] = m_last; ms[2 * (T - 1) + 1] = S_last; }
-    __syncthreads();
-    series_accounting<NT>(a, r, T, ms, m_last, S_last, A_prev, mb_prev);
-    // --- state hand-over: what k_filter_step leaves (slots beyond N: x = 0, flat cdf, log-weight -inf) ---
-    a.x_out[rowoff + tid] = xcur;
-    a.cdf_out[rowoff + tid] = lds_cdf[tid];
-    if (a.logw) a.logw[rowoff + tid] = lwcur;
-    for (int i = P + tid; i < kTile; i += NT) {
-        a.x_out[rowoff + i] = 0.0;
-        a.cdf_out[rowoff + i] = A_prev;
-        if (a.logw) a.logw[rowoff + i] = -dinf();
-    }
+    series_accounting<NT>(a, r, T, ms, A_prev, mb_prev, lds_etab);
+    hand_over_state<NT, 1, 1>(a, rowoff, &xcur, &lwcur, lds_cdf, A_prev);
 }
 
 }  // namespace ssme

@@ -35,7 +35,7 @@ the general form is k_filter_step<512, BIG=0, 2048, -1, WL2=1> (the step API nev
 
 Why no search can hang, and none leaves its arrays, on NaN tile maxima or a cdf of zeros (read from the code before the first run):
   * every loop has a trip count fixed by the shape, never by the data: count_less_pow2 halves a power-of-two step down to 1;
-    lds_count_search and count_less_radix8(_x2) are unrolled at compile time; the 64-ary descent of the one-launch split is three rounds
+    lds_count_search and count_less_radix8<P, NQ> are unrolled at compile time; the 64-ary descent of the one-launch split is three rounds
     (strides 256, 4, 1); count_from of k_level2_plan doubles `sz` only while p + sz - 1 < Bpow2 (at most log2 Bpow2 times) and then
     halves it; k_l2_ranges halves Bpow2 down to 1; series_accounting and the time loops run T times.  No loop waits for a value;
     the two tickets (step API, l2_ticket) are counted once per workgroup and reset by the last arriver whatever the data are.

@@ -917,7 +917,7 @@ def test_set_seed_reuses_graph_and_matches_fresh_handle(sa, oracle, spy):
 
 
 # ---- one-tile filters: whole series in one launch (pf_small.h) ---------------------------------------------------
-@pytest.mark.parametrize("n", [1, 2, 100, 256, 257, 500, 1000, 1024, 1025, 2048])
+@pytest.mark.parametrize("n", [1, 2, 64, 65, 100, 128, 129, 256, 257, 500, 512, 513, 1000, 1024, 1025, 2048])   # both sides of every kernel switch
 @pytest.mark.parametrize("rs", [0, 1, 2, 3])
 def test_small_series_kernel_matches_tiled_kernel_and_oracle(sa, oracle, spy, n, rs):
     """N <= 2048: the single-launch series kernel, the tiled per-step kernel and the oracle agree bit for bit
@@ -951,14 +951,15 @@ def test_small_series_kernel_matches_tiled_kernel_and_oracle(sa, oracle, spy, n,
 
 
 @pytest.mark.parametrize("model,th", [(1, [0.9, 0.0, 1.0, -0.1]), (2, [0.9, 0.5, 0.7])])
-def test_small_series_kernel_other_models_and_schedules(sa, oracle, spy, model, th):
+@pytest.mark.parametrize("n", [300, 700])       # one particle per lane (the draw carried a step ahead) and one pair per lane
+def test_small_series_kernel_other_models_and_schedules(sa, oracle, spy, model, th, n):
     y = spy[:30]
     z = np.concatenate([[0.0], y[:-1]]) if model == 1 else None
     for sched in (1, 3):
-        b = sa.ParticleFilterBank(model, 700, 2, 99, sa.RESAMP_MULTINOMIAL, sched)
+        b = sa.ParticleFilterBank(model, n, 2, 99, sa.RESAMP_MULTINOMIAL, sched)
         b.set_params(th)
         ll = b.run_series(y, z)
-        o = oracle.Filter(model, 700, th, 99, rep=1, resampler=0, resamp_sched=sched)
+        o = oracle.Filter(model, n, th, 99, rep=1, resampler=0, resamp_sched=sched)
         lo, po = o.run_series(y, z)
         assert_bits_equal([ll[1]], [lo], f"model {model} sched {sched}")
         assert_bits_equal(b.per_step()[1], po, "per-step")
