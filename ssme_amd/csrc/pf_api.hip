@@ -621,7 +621,7 @@ static int create_impl(const ssme_pf_config* cfg, int shard_rank, int shard_worl
         HIPCHK(own_alloc(h, h->l2_R, sizeof(double) * nb));
         HIPCHK(own_alloc(h, h->l2_lo, sizeof(int32_t) * nb, Mem::zeroed));
         HIPCHK(own_alloc(h, h->l2_hi, sizeof(int32_t) * nb, Mem::zeroed));
-        HIPCHK(own_alloc(h, h->scal, sizeof(FilterScalars) * h->R));
+        HIPCHK(own_alloc(h, h->scal, sizeof(FilterScalars) * h->R, Mem::zeroed));     // ssme_pf_get_loglik before set_params: 0, as after a reset
         HIPCHK(own_alloc(h, h->mc, sizeof(ModelConst) * h->R));
         HIPCHK(own_alloc(h, h->scratchR, sizeof(double) * h->R));
         HIPCHK(own_alloc(h, h->exp_part, sizeof(double) * nb * kMaxFunctionals));
