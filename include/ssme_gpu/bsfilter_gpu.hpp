@@ -28,6 +28,12 @@
 // [-1.7, 3.25] (a tail indicator, a clamp) is misclassified by such a probe, which is why it is no longer the default.
 // Every model object draws its own random stream (the reference clock-seeds each object): the filter id defaults to a
 // process-wide counter.  Errors: std::invalid_argument / std::runtime_error, as the reference throws; NaN/-inf are values.
+// What the classes share is written once, in the first namespace detail below: weighted_mean (every host sum
+// sum_i h(x_i) w_i / sum_i w_i: swarm members, Liu-West, user models), classify (the six-probe classifier, with 0 or 4
+// parameter columns), dispatch_expectations (declared -> probe -> one device call -> one lazy download -> results in the
+// caller's order; the declared range and the cap on device functionals are arguments), column0 / svol_theta (series and pack
+// of the two log-likelihood evaluators).  detail::user_core carries user_bs_gpu and user_bswc_gpu, detail::member_core the two
+// swarm-member models, detail::swarm_impl swarm_gpu and swarm_with_covs_gpu.
 #ifndef SSME_GPU_BSFILTER_GPU_HPP
 #define SSME_GPU_BSFILTER_GPU_HPP
 
@@ -44,6 +50,7 @@
 #include <mutex>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../ssme_pf.h"
@@ -101,6 +108,146 @@ inline unsigned resolve_filter_id(unsigned id) {
     static std::atomic<unsigned> next{0};
     return id == auto_filter_id ? next.fetch_add(1) : id;
 }
+template <typename T>
+class small_matrix {                                  // the least a dynamic matrix must offer here
+public:
+    small_matrix() = default;
+    small_matrix(long r, long c) : r_(r), c_(c), v_((std::size_t)(r * c), T(0)) {}
+    long rows() const { return r_; }
+    long cols() const { return c_; }
+    T& operator()(long i, long j) { return v_[(std::size_t)(i * c_ + j)]; }
+    const T& operator()(long i, long j) const { return v_[(std::size_t)(i * c_ + j)]; }
+private:
+    long r_ = 0, c_ = 0;
+    std::vector<T> v_;
+};
+// ---- expectations of host-side functionals: the pieces every model class shares ---------------------------------
+// sum_i v(i) w[i] / sum_i w[i], entry by entry (twin liu_west_filter.h:1662-1683).  v(i): the value of particle i, anything
+// with rows(), cols(), (r, c); the shape is that of particle 0.  One double accumulator per entry, particles in ascending
+// order, the weight sum in the same loop, one division at the end: the order of the roundings is part of the contract
+// (a member gives the same bits in its own handle, in a swarm_context and through every class of this header).
+template <typename float_t, typename Out, typename V>
+Out weighted_mean(std::size_t n, const std::vector<double>& w, const V& v) {
+    std::vector<double> acc;
+    long rows = 0, cols = 0;
+    double wsum = 0.0;
+    for (std::size_t i = 0; i < n; ++i) {
+        const auto& hv = v(i);
+        if (i == 0) { rows = (long)hv.rows(); cols = (long)hv.cols(); acc.assign((std::size_t)(rows * cols), 0.0); }
+        for (long r = 0; r < rows; ++r)
+            for (long c = 0; c < cols; ++c) acc[(std::size_t)(r * cols + c)] += (double)hv(r, c) * w[i];
+        wsum += w[i];
+    }
+    Out m(rows, cols);
+    for (long r = 0; r < rows; ++r)
+        for (long c = 0; c < cols; ++c) m(r, c) = (float_t)(acc[(std::size_t)(r * cols + c)] / wsum);
+    return m;
+}
+// E[f_k], k < n_fs, of SCALAR-valued functions of a vector state (the user-model classes): eval(k, x_i) = f_k at particle i,
+// x[d * n + i] as ssme_pf_download_weights fills it.  The n_fs values of one particle are one 1 x n_fs value of weighted_mean,
+// so the functions are called particle by particle, k ascending within a particle.
+template <std::size_t dimx, typename Eval>
+std::vector<double> state_means(std::size_t n, const std::vector<double>& x, const std::vector<double>& w, std::size_t n_fs, const Eval& eval) {
+    small_matrix<double> hv(1, (long)n_fs);
+    const small_matrix<double> m = weighted_mean<double, small_matrix<double>>(n, w, [&](std::size_t i) -> const small_matrix<double>& {
+        std::array<double, dimx> xi;
+        for (std::size_t d = 0; d < dimx; ++d) xi[d] = x[d * n + i];
+        for (std::size_t k = 0; k < n_fs; ++k) hv(0, (long)k) = eval(k, xi);
+        return hv;
+    });
+    std::vector<double> e(n_fs);
+    for (std::size_t k = 0; k < n_fs; ++k) e[k] = m(0, (long)k);
+    return e;
+}
+// Which built-in functional reproduces h?  Probed at six states (and six parameter vectors); exact agreement required
+// (exp(x/2): 4 ulp).  eval(x, p) = h at state x and parameters p[0..3], a matrix; n_par = how many parameter columns h can
+// see (0: the bootstrap members, 4: Liu-West).  Returns SSME_H_* or 4 + d for parameter d (and the factor to apply to the
+// device value), or -1 = evaluate on the host.  Precedence: constant, x, x^2, exp(x/2), then the parameters in order.
+template <typename float_t, typename Eval>
+int classify(const Eval& eval, int n_par, double* scale) {
+    static const double px[6] = {-1.7, -0.3125, 0.0, 0.5625, 1.9, 3.25};
+    static const double pp[6][4] = {{0.91, -0.07, 0.021, -0.31}, {0.83, 0.02, 0.034, -0.12}, {0.95, 0.09, 0.077, -0.45},
+                                    {0.88, -0.03, 0.055, -0.02}, {0.97, 0.05, 0.012, -0.27}, {0.81, -0.09, 0.093, -0.38}};
+    bool is_const = true, is_x = true, is_x2 = true, is_vol = true, is_p[4] = {true, true, true, true};
+    float_t c0 = 0;
+    for (int q = 0; q < 6; ++q) {
+        const float_t xx = (float_t)px[q];
+        float_t p[4];
+        for (int d = 0; d < 4; ++d) p[d] = (float_t)pp[q][d];
+        const auto m = eval(xx, (const float_t*)p);
+        if (m.rows() != 1 || m.cols() != 1) return -1;
+        const float_t v = m(0, 0);
+        if (q == 0) c0 = v;
+        is_const = is_const && (v == c0);
+        is_x = is_x && (v == xx);
+        is_x2 = is_x2 && (v == xx * xx);
+        const float_t e = (float_t)std::exp((float_t)0.5 * xx);
+        is_vol = is_vol && (std::fabs(v - e) <= 4 * std::numeric_limits<float_t>::epsilon() * e);
+        for (int d = 0; d < n_par; ++d) is_p[d] = is_p[d] && (v == p[d]);
+    }
+    *scale = 1.0;
+    if (is_const) { *scale = (double)c0 / 42.0; return SSME_H_CONST42; }   // E[c] = c E[42] / 42 (a NaN filter stays NaN)
+    if (is_x) return SSME_H_X;
+    if (is_x2) return SSME_H_X2;
+    if (is_vol) return SSME_H_VOL;
+    for (int d = 0; d < n_par; ++d) if (is_p[d]) return 4 + d;
+    return -1;
+}
+// What a filter type lets run on the device: the declared ids it accepts, and how many device functionals one call takes
+// (those beyond the cap are summed on the host).  Two filter types, two policies, each stated where it is used.
+struct device_policy {
+    int declared_lo, declared_hi;
+    std::size_t cap;
+};
+constexpr device_policy bootstrap_policy{SSME_H_X, SSME_H_CONST42, 4};                      // ssme_pf_get_expectations_multi takes 4
+constexpr device_policy liu_west_policy{0, 7, std::numeric_limits<std::size_t>::max()};     // 0-3 SSME_H_*, 4-7 phi, mu, sigma, rho; no cap
+// E[h_j], j < n_funcs, after the last step, in the caller's order: a functional declared as a built-in (or, with `probe`,
+// classified as one: classify_j(j, &scale)) goes to the device, all of them in ONE call device(ids); everything else is
+// host(j) over ONE download(), made when the first host functional is met.  Device results are 1 x 1 matrices.
+template <typename float_t, typename Mat, typename Classify, typename Device, typename Download, typename Host>
+std::vector<Mat> dispatch_expectations(std::size_t n_funcs, const std::vector<int>& declared, const device_policy& pol, bool probe,
+                                       const Classify& classify_j, const Device& device, const Download& download, const Host& host) {
+    std::vector<Mat> out;
+    if (n_funcs == 0) return out;
+    std::vector<int> kind(n_funcs, -1);
+    std::vector<double> scale(n_funcs, 1.0);
+    std::vector<int32_t> ids;
+    for (std::size_t j = 0; j < n_funcs; ++j) {
+        if (j < declared.size() && declared[j] >= pol.declared_lo && declared[j] <= pol.declared_hi) kind[j] = declared[j];
+        else if (probe) kind[j] = classify_j(j, &scale[j]);
+        if (kind[j] >= 0 && ids.size() == pol.cap) kind[j] = -1;       // more device functionals than one call takes: the rest on the host
+        if (kind[j] >= 0) ids.push_back(kind[j]);
+    }
+    std::vector<double> dev;
+    if (!ids.empty()) dev = device(ids);
+    bool downloaded = false;
+    std::size_t d = 0;
+    for (std::size_t j = 0; j < n_funcs; ++j) {
+        if (kind[j] >= 0) {
+            Mat m(1, 1);
+            m(0, 0) = (float_t)(dev[d++] * scale[j]);
+            out.push_back(m);
+            continue;
+        }
+        if (!downloaded) { download(); downloaded = true; }
+        out.push_back(host(j));
+    }
+    return out;
+}
+// ---- the two log-likelihood evaluators' inputs -------------------------------------------------------------------
+// column 0 of `data`, any container of vectors with operator()(0)
+template <typename Data>
+std::vector<double> column0(const Data& data) {
+    std::vector<double> y(data.size());
+    for (std::size_t i = 0; i < data.size(); ++i) y[i] = (double)data[i](0);
+    return y;
+}
+// a param::pack in the reference's order beta, phi, ss -> the C ABI's (beta, phi, sigma = sqrt(ss))
+template <typename Pack>
+std::array<double, 3> svol_theta(const Pack& theta) {
+    return {(double)theta.get_untrans_params(0, 0)(0), (double)theta.get_untrans_params(1, 1)(0),
+            std::sqrt((double)theta.get_untrans_params(2, 2)(0))};
+}
 }  // namespace detail
 
 // ---- svol_bs ---------------------------------------------------------------------------------------------
@@ -139,56 +286,76 @@ private:
 // ---- a model of the user's own (ssme_amd/csrc/model_api.h: SSME_MODEL_USER0) -------------------------------------------------------
 // The reference's way to a new model is a class derived from pf::filters::BSFilter<nparts, dimx, dimy, resampT, float_t> with five
 // callbacks (example/univ_svol_bootstrap_filter.h:17-41); here the callbacks live in the header that was compiled into the library
-// this program links (build.build_user_model), and this class is the caller-visible rest: filter(y), getLogCondLike(), and
+// this program links (build.build_user_model), and user_bs_gpu is the caller-visible rest: filter(y), getLogCondLike(), and
 // getExpectations() of ANY functions h(x) of the whole state, evaluated on the host over the downloaded particles and weights
-// (liu_west_filter.h:1662-1683); functions the model's header itself declares are summed on the device: getModelExpectations().  dimx / dimy must be the model's (checked against ssme_pf_user_model_dims).
-template <std::size_t nparts, std::size_t dimx = 1, std::size_t dimy = 1, typename float_t = double>
-class user_bs_gpu {
+// (liu_west_filter.h:1662-1683); functions the model's header itself declares are summed on the device: getModelExpectations().
+// dimx / dimy must be the model's (checked against ssme_pf_user_model_dims).
+// detail::user_core is what user_bs_gpu and user_bswc_gpu (the model with covariates) share: everything but the arity of func, the
+// filter overloads and the forecast call.
+namespace detail {
+template <std::size_t nparts, std::size_t dimx, std::size_t dimy, typename float_t>
+class user_core {
 public:
     using float_type = float_t;
     using state_vector = std::array<double, dimx>;
-    using func = std::function<double(const state_vector&)>;
-    explicit user_bs_gpu(const std::vector<double>& theta, gpu_options o = gpu_options(), unsigned filter_id = auto_filter_id) {
-        std::int32_t dx = 0, dy = 0;
-        check(ssme_pf_user_model_dims(&dx, &dy));                      // SSME_ERR_UNSUPPORTED: the stock library was linked
-        if (dx != (std::int32_t)dimx || dy != (std::int32_t)dimy) throw std::invalid_argument("user_bs_gpu: dimx / dimy are not the compiled-in model's");
-        h_ = handle(SSME_MODEL_USER0, (int)nparts, 1, o.seed, o.resampler, o.resamp_sched, o.device, detail::resolve_filter_id(filter_id));
-        check(ssme_pf_set_params(h_.get(), theta.data(), (std::int32_t)theta.size(), 1), h_.get());
-    }
-    // filter(obs) / filter(obs, fs): obs(j), j < dimy (an Eigen vector, a std::array, ...)
-    template <typename Osv>
-    void filter(const Osv& yt, const std::vector<func>& fs = std::vector<func>()) {
-        double y[dimy];
-        for (std::size_t j = 0; j < dimy; ++j) y[j] = (double)yt[j];
-        double out = 0.0;
-        check(ssme_pf_step(h_.get(), y, nullptr, &out), h_.get());
-        last_ = (float_t)out;
-        expectations_.assign(fs.size(), 0.0);
-        if (!fs.empty()) {
-            std::vector<double> x(dimx * nparts), w(nparts);
-            check(ssme_pf_download_weights(h_.get(), 0, x.data(), w.data()), h_.get());
-            std::vector<double> num(fs.size(), 0.0);
-            double den = 0.0;
-            for (std::size_t i = 0; i < nparts; ++i) {
-                state_vector xi;
-                for (std::size_t d = 0; d < dimx; ++d) xi[d] = x[d * nparts + i];
-                for (std::size_t k = 0; k < fs.size(); ++k) num[k] += fs[k](xi) * w[i];
-                den += w[i];
-            }
-            for (std::size_t k = 0; k < fs.size(); ++k) expectations_[k] = num[k] / den;
-        }
-    }
     float_t getLogCondLike() const { return last_; }
     const std::vector<double>& getExpectations() const { return expectations_; }
-    // the n_h functionals the model's header declares (model_api.h: n_h, h) after the last filter(), summed ON THE DEVICE: one small
-    // download instead of filter(y, fs)'s (dimx + 1) * nparts doubles.  Throws what check throws (std::runtime_error) when the linked
-    // library declares none.
+    // the n_h functionals the model's header declares (model_api.h: n_h, h; with covariates h(x_t, z_t)) after the last filter(),
+    // summed ON THE DEVICE: one small download instead of filter(y, fs)'s (dimx + 1) * nparts doubles.  Throws what check throws
+    // (std::runtime_error) when the linked library declares none.
     std::vector<double> getModelExpectations() const {
         const int n = ssme_pf_user_model_n_h();
         if (n < 1) check(SSME_ERR_UNSUPPORTED, h_.get());
         std::vector<double> out((std::size_t)n);
         check(ssme_pf_get_user_expectations(h_.get(), out.data()), h_.get());
         return out;
+    }
+    ssme_pf_handle native() const { return h_.get(); }
+
+protected:
+    // who: the public class, for the messages.  dimcov: the class's covariate dimension; -1: the class without covariates
+    user_core(const char* who, int dimcov, const std::vector<double>& theta, const gpu_options& o, unsigned filter_id) {
+        std::int32_t dx = 0, dy = 0;
+        check(ssme_pf_user_model_dims(&dx, &dy));                      // SSME_ERR_UNSUPPORTED: the stock library was linked
+        if (dx != (std::int32_t)dimx || dy != (std::int32_t)dimy) throw std::invalid_argument(std::string(who) + ": dimx / dimy are not the compiled-in model's");
+        if (dimcov >= 0 && ssme_pf_user_model_dim_cov() != dimcov) throw std::invalid_argument(std::string(who) + ": dimcov is not the compiled-in model's dim_cov");
+        h_ = handle(SSME_MODEL_USER0, (int)nparts, 1, o.seed, o.resampler, o.resamp_sched, o.device, resolve_filter_id(filter_id));
+        check(ssme_pf_set_params(h_.get(), theta.data(), (std::int32_t)theta.size(), 1), h_.get());
+    }
+    // one step on obs[j], j < dimy, with the step's covariates z (nullptr: none); then E[f_k], k < n_fs, on the host over one
+    // download of (x, weights): eval(k, x_i) = f_k at particle i (detail::state_means)
+    template <typename Osv, typename Eval>
+    void step(const Osv& yt, const double* z, std::size_t n_fs, const Eval& eval) {
+        double y[dimy];
+        for (std::size_t j = 0; j < dimy; ++j) y[j] = (double)yt[j];
+        double out = 0.0;
+        check(ssme_pf_step(h_.get(), y, z, &out), h_.get());
+        last_ = (float_t)out;
+        expectations_.assign(n_fs, 0.0);
+        if (n_fs == 0) return;
+        std::vector<double> x(dimx * nparts), w(nparts);
+        check(ssme_pf_download_weights(h_.get(), 0, x.data(), w.data()), h_.get());
+        expectations_ = state_means<dimx>(nparts, x, w, n_fs, eval);
+    }
+
+private:
+    handle h_;
+    float_t last_ = 0;
+    std::vector<double> expectations_;
+};
+}  // namespace detail
+
+template <std::size_t nparts, std::size_t dimx = 1, std::size_t dimy = 1, typename float_t = double>
+class user_bs_gpu : public detail::user_core<nparts, dimx, dimy, float_t> {
+public:
+    using state_vector = std::array<double, dimx>;
+    using func = std::function<double(const state_vector&)>;
+    explicit user_bs_gpu(const std::vector<double>& theta, gpu_options o = gpu_options(), unsigned filter_id = auto_filter_id)
+        : detail::user_core<nparts, dimx, dimy, float_t>("user_bs_gpu", -1, theta, o, filter_id) {}
+    // filter(obs) / filter(obs, fs): obs(j), j < dimy (an Eigen vector, a std::array, ...)
+    template <typename Osv>
+    void filter(const Osv& yt, const std::vector<func>& fs = std::vector<func>()) {
+        this->step(yt, nullptr, fs.size(), [&fs](std::size_t k, const state_vector& xi) { return fs[k](xi); });
     }
     // sim_future_obs(num_future_steps) of the model's FutureSimulator add-on (test/test_pswarm.cpp:64-67, 112-116) after the last
     // filter(), ON THE DEVICE, for a model whose header declares its observation draw (model_api.h: gsamp / gsamp_vec):
@@ -197,15 +364,9 @@ public:
     // linked library declares no draw (SSME_ERR_UNSUPPORTED of the call itself).
     std::vector<double> sim_future_obs(unsigned num_steps, double last_obs = 0.0) {
         std::vector<double> y((std::size_t)num_steps * dimy * nparts);
-        check(ssme_pf_sim_future_obs(h_.get(), (std::int32_t)num_steps, &last_obs, y.data(), nullptr, nullptr), h_.get());
+        check(ssme_pf_sim_future_obs(this->native(), (std::int32_t)num_steps, &last_obs, y.data(), nullptr, nullptr), this->native());
         return y;
     }
-    ssme_pf_handle native() const { return h_.get(); }
-
-private:
-    handle h_;
-    float_t last_ = 0;
-    std::vector<double> expectations_;
 };
 
 // ---- a model of the user's own WITH COVARIATES (model_api.h: dim_cov) ---------------------------------------------------------------
@@ -215,160 +376,29 @@ private:
 // whole state and the step's covariates, evaluated on the host over the downloaded particles and weights as user_bs_gpu does;
 // functions the header declares are summed on the device: getModelExpectations().  dimx / dimy / dimcov must be the model's.
 template <std::size_t nparts, std::size_t dimx, std::size_t dimy, std::size_t dimcov, typename float_t = double>
-class user_bswc_gpu {
+class user_bswc_gpu : public detail::user_core<nparts, dimx, dimy, float_t> {
 public:
-    using float_type = float_t;
     using state_vector = std::array<double, dimx>;
     using cov_vector = std::array<double, dimcov>;
     using func = std::function<double(const state_vector&, const cov_vector&)>;
-    explicit user_bswc_gpu(const std::vector<double>& theta, gpu_options o = gpu_options(), unsigned filter_id = auto_filter_id) {
-        std::int32_t dx = 0, dy = 0;
-        check(ssme_pf_user_model_dims(&dx, &dy));                      // SSME_ERR_UNSUPPORTED: the stock library was linked
-        if (dx != (std::int32_t)dimx || dy != (std::int32_t)dimy) throw std::invalid_argument("user_bswc_gpu: dimx / dimy are not the compiled-in model's");
-        if (ssme_pf_user_model_dim_cov() != (int)dimcov) throw std::invalid_argument("user_bswc_gpu: dimcov is not the compiled-in model's dim_cov");
-        h_ = handle(SSME_MODEL_USER0, (int)nparts, 1, o.seed, o.resampler, o.resamp_sched, o.device, detail::resolve_filter_id(filter_id));
-        check(ssme_pf_set_params(h_.get(), theta.data(), (std::int32_t)theta.size(), 1), h_.get());
-    }
+    explicit user_bswc_gpu(const std::vector<double>& theta, gpu_options o = gpu_options(), unsigned filter_id = auto_filter_id)
+        : detail::user_core<nparts, dimx, dimy, float_t>("user_bswc_gpu", (int)dimcov, theta, o, filter_id) {}
     // filter(obs, cov) / filter(obs, cov, fs): obs[j], j < dimy; cov[j], j < dimcov (an Eigen vector, a std::array, ...)
     template <typename Osv, typename Csv>
     void filter(const Osv& yt, const Csv& zt, const std::vector<func>& fs = std::vector<func>()) {
-        double y[dimy];
         cov_vector z;
-        for (std::size_t j = 0; j < dimy; ++j) y[j] = (double)yt[j];
         for (std::size_t j = 0; j < dimcov; ++j) z[j] = (double)zt[j];
-        double out = 0.0;
-        check(ssme_pf_step(h_.get(), y, z.data(), &out), h_.get());
-        last_ = (float_t)out;
-        expectations_.assign(fs.size(), 0.0);
-        if (!fs.empty()) {
-            std::vector<double> x(dimx * nparts), w(nparts);
-            check(ssme_pf_download_weights(h_.get(), 0, x.data(), w.data()), h_.get());
-            std::vector<double> num(fs.size(), 0.0);
-            double den = 0.0;
-            for (std::size_t i = 0; i < nparts; ++i) {
-                state_vector xi;
-                for (std::size_t d = 0; d < dimx; ++d) xi[d] = x[d * nparts + i];
-                for (std::size_t k = 0; k < fs.size(); ++k) num[k] += fs[k](xi, z) * w[i];
-                den += w[i];
-            }
-            for (std::size_t k = 0; k < fs.size(); ++k) expectations_[k] = num[k] / den;
-        }
-    }
-    float_t getLogCondLike() const { return last_; }
-    const std::vector<double>& getExpectations() const { return expectations_; }
-    // the n_h functionals the header declares, h(x_t, z_t), after the last filter(), summed on the device
-    std::vector<double> getModelExpectations() const {
-        const int n = ssme_pf_user_model_n_h();
-        if (n < 1) check(SSME_ERR_UNSUPPORTED, h_.get());
-        std::vector<double> out((std::size_t)n);
-        check(ssme_pf_get_user_expectations(h_.get(), out.data()), h_.get());
-        return out;
+        this->step(yt, z.data(), fs.size(), [&fs, &z](std::size_t k, const state_vector& xi) { return fs[k](xi, z); });
     }
     // sim_future_obs with the exogenous covariates of the horizons, future_covs[k * dimcov + j] (ssme_pf_sim_future_obs_cov):
     // y[time][component][particle], row-major.  Throws std::invalid_argument when future_covs is not num_steps * dimcov long.
     std::vector<double> sim_future_obs(unsigned num_steps, const std::vector<double>& future_covs) {
         if (future_covs.size() != (std::size_t)num_steps * dimcov) throw std::invalid_argument("user_bswc_gpu::sim_future_obs: num_steps * dimcov covariates");
         std::vector<double> y((std::size_t)num_steps * dimy * nparts);
-        check(ssme_pf_sim_future_obs_cov(h_.get(), (std::int32_t)num_steps, future_covs.data(), y.data(), nullptr, nullptr), h_.get());
+        check(ssme_pf_sim_future_obs_cov(this->native(), (std::int32_t)num_steps, future_covs.data(), y.data(), nullptr, nullptr), this->native());
         return y;
     }
-    ssme_pf_handle native() const { return h_.get(); }
-
-private:
-    handle h_;
-    float_t last_ = 0;
-    std::vector<double> expectations_;
 };
-
-// ---- expectations of host-side functionals ---------------------------------------------------------------------
-// Shared by the swarm-member models below.  h: any callable Mat(const Ssv&) (the covariate, if any, already bound).
-namespace detail {
-template <typename float_t, typename Mat, typename Ssv>
-struct functional_engine {
-    // Which device functional reproduces h?  Probed at six states; exact agreement required (exp(x/2): 4 ulp).
-    // Returns SSME_H_* (and the factor to apply to the device value) or -1 = evaluate on the host.
-    template <typename H>
-    static int classify(const H& h, double* scale) {
-        static const double probes[6] = {-1.7, -0.3125, 0.0, 0.5625, 1.9, 3.25};
-        bool is_const = true, is_x = true, is_x2 = true, is_vol = true;
-        float_t c0 = 0;
-        for (int p = 0; p < 6; ++p) {
-            Ssv xv;
-            xv(0) = (float_t)probes[p];
-            const Mat m = h(xv);
-            if (m.rows() != 1 || m.cols() != 1) return -1;
-            const float_t v = m(0, 0), xx = xv(0);
-            if (p == 0) c0 = v;
-            is_const = is_const && (v == c0);
-            is_x = is_x && (v == xx);
-            is_x2 = is_x2 && (v == xx * xx);
-            const float_t e = (float_t)std::exp((float_t)0.5 * xx);
-            is_vol = is_vol && (std::fabs(v - e) <= 4 * std::numeric_limits<float_t>::epsilon() * e);
-        }
-        *scale = 1.0;
-        if (is_const) { *scale = (double)c0 / 42.0; return SSME_H_CONST42; }   // E[c] = c E[42] / 42 (a NaN filter stays NaN)
-        if (is_x) return SSME_H_X;
-        if (is_x2) return SSME_H_X2;
-        if (is_vol) return SSME_H_VOL;
-        return -1;
-    }
-    // sum_i h(x_i) w_i / sum_i w_i on the host, any matrix shape (twin liu_west_filter.h:1662-1683)
-    template <typename H>
-    static Mat host_expectation(const H& h, const std::vector<double>& x, const std::vector<double>& w) {
-        std::vector<double> acc;
-        long rows = 0, cols = 0;
-        double wsum = 0.0;
-        for (std::size_t i = 0; i < x.size(); ++i) {
-            Ssv xv;
-            xv(0) = (float_t)x[i];
-            const Mat hv = h(xv);
-            if (i == 0) { rows = (long)hv.rows(); cols = (long)hv.cols(); acc.assign((std::size_t)(rows * cols), 0.0); }
-            for (long r = 0; r < rows; ++r)
-                for (long c = 0; c < cols; ++c) acc[(std::size_t)(r * cols + c)] += (double)hv(r, c) * w[i];
-            wsum += w[i];
-        }
-        Mat m(rows, cols);
-        for (long r = 0; r < rows; ++r)
-            for (long c = 0; c < cols; ++c) m(r, c) = (float_t)(acc[(std::size_t)(r * cols + c)] / wsum);
-        return m;
-    }
-    // E[h_i] for every h of `hs` after the last step of single-filter handle `hd`: device functionals in one pass,
-    // everything else on the host over ONE download of (x, weights).
-    template <typename H>
-    static std::vector<Mat> expectations(ssme_pf_handle hd, const std::vector<H>& hs, std::size_t nparts, bool probe,
-                                         const std::vector<int>& declared = std::vector<int>()) {
-        std::vector<Mat> out;
-        if (hs.empty()) return out;
-        std::vector<int> kind(hs.size(), -1);
-        std::vector<double> scale(hs.size(), 1.0);
-        std::vector<int32_t> ids;
-        for (std::size_t i = 0; i < hs.size(); ++i) {
-            if (i < declared.size() && declared[i] >= SSME_H_X && declared[i] <= SSME_H_CONST42) kind[i] = declared[i];
-            else if (probe) kind[i] = classify(hs[i], &scale[i]);
-            if (kind[i] >= 0 && ids.size() == 4) kind[i] = -1;           // more than 4 device functionals: the rest on the host
-            if (kind[i] >= 0) ids.push_back(kind[i]);
-        }
-        std::vector<double> dev(ids.size());
-        if (!ids.empty()) check(ssme_pf_get_expectations_multi(hd, ids.data(), (int32_t)ids.size(), dev.data()), hd);
-        std::vector<double> x, w;
-        std::size_t d = 0;
-        for (std::size_t i = 0; i < hs.size(); ++i) {
-            if (kind[i] >= 0) {
-                Mat m(1, 1);
-                m(0, 0) = (float_t)(dev[d++] * scale[i]);
-                out.push_back(m);
-            } else {
-                if (w.empty()) {
-                    x.resize(nparts); w.resize(nparts);
-                    check(ssme_pf_download_weights(hd, 0, x.data(), w.data()), hd);
-                }
-                out.push_back(host_expectation(hs[i], x, w));
-            }
-        }
-        return out;
-    }
-};
-}  // namespace detail
 
 // ---- swarm_context: ONE launch per observation behind the UNMODIFIED Swarm / SwarmWithCovs templates ----------------------
 // The reference's swarm calls filter(y_t[, z_t], fs) -> getExpectations() -> getLogCondLike() on every member, from the
@@ -510,15 +540,20 @@ public:
         idx_ = ctx->add_member(theta);
         probe_ = ctx->probe();
     }
-    // hs: the functionals with the covariate (if any) already bound
+    // hs: the functionals with the covariate (if any) already bound.  In a swarm_context the device slots are the context's
+    // (declared once for all members); a member of its own goes through dispatch_expectations.  Host sums are the same function.
     template <typename H>
     void step(double y, const double* z, const std::vector<H>& hs) {
+        std::vector<double> x, w;
+        // sum_i h(x_i) w_i / sum_i w_i, any matrix shape; the state is cast to float_t before h sees it
+        const auto host_mean = [&x, &w](const H& h) {
+            return weighted_mean<float_t, Mat>(x.size(), w, [&h, &x](std::size_t i) { Ssv xv; xv(0) = (float_t)x[i]; return h(xv); });
+        };
         if (ctx_) {
             ctx_->filter(idx_, steps_, y, z);
             ++steps_;
             last_ = (float_t)ctx_->log_cond_like(idx_);
             expectations_.clear();
-            std::vector<double> x, w;
             for (std::size_t j = 0; j < hs.size(); ++j) {
                 int slot = ctx_->device_slot(j);
                 if (slot >= 0) {
@@ -528,7 +563,7 @@ public:
                     continue;
                 }
                 if (w.empty()) ctx_->download(idx_, steps_, x, w);
-                expectations_.push_back(functional_engine<float_t, Mat, Ssv>::host_expectation(hs[j], x, w));
+                expectations_.push_back(host_mean(hs[j]));
             }
             return;
         }
@@ -536,7 +571,19 @@ public:
         double out = 0.0;
         check(ssme_pf_step(h_.get(), &y, z, &out), h_.get());
         last_ = (float_t)out;
-        expectations_ = functional_engine<float_t, Mat, Ssv>::expectations(h_.get(), hs, nparts, probe_, declared_);
+        const ssme_pf_handle hd = h_.get();
+        expectations_ = dispatch_expectations<float_t, Mat>(
+            hs.size(), declared_, bootstrap_policy, probe_,
+            [&hs](std::size_t j, double* scale) {
+                return classify<float_t>([&hs, j](float_t xx, const float_t*) { Ssv xv; xv(0) = xx; return hs[j](xv); }, 0, scale);
+            },
+            [hd](const std::vector<int32_t>& ids) {
+                std::vector<double> dev(ids.size());
+                check(ssme_pf_get_expectations_multi(hd, ids.data(), (int32_t)ids.size(), dev.data()), hd);
+                return dev;
+            },
+            [hd, &x, &w] { x.resize(nparts); w.resize(nparts); check(ssme_pf_download_weights(hd, 0, x.data(), w.data()), hd); },
+            [&hs, &host_mean](std::size_t j) { return host_mean(hs[j]); });
     }
     // y[time][particle] of this member (ssme_pf_sim_future_obs; in a swarm_context one device call serves all members)
     std::vector<double> sim_future_obs(unsigned num_steps, double last_obs) {
@@ -643,12 +690,9 @@ private:
 template <typename Pack, typename Data>
 double log_like_eval_gpu(const Pack& theta, const Data& data, int nparts, int num_pfilters, gpu_options o = gpu_options()) {
     if (data.empty()) throw std::length_error("can't read in data\n");   // estimate_univ_svol.h:112-113
-    std::vector<double> y(data.size());
-    for (std::size_t i = 0; i < data.size(); ++i) y[i] = (double)data[i](0);
+    const std::vector<double> y = detail::column0(data);
     handle h(SSME_MODEL_SVOL, nparts, num_pfilters, o.seed, o.resampler, o.resamp_sched, o.device, 0);
-    const double th[3] = {(double)theta.get_untrans_params(0, 0)(0), (double)theta.get_untrans_params(1, 1)(0),
-                          std::sqrt((double)theta.get_untrans_params(2, 2)(0))};
-    check(ssme_pf_set_params(h.get(), th, 3, 1), h.get());
+    check(ssme_pf_set_params(h.get(), detail::svol_theta(theta).data(), 3, 1), h.get());
     std::vector<double> ll((std::size_t)num_pfilters);
     check(ssme_pf_run_series(h.get(), y.data(), nullptr, (int)y.size(), ll.data()), h.get());
     double out = 0.0;
@@ -666,16 +710,14 @@ public:
     svol_log_like_evaluator(const Data& data, int nparts, int num_pfilters, gpu_options o = gpu_options())
         : h_(SSME_MODEL_SVOL, nparts, num_pfilters, o.seed, o.resampler, o.resamp_sched, o.device, 0), ll_((std::size_t)num_pfilters) {
         if (data.empty()) throw std::length_error("can't read in data\n");
-        y_.resize(data.size());
-        for (std::size_t i = 0; i < data.size(); ++i) y_[i] = (double)data[i](0);
+        y_ = detail::column0(data);
     }
     // theta in the reference's pack order: beta, phi, ss (sigma = sqrt(ss))
     template <typename Pack>
     double operator()(const Pack& theta, std::uint64_t seed) {
-        const double th[3] = {(double)theta.get_untrans_params(0, 0)(0), (double)theta.get_untrans_params(1, 1)(0),
-                              std::sqrt((double)theta.get_untrans_params(2, 2)(0))};
+        const std::array<double, 3> th = detail::svol_theta(theta);
         check(ssme_pf_set_seed(h_.get(), seed), h_.get());
-        check(ssme_pf_set_params(h_.get(), th, 3, 1), h_.get());
+        check(ssme_pf_set_params(h_.get(), th.data(), 3, 1), h_.get());
         check(ssme_pf_run_series(h_.get(), y_.data(), nullptr, (int)y_.size(), ll_.data()), h_.get());
         double out = 0.0;
         check(ssme_pf_log_mean_exp(h_.get(), &out), h_.get());
@@ -704,19 +746,6 @@ private:
 // gpu_options::probe_functionals opts into classification by six probe evaluations (see the header comment).  Mat = the caller's dynamic matrix
 // (Eigen::Matrix<float_t,-1,-1> in the reference); detail::small_matrix when none is given.
 namespace detail {
-template <typename T>
-class small_matrix {                                  // the least a dynamic matrix must offer here
-public:
-    small_matrix() = default;
-    small_matrix(long r, long c) : r_(r), c_(c), v_((std::size_t)(r * c), T(0)) {}
-    long rows() const { return r_; }
-    long cols() const { return c_; }
-    T& operator()(long i, long j) { return v_[(std::size_t)(i * c_ + j)]; }
-    const T& operator()(long i, long j) const { return v_[(std::size_t)(i * c_ + j)]; }
-private:
-    long r_ = 0, c_ = 0;
-    std::vector<T> v_;
-};
 // argument types of the two functional signatures
 template <typename F> struct lw_func_traits;
 template <typename M, typename S, typename C, typename P>
@@ -793,96 +822,51 @@ public:
     // (ssme_lw_sim_future_obs): y[time][particle], row-major.  last_obs = the last observation.
     std::vector<double> sim_future_obs(unsigned num_future_steps, double last_obs) {
         std::vector<double> y((std::size_t)num_future_steps * nparts);
-        const int rc = ssme_lw_sim_future_obs(h_.get(), (int32_t)num_future_steps, &last_obs, y.data(), nullptr, nullptr, nullptr);
-        if (rc != SSME_OK) throw std::runtime_error(std::string(ssme_pf_strerror(rc)) + " (" + ssme_lw_last_error(h_.get()) + ")");
+        lw_check(ssme_lw_sim_future_obs(h_.get(), (int32_t)num_future_steps, &last_obs, y.data(), nullptr, nullptr, nullptr));
         return y;
     }
     ssme_lw_handle native() const { return h_.get(); }
 
 private:
+    // the Liu-West calls' error: the status text and, always, what the handle recorded
+    void lw_check(int rc) const {
+        if (rc != SSME_OK) throw std::runtime_error(std::string(ssme_pf_strerror(rc)) + " (" + ssme_lw_last_error(h_.get()) + ")");
+    }
     void step(double y, double z) {
         double out = 0.0;
-        const int rc = ssme_lw_step(h_.get(), &y, &z, &out);
-        if (rc != SSME_OK) throw std::runtime_error(std::string(ssme_pf_strerror(rc)) + " (" + ssme_lw_last_error(h_.get()) + ")");
+        lw_check(ssme_lw_step(h_.get(), &y, &z, &out));
         last_ = (float_t)out;
     }
-    // Which built-in id reproduces h?  Six probes with distinct states and parameters; -1 = evaluate on the host.
-    template <typename F>
-    static int classify(const F& h, double z, double* scale) {
-        using T = detail::lw_func_traits<F>;
-        static const double px[6] = {-1.7, -0.3125, 0.0, 0.5625, 1.9, 3.25};
-        static const double pp[6][4] = {{0.91, -0.07, 0.021, -0.31}, {0.83, 0.02, 0.034, -0.12}, {0.95, 0.09, 0.077, -0.45},
-                                        {0.88, -0.03, 0.055, -0.02}, {0.97, 0.05, 0.012, -0.27}, {0.81, -0.09, 0.093, -0.38}};
-        bool is_const = true, is_x = true, is_x2 = true, is_vol = true, is_p[4] = {true, true, true, true};
-        float_t c0 = 0;
-        for (int q = 0; q < 6; ++q) {
-            typename T::Ssv xv; typename T::Psv pv;
-            xv(0) = (float_t)px[q];
-            for (int d = 0; d < 4; ++d) pv(d) = (float_t)pp[q][d];
-            const Mat m = T::call(h, xv, z, pv);
-            if (m.rows() != 1 || m.cols() != 1) return -1;
-            const float_t v = m(0, 0), xx = xv(0);
-            if (q == 0) c0 = v;
-            is_const = is_const && (v == c0);
-            is_x = is_x && (v == xx);
-            is_x2 = is_x2 && (v == xx * xx);
-            const float_t e = (float_t)std::exp((float_t)0.5 * xx);
-            is_vol = is_vol && (std::fabs(v - e) <= 4 * std::numeric_limits<float_t>::epsilon() * e);
-            for (int d = 0; d < 4; ++d) is_p[d] = is_p[d] && (v == pv(d));
-        }
-        *scale = 1.0;
-        if (is_const) { *scale = (double)c0 / 42.0; return SSME_H_CONST42; }
-        if (is_x) return SSME_H_X;
-        if (is_x2) return SSME_H_X2;
-        if (is_vol) return SSME_H_VOL;
-        for (int d = 0; d < 4; ++d) if (is_p[d]) return 4 + d;
-        return -1;
-    }
+    // declared / probed built-ins (0-3 of the state, 4-7 the parameters) on the device through getExpectations(ids), everything
+    // else summed on the host over one download of (x, untransformed theta, weights): detail::dispatch_expectations
     template <typename F>
     void compute_expectations(const std::vector<F>& fs, double z) {
         using T = detail::lw_func_traits<F>;
-        expectations_.clear();
-        if (fs.empty()) return;
-        std::vector<int> kind(fs.size(), -1);
-        std::vector<double> scale(fs.size(), 1.0);
-        std::vector<int32_t> ids;
-        for (std::size_t i = 0; i < fs.size(); ++i) {
-            if (i < declared_.size() && declared_[i] >= 0 && declared_[i] <= 7) kind[i] = declared_[i];    // 0-3 SSME_H_*, 4-7 phi, mu, sigma, rho
-            else if (probe_) kind[i] = classify(fs[i], z, &scale[i]);
-            if (kind[i] >= 0) ids.push_back(kind[i]);
-        }
-        const std::vector<double> dev = getExpectations(ids);
+        // f at state xx and parameters p[0..3], both already float_t
+        const auto at = [z](const F& f, float_t xx, const float_t* p) -> Mat {
+            typename T::Ssv xv; typename T::Psv pv;
+            xv(0) = xx;
+            for (int d = 0; d < 4; ++d) pv(d) = p[d];
+            return T::call(f, xv, z, pv);
+        };
         std::vector<double> x, th, w;
-        std::size_t d = 0;
-        for (std::size_t i = 0; i < fs.size(); ++i) {
-            if (kind[i] >= 0) {
-                Mat m(1, 1);
-                m(0, 0) = (float_t)(dev[d++] * scale[i]);
-                expectations_.push_back(m);
-                continue;
-            }
-            if (w.empty()) {       // one download of (x, untransformed theta, weights) serves every host functional
+        expectations_ = detail::dispatch_expectations<float_t, Mat>(
+            fs.size(), declared_, detail::liu_west_policy, probe_,
+            [&fs, &at](std::size_t j, double* scale) {
+                return detail::classify<float_t>([&fs, &at, j](float_t xx, const float_t* p) { return at(fs[j], xx, p); }, 4, scale);
+            },
+            [this](const std::vector<int32_t>& ids) { return getExpectations(ids); },
+            [this, &x, &th, &w] {
                 x.resize(nparts); th.resize(4 * nparts); w.resize(nparts);
-                check(ssme_lw_download_weights(h_.get(), 0, x.data(), th.data(), w.data()));
-            }
-            std::vector<double> acc;
-            long rows = 0, cols = 0;
-            double wsum = 0.0;
-            for (std::size_t p = 0; p < nparts; ++p) {
-                typename T::Ssv xv; typename T::Psv pv;
-                xv(0) = (float_t)x[p];
-                for (int q = 0; q < 4; ++q) pv(q) = (float_t)th[(std::size_t)q * nparts + p];
-                const Mat hv = T::call(fs[i], xv, z, pv);
-                if (p == 0) { rows = (long)hv.rows(); cols = (long)hv.cols(); acc.assign((std::size_t)(rows * cols), 0.0); }
-                for (long r = 0; r < rows; ++r)
-                    for (long c = 0; c < cols; ++c) acc[(std::size_t)(r * cols + c)] += (double)hv(r, c) * w[p];
-                wsum += w[p];
-            }
-            Mat m(rows, cols);
-            for (long r = 0; r < rows; ++r)
-                for (long c = 0; c < cols; ++c) m(r, c) = (float_t)(acc[(std::size_t)(r * cols + c)] / wsum);
-            expectations_.push_back(m);
-        }
+                lw_check(ssme_lw_download_weights(h_.get(), 0, x.data(), th.data(), w.data()));
+            },
+            [&fs, &at, &x, &th, &w](std::size_t j) {
+                return detail::weighted_mean<float_t, Mat>(nparts, w, [&fs, &at, &x, &th, j](std::size_t i) {
+                    float_t p[4];
+                    for (int q = 0; q < 4; ++q) p[q] = (float_t)th[(std::size_t)q * nparts + i];
+                    return at(fs[j], (float_t)x[i], p);
+                });
+            });
     }
 
     std::shared_ptr<ssme_lw_s> h_;
@@ -895,31 +879,24 @@ private:
 template <std::size_t nparts, typename float_t = double, typename Mat = detail::small_matrix<float_t>>
 using svol_lw_2_par_gpu = svol_lw_1_par_gpu<nparts, float_t, 1, Mat>;
 
-// ---- SwarmWithCovs over SVOL-leverage members (include/ssme/pswarm_filter.h:325-560; test/test_pswarm.cpp:146-208) ----
-// All nparamparts member filters live in ONE handle (n_filters = nparamparts, one theta row each): update(y, z) is one
-// launch; the swarm's log conditional likelihood and expectations are the plain averages over the members, as the
-// reference's intra/inter_agg_func compute them (:392-460).  samp_untrans_params() is the reference's pure virtual.
-template <std::size_t n_state_parts, std::size_t n_param_parts, typename float_t = double>
-class swarm_with_covs_gpu {
+// ---- the batched swarms: all nparamparts member filters in ONE handle --------------------------------------------------
+// (n_filters = nparamparts, one theta row each): an update is one launch; the swarm's log conditional likelihood and
+// expectations are the plain averages over the members, as the reference's intra/inter_agg_func compute them
+// (pswarm_filter.h:392-460).  samp_untrans_params() is the reference's pure virtual.  detail::swarm_impl is everything the
+// two public classes share; they add the model, the order of its parameters and the signature of update().
+namespace detail {
+template <std::size_t n_state_parts, std::size_t n_param_parts, typename float_t>
+class swarm_impl {
 public:
     using float_type = float_t;
     using func = int;                                            // SSME_H_* functional id
-    explicit swarm_with_covs_gpu(const std::vector<func>& fs, gpu_options o = gpu_options()) : fs_(fs), opt_(o) {}
-    virtual ~swarm_with_covs_gpu() = default;
-    virtual std::vector<float_t> samp_untrans_params() = 0;      // order phi, mu, sigma, rho
-
-    template <typename Osv, typename Csv>
-    void update(const Osv& yt, const Csv& zt) {
-        if (!h_) finish_construction();
-        const double y = (double)yt(0), z = (double)zt(0);
-        check(ssme_pf_step(h_.get(), &y, &z, nullptr), h_.get());
-        aggregate();
-        ++num_obs_;
-    }
+    virtual ~swarm_impl() = default;
+    virtual std::vector<float_t> samp_untrans_params() = 0;      // in the order the public class states
     float_t getLogCondLike() const { return log_cond_like_; }
     std::vector<double> getExpectations() const { return expectations_; }
-    // SwarmWithCovs::simFutureObs (pswarm_filter.h:547-553): sim_future_obs of every member, here ONE device call for all of them.
-    // Returns y[member][time][particle], row-major ("param, time, then state particle", :49-50).  last_obs = the last observation.
+    // Swarm / SwarmWithCovs::simFutureObs (pswarm_filter.h:247-253, 547-553): sim_future_obs of every member, here ONE device call
+    // for all of them.  Returns y[member][time][particle], row-major ("param, time, then state particle", :49-50).
+    // last_obs = the last observation (read by the leverage model only).
     std::vector<double> simFutureObs(unsigned num_future_steps, double last_obs = 0.0) {
         if (!h_) finish_construction();
         const std::vector<double> lo(n_param_parts, last_obs);
@@ -927,8 +904,18 @@ public:
         check(ssme_pf_sim_future_obs(h_.get(), (int32_t)num_future_steps, lo.data(), y.data(), nullptr, nullptr), h_.get());
         return y;
     }
-    const std::vector<double>& params() const { return theta_; }         // [n_param_parts][4]
     ssme_pf_handle native() const { return h_.get(); }                  // the one handle of all members (null before the first update)
+
+protected:
+    // order[d] = which entry of samp_untrans_params() is parameter d of the C ABI; what = the message for a vector of another length
+    swarm_impl(int model, std::vector<int> order, const char* what, const std::vector<func>& fs, const gpu_options& o)
+        : model_(model), order_(std::move(order)), what_(what), fs_(fs), opt_(o) {}
+    void step(double y, const double* z) {                        // z = nullptr: no covariate
+        if (!h_) finish_construction();
+        check(ssme_pf_step(h_.get(), &y, z, nullptr), h_.get());
+        aggregate();
+    }
+    std::vector<double> theta_;                                   // [n_param_parts][order.size()], C ABI order
 
 private:
     // intra/inter_agg_func (pswarm_filter.h:96-160): plain means over the members, reduced on the device, one download
@@ -941,82 +928,55 @@ private:
         log_cond_like_ = (float_t)lcl;
     }
     void finish_construction() {                                  // pswarm_filter.h:280-304
-        theta_.resize(n_param_parts * 4);
+        const std::size_t n_theta = order_.size();
+        theta_.resize(n_param_parts * n_theta);
         for (std::size_t i = 0; i < n_param_parts; ++i) {
             const std::vector<float_t> p = samp_untrans_params();
-            if (p.size() != 4) throw std::invalid_argument("samp_untrans_params must return phi, mu, sigma, rho");
-            for (int d = 0; d < 4; ++d) theta_[i * 4 + d] = (double)p[d];
+            if (p.size() != n_theta) throw std::invalid_argument(what_);
+            for (std::size_t d = 0; d < n_theta; ++d) theta_[i * n_theta + d] = (double)p[(std::size_t)order_[d]];
         }
-        h_ = handle(SSME_MODEL_SVOL_LEVERAGE, (int)n_state_parts, (int)n_param_parts, opt_.seed, opt_.resampler, opt_.resamp_sched,
-                    opt_.device, 0, detail::dtype_of<float_t>());
-        check(ssme_pf_set_params(h_.get(), theta_.data(), 4, (int)n_param_parts), h_.get());
+        h_ = handle(model_, (int)n_state_parts, (int)n_param_parts, opt_.seed, opt_.resampler, opt_.resamp_sched, opt_.device, 0,
+                    dtype_of<float_t>());
+        check(ssme_pf_set_params(h_.get(), theta_.data(), (int)n_theta, (int)n_param_parts), h_.get());
     }
-    std::vector<func> fs_;
-    gpu_options opt_;
-    handle h_;
-    std::vector<double> theta_, expectations_;
-    float_t log_cond_like_ = 0;
-    unsigned num_obs_ = 0;
-};
-
-// ---- Swarm over univariate-SVOL members (include/ssme/pswarm_filter.h:23-320: the variant without covariates) ---------
-// update(y) = filter(y, fs) on every member, plain averages over members; parameters in the model's ctor order of
-// svol_bs: samp_untrans_params() returns (phi, beta, sigma) (univ_svol_bootstrap_filter.h:34).
-template <std::size_t n_state_parts, std::size_t n_param_parts, typename float_t = double>
-class swarm_gpu {
-public:
-    using float_type = float_t;
-    using func = int;
-    explicit swarm_gpu(const std::vector<func>& fs, gpu_options o = gpu_options()) : fs_(fs), opt_(o) {}
-    virtual ~swarm_gpu() = default;
-    virtual std::vector<float_t> samp_untrans_params() = 0;      // phi, beta, sigma
-
-    template <typename Osv>
-    void update(const Osv& yt) {
-        if (!h_) finish_construction();
-        const double y = (double)yt(0);
-        check(ssme_pf_step(h_.get(), &y, nullptr, nullptr), h_.get());
-        aggregate();
-    }
-    float_t getLogCondLike() const { return log_cond_like_; }
-    std::vector<double> getExpectations() const { return expectations_; }
-    // Swarm::simFutureObs (pswarm_filter.h:247-253): sim_future_obs of every member, here ONE device call for all of them.
-    // Returns y[member][time][particle], row-major ("param, time, then state particle", :49-50).
-    std::vector<double> simFutureObs(unsigned num_future_steps, double last_obs = 0.0) {
-        if (!h_) finish_construction();
-        const std::vector<double> lo(n_param_parts, last_obs);
-        std::vector<double> y(n_param_parts * (std::size_t)num_future_steps * n_state_parts);
-        check(ssme_pf_sim_future_obs(h_.get(), (int32_t)num_future_steps, lo.data(), y.data(), nullptr, nullptr), h_.get());
-        return y;
-    }
-    ssme_pf_handle native() const { return h_.get(); }                  // the one handle of all members (null before the first update)
-
-private:
-    // intra/inter_agg_func (pswarm_filter.h:96-160): plain means over the members, reduced on the device, one download
-    void aggregate() {
-        if (fs_.size() > 4) throw std::invalid_argument("at most 4 device functionals per swarm");
-        std::vector<int32_t> ids(fs_.begin(), fs_.end());
-        double lcl = 0.0;
-        expectations_.assign(fs_.size(), 0.0);
-        check(ssme_pf_swarm_aggregate(h_.get(), ids.data(), (int32_t)ids.size(), &lcl, expectations_.data()), h_.get());
-        log_cond_like_ = (float_t)lcl;
-    }
-    void finish_construction() {
-        std::vector<double> theta(n_param_parts * 3);
-        for (std::size_t i = 0; i < n_param_parts; ++i) {
-            const std::vector<float_t> p = samp_untrans_params();
-            if (p.size() != 3) throw std::invalid_argument("samp_untrans_params must return phi, beta, sigma");
-            theta[i * 3 + 0] = (double)p[1]; theta[i * 3 + 1] = (double)p[0]; theta[i * 3 + 2] = (double)p[2];   // C ABI order: beta, phi, sigma
-        }
-        h_ = handle(SSME_MODEL_SVOL, (int)n_state_parts, (int)n_param_parts, opt_.seed, opt_.resampler, opt_.resamp_sched, opt_.device, 0,
-                    detail::dtype_of<float_t>());
-        check(ssme_pf_set_params(h_.get(), theta.data(), 3, (int)n_param_parts), h_.get());
-    }
+    int model_;
+    std::vector<int> order_;
+    const char* what_;
     std::vector<func> fs_;
     gpu_options opt_;
     handle h_;
     std::vector<double> expectations_;
     float_t log_cond_like_ = 0;
+};
+}  // namespace detail
+
+// SwarmWithCovs over SVOL-leverage members (include/ssme/pswarm_filter.h:325-560; test/test_pswarm.cpp:146-208):
+// samp_untrans_params() returns (phi, mu, sigma, rho), the C ABI's own order.
+template <std::size_t n_state_parts, std::size_t n_param_parts, typename float_t = double>
+class swarm_with_covs_gpu : public detail::swarm_impl<n_state_parts, n_param_parts, float_t> {
+public:
+    explicit swarm_with_covs_gpu(const std::vector<int>& fs, gpu_options o = gpu_options())
+        : detail::swarm_impl<n_state_parts, n_param_parts, float_t>(SSME_MODEL_SVOL_LEVERAGE, {0, 1, 2, 3},
+                                                                     "samp_untrans_params must return phi, mu, sigma, rho", fs, o) {}
+    template <typename Osv, typename Csv>
+    void update(const Osv& yt, const Csv& zt) {
+        const double z = (double)zt(0);
+        this->step((double)yt(0), &z);
+    }
+    const std::vector<double>& params() const { return this->theta_; }   // [n_param_parts][4]
+};
+
+// Swarm over univariate-SVOL members (include/ssme/pswarm_filter.h:23-320: the variant without covariates): update(y) =
+// filter(y, fs) on every member; parameters in the model's ctor order of svol_bs: samp_untrans_params() returns
+// (phi, beta, sigma) (univ_svol_bootstrap_filter.h:34), the C ABI takes (beta, phi, sigma).
+template <std::size_t n_state_parts, std::size_t n_param_parts, typename float_t = double>
+class swarm_gpu : public detail::swarm_impl<n_state_parts, n_param_parts, float_t> {
+public:
+    explicit swarm_gpu(const std::vector<int>& fs, gpu_options o = gpu_options())
+        : detail::swarm_impl<n_state_parts, n_param_parts, float_t>(SSME_MODEL_SVOL, {1, 0, 2},
+                                                                     "samp_untrans_params must return phi, beta, sigma", fs, o) {}
+    template <typename Osv>
+    void update(const Osv& yt) { this->step((double)yt(0), nullptr); }
 };
 
 // ---- headerless CSV -> rows of doubles (utils::read_data, include/ssme/utils.h:25-64) -------------------------------

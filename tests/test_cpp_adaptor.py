@@ -118,6 +118,18 @@ def test_adaptor_matches_oracle(oracle, spy):
     assert int(n) == spy.size and float(first) == spy[0]
 
 
+def test_functional_host_helpers(tmp_path):
+    """The classifier, the weighted mean and the dispatch of the adaptor's functionals (namespace detail of the header) on hand-made
+    inputs with exact expected values: tests/cpp/test_functional_host.cpp needs no device and exits non-zero on a mismatch."""
+    from ssme_amd import build
+    so = build.build()
+    exe = str(tmp_path / "test_functional_host")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-pthread", os.path.join(ROOT, "tests", "cpp", "test_functional_host.cpp"),
+                           "-o", exe, so, "-Wl,-rpath," + os.path.dirname(so)])
+    p = subprocess.run([exe], capture_output=True, text=True)
+    assert p.returncode == 0 and p.stdout.strip() == "functional_host ok", p.stdout + p.stderr
+
+
 def test_pmmh_harness_compiles():
     from ssme_amd import build
     so = build.build()
