@@ -731,6 +731,46 @@ private:
     std::vector<double> y_, ll_;
 };
 
+// The same for a model of the caller's own (the library built with a user model header, model_api.h): one handle of num_pfilters
+// replicate filters of nparts particles, the whole series per evaluation through ssme_pf_run_series -- one launch per evaluation
+// for a filter of at most 2048 particles, vector states included (ssme_pf_get_series_route on native() says which route).
+// y: T rows of dimy values (row-major); z: T rows of dimcov covariates when dimcov > 0, empty otherwise.  Dimensions are checked
+// against the compiled-in model as user_bs_gpu / user_bswc_gpu check them (std::invalid_argument); empty data is std::length_error.
+template <std::size_t dimx, std::size_t dimy, std::size_t dimcov = 0>
+class user_log_like_evaluator {
+public:
+    user_log_like_evaluator(const std::vector<double>& y, const std::vector<double>& z, int nparts, int num_pfilters,
+                            gpu_options o = gpu_options())
+        : y_(y), z_(z), ll_((std::size_t)(num_pfilters > 0 ? num_pfilters : 0)) {
+        std::int32_t dx = 0, dy = 0;
+        check(ssme_pf_user_model_dims(&dx, &dy));                      // SSME_ERR_UNSUPPORTED: the stock library was linked
+        if (dx != (std::int32_t)dimx || dy != (std::int32_t)dimy) throw std::invalid_argument("user_log_like_evaluator: dimx / dimy are not the compiled-in model's");
+        if (ssme_pf_user_model_dim_cov() != (int)dimcov) throw std::invalid_argument("user_log_like_evaluator: dimcov is not the compiled-in model's dim_cov");
+        if (y.empty()) throw std::length_error("can't read in data\n");
+        if (y.size() % dimy != 0) throw std::invalid_argument("user_log_like_evaluator: y holds T rows of dimy values");
+        T_ = y.size() / dimy;
+        if (z.size() != T_ * dimcov) throw std::invalid_argument("user_log_like_evaluator: z holds T rows of dimcov values");
+        h_ = handle(SSME_MODEL_USER0, nparts, num_pfilters, o.seed, o.resampler, o.resamp_sched, o.device, 0);
+    }
+    // theta: the model's untransformed parameters (n_theta of its header), shared by the replicates
+    double operator()(const std::vector<double>& theta, std::uint64_t seed) {
+        check(ssme_pf_set_seed(h_.get(), seed), h_.get());
+        check(ssme_pf_set_params(h_.get(), theta.data(), (std::int32_t)theta.size(), 1), h_.get());
+        check(ssme_pf_run_series(h_.get(), y_.data(), dimcov > 0 ? z_.data() : nullptr, (std::int32_t)T_, ll_.data()), h_.get());
+        double out = 0.0;
+        check(ssme_pf_log_mean_exp(h_.get(), &out), h_.get());
+        return out;
+    }
+    const std::vector<double>& logliks() const { return ll_; }          // the replicates' log-likelihoods of the last evaluation
+    float device_ms() const { float ms = 0; ssme_pf_last_elapsed_ms(h_.get(), &ms); return ms; }
+    ssme_pf_handle native() const { return h_.get(); }
+
+private:
+    handle h_;
+    std::vector<double> y_, z_, ll_;
+    std::size_t T_ = 0;
+};
+
 // ---- svol_lw_1_par / svol_lw_2_par (Liu-West filters) ------------------------------------------------------------
 // test/test_liu_west.cpp:22-157: ctor (delta, phi_l, phi_u, mu_l, mu_u, sig_l, sig_u, rho_l, rho_u[, dte]);
 // filter(y, z[, fs]), getLogCondLike(), getExpectations() (liu_west_filter.h:971-1159).  Transforms as svol_lw_1_par passes

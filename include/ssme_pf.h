@@ -226,8 +226,14 @@ int ssme_pf_set_debug(ssme_pf_handle h, int32_t flags);
 int ssme_pf_set_tuning(ssme_pf_handle h, int32_t threads_per_tile);
 
 /* Filters of one tile (N <= 2048) run ssme_pf_run_series as ONE launch that loops over the series with the state in
- * LDS (default 1); 0 forces the tiled per-step kernel.  Results are bit-identical either way (parity tests). */
+ * LDS (the default, vector user models included: all dim_x planes live in LDS); 0 forces the tiled per-step kernel, 1 the
+ * one-launch kernels.  Results are bit-identical either way (parity tests). */
 int ssme_pf_set_small_series(ssme_pf_handle h, int32_t enable);
+/* What ssme_pf_run_series launches for this handle as it is configured now: the tiled step kernel (threads per tile), or one of
+ * the two whole-series kernels of one-tile filters -- one particle per lane (N <= 512) or one particle pair per lane -- and the
+ * threads of its one workgroup per filter.  Needs no prior step.  Sharded handles: SSME_ERR_STATE, as for ssme_pf_run_series. */
+enum { SSME_ROUTE_TILED = 0, SSME_ROUTE_SERIES_LANE = 1, SSME_ROUTE_SERIES_PAIR = 2 };
+int ssme_pf_get_series_route(ssme_pf_handle h, int32_t* route, int32_t* threads_per_block);
 /* Execution policy of run_series: 0 = eager launches, 1 = one hipGraph per series (default). */
 int ssme_pf_set_graph_mode(ssme_pf_handle h, int32_t mode);
 

@@ -34,8 +34,9 @@
 //     static __device__ double logg_vec(const ssme::ModelConst& c, const double* y, const double* x, const ssme::ExpTabEntry* etab);
 // INSTEAD of prop / logg.  Particles are stored as dim_x planes ([dim_x][n_filters][N]; ssme_pf_download_state returns them in that
 // order), a series is T rows of dim_y values, component 0 of the normals is the pair's Box-Muller draw of the scalar kernels and
-// component d >= 1 comes from one more Philox call per particle pair (counter stream STREAM_XDIM + d).  Such a model runs on the
-// tiled step kernel at every N (no whole-series kernel), unsharded; device functionals see component 0.
+// component d >= 1 comes from one more Philox call per particle pair (counter stream STREAM_XDIM + d).  Such a model is unsharded;
+// at N <= 2048 ssme_pf_run_series runs its whole series in one launch with all dim_x planes in LDS, like a scalar model
+// (pf_small.h; ssme_pf_get_series_route says which route a handle takes); device functionals see component 0.
 // tests/models/svol_two_factor.h is the test model (two volatility factors, two observed series).
 //
 // FUNCTIONALS of the model's own (optional; getExpectations() of the functions h the reference's callers pass to filter(y[, z], fs),
@@ -82,7 +83,7 @@
 //     functionals  h(c, x, double zcov, etab, out)                  h(c, x, const double* zcov, etab, out)
 // filter(y_t, z_t) uses the same z_t for fSamp into x_t and for logGEv of y_t, as BSFilterWC::filter does; one z_t serves all filters
 // of a handle; z = NULL means zeros.  Callers pass K values per step (ssme_pf_step) or z[t * K + j] (ssme_pf_run_series); h receives
-// the covariates of the last step.  A scalar dim_cov model of at most 2048 particles still runs the whole series in one launch.
+// the covariates of the last step.  A dim_cov model of at most 2048 particles, scalar or vector, still runs the whole series in one launch.
 // FIRST STEP of its own (optional, dim_cov headers only; both or neither -- one without the other is a static_assert):
 //     static __device__ void first(const ssme::ModelConst& c, const double* zn /*dim_x*/, const double* y /*dim_y*/,
 //                                  const double* zcov, double* x0 /*dim_x*/, const ssme::ExpTabEntry* etab);           // q1Samp(y1, z1)

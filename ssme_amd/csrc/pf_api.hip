@@ -40,7 +40,7 @@ struct ssme_pf_s : HandleCore {
     double* yz_step;         // device [2]: y and z of the step API, uploaded by ONE copy
     int32_t* ticket;         // device [R]: arrival counters of the step API's in-kernel accounting (zero between launches)
     int num_cus;             // compute units of the device (priority schedule of the step kernel)
-    int small_series;        // 1: one-tile filters run the whole series in one launch (k_filter_series_small)
+    int small_series;        // 1: one-tile filters run the whole series in one launch (pf_small.h; series_route decides)
     double y_step_v[3];      // step API: components 1 .. of this call's vector observation
     double z_step_v[3];      // ... and covariates 1 .. of a user model with dim_cov > 1
     int dx, dy;              // state / observation dimension: 1, or the user model's dim_x / dim_y (model_api.h)
@@ -399,16 +399,30 @@ static void enqueue_step(ssme_pf_handle h, int t, int yi, int gi, bool has_z, bo
 }
 
 // whole series in one launch for one-tile filters (pf_small.h); reads buffers `cur`-independent, writes x[1] etc.
+// What ssme_pf_run_series launches for an unsharded handle as it is configured now: the ONE place that decides it
+// (ssme_pf_run_series, launch_small_m and ssme_pf_get_series_route all ask here).
+// Vector user models take the whole-series kernels by default like every other model: measured for (lane | pair kernel) x
+// dim_x = 2, 3, 4 at N = 100 .. 2000, the route is 1.6 to 10 us per step faster than the tiled kernel at every shape, against a
+// spread of the tiled kernel's own passes of 0.01 to 0.04 us (profiles/vector_series_timing.txt).
+struct SeriesRoute { int route, threads, pairs; };   // SSME_ROUTE_*; threads per workgroup; pairs per lane (pair kernel), 0 otherwise
+static SeriesRoute series_route(const ssme_pf_s* h) {
+    const SeriesRoute tiled = {SSME_ROUTE_TILED, h->nt, 0};
+    if (!(h->B == 1 && h->tile == kTile && h->small_series)) return tiled;
+    // one particle per lane up to 512 particles (twice the waves, about half the chain per wave: N = 100 3.0 -> 2.2 us per step,
+    // N = 500 3.3 -> 3.1); pairs above (N = 1000: 4.6 against 4.9 us; profiles/r02_small_series.txt)
+    if (h->N <= 512) return {SSME_ROUTE_SERIES_LANE, h->N <= 64 ? 64 : (h->N <= 128 ? 128 : (h->N <= 256 ? 256 : 512)), 0};
+    return {SSME_ROUTE_SERIES_PAIR, 512, h->N <= 1024 ? 1 : 2};
+}
 template <int MODEL>
 static void launch_small_m(ssme_pf_handle h, const StepArgs& a, int T) {
     const dim3 grid(h->R);
-    // one particle per lane up to 512 particles (twice the waves, about half the chain per wave: N = 100 3.0 -> 2.2 us per step,
-    // N = 500 3.3 -> 3.1); pairs above (N = 1000: 4.6 against 4.9 us; profiles/r02_small_series.txt)
-    if (h->N <= 64) hipLaunchKernelGGL((k_filter_series_lane<MODEL, 64>), grid, dim3(64), 0, h->stream, a, T);
-    else if (h->N <= 128) hipLaunchKernelGGL((k_filter_series_lane<MODEL, 128>), grid, dim3(128), 0, h->stream, a, T);
-    else if (h->N <= 256) hipLaunchKernelGGL((k_filter_series_lane<MODEL, 256>), grid, dim3(256), 0, h->stream, a, T);
-    else if (h->N <= 512) hipLaunchKernelGGL((k_filter_series_lane<MODEL, 512>), grid, dim3(512), 0, h->stream, a, T);
-    else if (h->N <= 1024) hipLaunchKernelGGL((k_filter_series_small<MODEL, 512, 1>), grid, dim3(512), 0, h->stream, a, T);
+    const SeriesRoute s = series_route(h);
+    if (s.route == SSME_ROUTE_SERIES_LANE) {
+        if (s.threads == 64) hipLaunchKernelGGL((k_filter_series_lane<MODEL, 64>), grid, dim3(64), 0, h->stream, a, T);
+        else if (s.threads == 128) hipLaunchKernelGGL((k_filter_series_lane<MODEL, 128>), grid, dim3(128), 0, h->stream, a, T);
+        else if (s.threads == 256) hipLaunchKernelGGL((k_filter_series_lane<MODEL, 256>), grid, dim3(256), 0, h->stream, a, T);
+        else hipLaunchKernelGGL((k_filter_series_lane<MODEL, 512>), grid, dim3(512), 0, h->stream, a, T);
+    } else if (s.pairs == 1) hipLaunchKernelGGL((k_filter_series_small<MODEL, 512, 1>), grid, dim3(512), 0, h->stream, a, T);
     else hipLaunchKernelGGL((k_filter_series_small<MODEL, 512, 2>), grid, dim3(512), 0, h->stream, a, T);
 }
 static void enqueue_series_small(ssme_pf_handle h, int T, bool has_z) {
@@ -594,7 +608,6 @@ static int create_impl(const ssme_pf_config* cfg, int shard_rank, int shard_worl
     dims_of(cfg->model, &h->dx, &h->dy);
     h->kcov = kcov_of(cfg->model);
     h->kz = h->kcov > 0 ? h->kcov : 1;
-    if (h->dx > 1 || h->dy > 1) h->small_series = 0;             // vector models run the tiled step kernel at every N
     with_model(cfg->model, [&](auto m) { h->kern = step_kernels<decltype(m)::value>(tile); });
     h->nt = h->kern.nt;
     hipError_t e = hipSetDevice(cfg->device);
@@ -1038,7 +1051,16 @@ int ssme_pf_set_tuning(ssme_pf_handle h, int32_t threads_per_tile) {
 
 int ssme_pf_set_small_series(ssme_pf_handle h, int32_t enable) {
     if (!h || enable < 0 || enable > 1) return SSME_ERR_INVALID_ARG;
-    h->small_series = (h->dx > 1 || h->dy > 1) ? 0 : enable;      // vector models have no whole-series kernel
+    h->small_series = enable;
+    return SSME_OK;
+}
+
+int ssme_pf_get_series_route(ssme_pf_handle h, int32_t* route, int32_t* threads_per_block) {
+    if (!h || !route || !threads_per_block) return SSME_ERR_INVALID_ARG;
+    if (h->shard_world > 0) return SSME_ERR_STATE;     // sharded handles are driven by ssme_pf_shard_*
+    const SeriesRoute s = series_route(h);
+    *route = s.route;
+    *threads_per_block = s.threads;
     return SSME_OK;
 }
 
@@ -1122,7 +1144,7 @@ int ssme_pf_run_series(ssme_pf_handle h, const double* y, const double* z, int32
     if (rc != SSME_OK) return rc;
     const bool has_z = z != nullptr;
     const int lw = logw_needed(h) ? 1 : 0;
-    if (h->B == 1 && h->tile == kTile && h->small_series) {
+    if (series_route(h).route != SSME_ROUTE_TILED) {
         HIPCHK(hipEventRecord(h->ev0, h->stream));
         enqueue_series_small(h, T, has_z);
         HIPCHK(hipEventRecord(h->ev1, h->stream));

@@ -347,6 +347,31 @@ __device__ __forceinline__ double scalar_step(const ModelConst& c, bool first_st
     }
 }
 
+// One filter step of one particle of a VECTOR user model (dim_x or dim_y > 1): xn[dim_x] <- the model's first step (first of a
+// dim_cov header that declares it, init_vec otherwise) or prop_vec from x[dim_x] and the normals zn[dim_x]; returns the increment of
+// the particle's log-weight, -inf for a `bad` filter (the model is called first, the select applied afterwards).  y: dim_y values;
+// zcov / zc as in scalar_step.  The one text k_filter_step and both whole-series kernels (pf_small.h) run for such a model.
+template <int MODEL>
+__device__ __forceinline__ double vector_step(const ModelConst& c, bool first_step, const double* x, const double* zn, const double* y,
+                                              double zcov, const CovVals<model_kcov<MODEL>()>& zc, double* xn, const ExpTabEntry* etab) {
+#if SSME_HAS_USER_MODEL
+    using M = typename user_model_of<MODEL>::type;
+    if constexpr (model_kcov<MODEL>() > 0) return cov_step<M>(c, first_step, x, zn, y, zc.v, xn, etab);
+    else {
+        using UC = user_calls<M>;
+        if (first_step) UC::init_vec(c, zn, xn);
+        else UC::prop_vec(c, x, zn, zcov, xn, etab);
+        return c.bad ? -dinf() : UC::logg_vec(c, y, xn, etab);
+    }
+#else
+    return 0.0;          // no vector model without a user model: never instantiated
+#endif
+}
+// the normals of state component d >= 1 of particle pair `pair` at time t: one more Philox call per pair and component
+__device__ __forceinline__ u32x4 xdim_words(uint32_t pair, uint32_t t, uint32_t rep, int d, uint32_t k0, uint32_t k1) {
+    return philox4x32_10(pair, t, rep, (uint32_t)(STREAM_XDIM + d), k0, k1);
+}
+
 // two standard normals for the pair `pair` at time t (Box-Muller)
 __device__ __forceinline__ void normal_pair(uint32_t pair, uint32_t t, uint32_t rep, uint32_t k0, uint32_t k1,
                                             double* z0, double* z1) {
@@ -1274,7 +1299,7 @@ __global__ __launch_bounds__(NT) void k_filter_step(const StepArgs a) {
             znd[0][0] = zn[k][0]; znd[0][1] = zn[k][1];
 #pragma unroll
             for (int d = 1; d < DX; ++d) {
-                const u32x4 o = philox4x32_10((uint32_t)(b * (TILE / 2) + k * NT + tid), (uint32_t)a.t, rep, (uint32_t)(STREAM_XDIM + d), key0, key1);
+                const u32x4 o = xdim_words((uint32_t)(b * (TILE / 2) + k * NT + tid), (uint32_t)a.t, rep, d, key0, key1);
                 pair_normals(o.v0, o.v1, &lds_dtab, &znd[d][0], &znd[d][1]);
             }
 #pragma unroll
@@ -1285,14 +1310,7 @@ __global__ __launch_bounds__(NT) void k_filter_step(const StepArgs a) {
                 for (int d = 1; d < DX; ++d) xv[d] = first_step ? 0.0 : a.x_in[(size_t)d * a.xplane + rowoff + (size_t)srcv[k][c]];
 #pragma unroll
                 for (int d = 0; d < DX; ++d) zv[d] = znd[d][c];
-                double gv;
-                if constexpr (KC > 0) gv = cov_step<typename user_model_of<MODEL>::type>(mc, first_step, xv, zv, yv, zc.v, xn, lds_etab);
-                else {
-                    using UC = user_calls<typename user_model_of<MODEL>::type>;
-                    if (first_step) UC::init_vec(mc, zv, xn);
-                    else UC::prop_vec(mc, xv, zv, zcov, xn, lds_etab);
-                    gv = mc.bad ? -dinf() : UC::logg_vec(mc, yv, xn, lds_etab);
-                }
+                const double gv = vector_step<MODEL>(mc, first_step, xv, zv, yv, zcov, zc, xn, lds_etab);
                 xo[c] = xn[0];
 #pragma unroll
                 for (int d = 1; d < DX; ++d) xov[d][c] = xn[d];

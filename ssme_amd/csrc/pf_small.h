@@ -12,22 +12,50 @@
 //
 // Two kernels, one particle pair per lane (k_filter_series_small) and one particle per lane (k_filter_series_lane), built
 // from the same pieces: a step is prefetch (SeriesInputs), level-2 (one_tile_level2), draws, targets (target_of), search
-// (count_less_radix8) and gather, model step (scalar_step), maximum, weights and scan, publish; after the loop
-// series_accounting and hand_over_state.
+// (count_less_radix8) and gather, model step (scalar_step; vector_step for a vector user model), maximum, weights and scan, publish;
+// after the loop series_accounting and hand_over_state.
+//
+// A vector user model (dim_x or dim_y > 1, model_api.h) runs the same two kernels: `if constexpr` on model_dx / model_dy adds the
+// planes d >= 1 of the state to LDS (lds_x[DX][P]: at most (4 + 1) x 2048 x 8 B + tables = 84 KiB at (dim_x, N) = (4, 2048), one
+// workgroup per CU), their normals (xdim_words) and the DY values of an observation row; component 0 and everything about the weights
+// is the scalar text.  Shapes are the scalar models' (512 threads x 1 or 2 pairs; lanes up to 512): no instantiation of the four test
+// headers spills a VGPR (profiles/vector_series_kernels.txt).
 #pragma once
 #include "pf_kernels.h"
+
+#ifndef SSME_LANE_XDIM_AHEAD
+#define SSME_LANE_XDIM_AHEAD 1             // lane kernel, vector models: the d >= 1 normals of step t + 1 are drawn during step t, as
+#endif                                     // component 0's are (0: at the model step).  Same bits.  Measured both ways: within 0.06 us per
+                                           // step of each other in either direction, except the dim_cov model (2.28 against 2.41 us at
+                                           // N = 100 ahead): kept ahead (profiles/vector_series_timing.txt, section 2)
 
 namespace ssme {
 
 // The inputs of a step that do not depend on the filter's state, requested one step ahead (uniform scalar loads).
-template <int KC>
-struct SeriesInputs {
-    double y, z;                 // observation; scalar covariate (0 without one)
+// Components 1 .. DY-1 of a vector observation (a row of a series is DY values); nothing for a scalar one.
+template <int DY>
+struct ObsTail {
+    double yv[DY - 1];
+    __device__ __forceinline__ void load_tail(const double* y, int row) {
+#pragma unroll
+        for (int d = 1; d < DY; ++d) yv[d - 1] = y[row * DY + d];
+    }
+    __device__ __forceinline__ double tail(int d) const { return yv[d - 1]; }
+};
+template <>
+struct ObsTail<1> {
+    __device__ __forceinline__ void load_tail(const double*, int) {}
+    __device__ __forceinline__ double tail(int) const { return 0.0; }
+};
+template <int KC, int DY = 1>
+struct SeriesInputs : ObsTail<DY> {
+    double y, z;                 // observation (component 0 of a vector one); scalar covariate (0 without one)
     CovVals<KC> zc;              // dim_cov user model: its KC covariates take the scalar one's place
     double gam, pgam, G;         // sorted-multinomial resampling steps: Gamma of tile 0, the prefix before it, the total (B = 1)
 
     __device__ __forceinline__ void load_row(const StepArgs& a, int r, int row) {
-        y = a.y[row];
+        y = a.y[row * DY];
+        this->load_tail(a.y, row);
         if (a.z) {                   // a series without covariates keeps the zeros of load_first
             if constexpr (KC > 0) zc.load(a.z, (size_t)row);
             else z = a.z[row];
@@ -48,7 +76,31 @@ struct SeriesInputs {
     __device__ __forceinline__ void request(const StepArgs& a, int r, int row, int T) {
         if (row < T) load_row(a, r, row);
     }
+    // the DY values of the observation, as the vector callbacks take them
+    __device__ __forceinline__ void obs(double* yv) const {
+        yv[0] = y;
+#pragma unroll
+        for (int d = 1; d < DY; ++d) yv[d] = this->tail(d);
+    }
 };
+
+// One step of one particle of a vector model inside the series kernels: vector_step on component 0 from the scalar path (x0, zn0)
+// and components d >= 1 from xv / znv (slot 0 of both unused); the new components d >= 1 return in xnv[d], component 0 in *xn0.
+template <int MODEL, class IN>
+__device__ __forceinline__ double series_vector_step(const ModelConst& mc, bool first_step, double x0, double zn0, const double* xv,
+                                                     const double* znv, const IN& in, double* xn0, double* xnv, const ExpTabEntry* etab) {
+    constexpr int DX = model_dx<MODEL>();
+    double x[kMaxDim], zn[kMaxDim], y[kMaxDim], xn[kMaxDim];
+    x[0] = x0; zn[0] = zn0;
+#pragma unroll
+    for (int d = 1; d < DX; ++d) { x[d] = xv[d]; zn[d] = znv[d]; }
+    in.obs(y);
+    const double g = vector_step<MODEL>(mc, first_step, x, zn, y, in.z, in.zc, xn, etab);
+    *xn0 = xn[0];
+#pragma unroll
+    for (int d = 1; d < DX; ++d) xnv[d] = xn[d];
+    return g;
+}
 
 // Level-2 of a filter of one tile (level2_scan for B = 1) from the previous step's tile sum and maximum: m, S = A' and
 // R0 = A / A'.  Thread 0 records (m, S) at ms_t; the logarithm is taken after the loop (series_accounting).
@@ -183,20 +235,26 @@ __device__ __forceinline__ void series_accounting(const StepArgs& a, int r, int 
 
 // State hand-over after the series, as k_filter_step leaves it: a lane's NK runs of PPT slots (x, lw: [NK][PPT], slot
 // (k NT + tid) PPT), the cdf from LDS, and beyond P = NT NK PPT: x = 0, cdf flat at the tile sum, log-weight -inf.
-template <int NT, int NK, int PPT>
-__device__ __forceinline__ void hand_over_state(const StepArgs& a, size_t rowoff, const double* x, const double* lw,
+// A vector state: xv holds components 1 .. DX-1 as [DX][NK][PPT] (slot 0 unused); plane d goes to x_out + d * xplane, zeros up
+// to the tile end in every plane.
+template <int NT, int NK, int PPT, int DX = 1>
+__device__ __forceinline__ void hand_over_state(const StepArgs& a, size_t rowoff, const double* x, const double* xv, const double* lw,
                                                 const double* lds_cdf, double A_prev) {
     const int tid = threadIdx.x;
 #pragma unroll
     for (int k = 0; k < NK; ++k) {
         const int i = (k * NT + tid) * PPT;
         store_slots<PPT>(a.x_out + rowoff + i, x + k * PPT);
+#pragma unroll
+        for (int d = 1; d < DX; ++d) store_slots<PPT>(a.x_out + (size_t)d * a.xplane + rowoff + i, xv + (d * NK + k) * PPT);
         store_slots<PPT>(a.cdf_out + rowoff + i, lds_cdf + i);
         if (a.logw) store_slots<PPT>(a.logw + rowoff + i, lw + k * PPT);
     }
     const double zero[2] = {0.0, 0.0}, flat[2] = {A_prev, A_prev}, ninf[2] = {-dinf(), -dinf()};
     for (int i = (NT * NK + tid) * PPT; i < kTile; i += NT * PPT) {
         store_slots<PPT>(a.x_out + rowoff + i, zero);
+#pragma unroll
+        for (int d = 1; d < DX; ++d) store_slots<PPT>(a.x_out + (size_t)d * a.xplane + rowoff + i, zero);
         store_slots<PPT>(a.cdf_out + rowoff + i, flat);
         if (a.logw) store_slots<PPT>(a.logw + rowoff + i, ninf);
     }
@@ -210,7 +268,12 @@ __device__ __forceinline__ void hand_over_state(const StepArgs& a, size_t rowoff
 template <int MODEL, int NT, int NK>
 __global__ __launch_bounds__(NT) void k_filter_series_small(const StepArgs a, const int T) {
     constexpr int P = 2 * NT * NK;
-    __shared__ __attribute__((aligned(16))) double lds_x[P];
+    // A vector user model (model_api.h): component 0 travels the scalar path below unchanged; components d >= 1 live in planes
+    // lds_x + d P, are gathered at the same ancestor, and draw their normals from stream STREAM_XDIM + d (xdim_words) for the
+    // pair index k NT + tid, as k_filter_step's VEC branch does with B = 1.
+    constexpr int DX = model_dx<MODEL>(), DY = model_dy<MODEL>();
+    constexpr bool VEC = DX > 1 || DY > 1;
+    __shared__ __attribute__((aligned(16))) double lds_x[DX * P];
     __shared__ __attribute__((aligned(16))) double lds_cdf[P];
     __shared__ double lds_seg_a[16];
     __shared__ double lds_seg_c[16];
@@ -232,8 +295,15 @@ __global__ __launch_bounds__(NT) void k_filter_series_small(const StepArgs a, co
     double xcur[NK][2], lwcur[NK][2];
 #pragma unroll
     for (int k = 0; k < NK; ++k) { xcur[k][0] = 0.0; xcur[k][1] = 0.0; lwcur[k][0] = 0.0; lwcur[k][1] = 0.0; }
+    double xcv[DX][NK][2];                             // components d >= 1 of the lane's particles (slot 0 unused)
+    if constexpr (DX > 1) {
+#pragma unroll
+        for (int d = 1; d < DX; ++d)
+#pragma unroll
+            for (int k = 0; k < NK; ++k) { xcv[d][k][0] = 0.0; xcv[d][k][1] = 0.0; }
+    }
     double A_prev = 0.0, mb_prev = 0.0;
-    SeriesInputs<model_kcov<MODEL>()> in_n;
+    SeriesInputs<model_kcov<MODEL>(), DY> in_n;
     in_n.load_first(a, r);
 
     for (int t = 0; t < T; ++t) {
@@ -271,6 +341,13 @@ __global__ __launch_bounds__(NT) void k_filter_series_small(const StepArgs a, co
         }
 
         double xin[NK][2], lw_old[NK][2];
+        double xinv[DX][NK][2];                        // vector state: the inputs of components d >= 1 (nothing is read at t = 0)
+        if constexpr (DX > 1) {
+#pragma unroll
+            for (int d = 1; d < DX; ++d)
+#pragma unroll
+                for (int k = 0; k < NK; ++k) { xinv[d][k][0] = (t == 0) ? 0.0 : xcv[d][k][0]; xinv[d][k][1] = (t == 0) ? 0.0 : xcv[d][k][1]; }
+        }
         if (t == 0) {
 #pragma unroll
             for (int k = 0; k < NK; ++k) { xin[k][0] = 0.0; xin[k][1] = 0.0; lw_old[k][0] = 0.0; lw_old[k][1] = 0.0; }
@@ -314,6 +391,10 @@ __global__ __launch_bounds__(NT) void k_filter_series_small(const StepArgs a, co
                     const int anc = jj[c] < a.N - 1 ? jj[c] : a.N - 1;
                     if (a.anc && (i0 + c) < a.N) a.anc[rowoff + i0 + c] = (uint32_t)anc;
                     xin[k][c] = lds_x[anc];
+                    if constexpr (DX > 1) {            // every plane at the one clamped ancestor
+#pragma unroll
+                        for (int d = 1; d < DX; ++d) xinv[d][k][c] = lds_x[d * P + anc];
+                    }
                     lw_old[k][c] = 0.0;
                 }
             }
@@ -326,11 +407,26 @@ __global__ __launch_bounds__(NT) void k_filter_series_small(const StepArgs a, co
 #pragma unroll
         for (int k = 0; k < NK; ++k) {
             const int i0 = (k * NT + tid) * 2;
+            double znv[DX][2];                         // vector state: the pair's normals of components d >= 1
+            if constexpr (DX > 1) {
+#pragma unroll
+                for (int d = 1; d < DX; ++d) {
+                    const u32x4 o = xdim_words((uint32_t)(k * NT + tid), (uint32_t)t, rep, d, key0, key1);
+                    pair_normals(o.v0, o.v1, &lds_dtab, &znv[d][0], &znv[d][1]);
+                }
+            }
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
-                double xn;
-                const double l = lw_old[k][c] + scalar_step<MODEL>(mc, t == 0, xin[k][c], zn[k][c], in.y, in.z, in.zc, &xn, lds_etab);
+                double xn, l;
                 const bool valid = (i0 + c) < a.N;
+                if constexpr (VEC) {
+                    double xv[DX], zv[DX], xnv[DX];
+#pragma unroll
+                    for (int d = 1; d < DX; ++d) { xv[d] = xinv[d][k][c]; zv[d] = znv[d][c]; }
+                    l = lw_old[k][c] + series_vector_step<MODEL>(mc, t == 0, xin[k][c], zn[k][c], xv, zv, in, &xn, xnv, lds_etab);
+#pragma unroll
+                    for (int d = 1; d < DX; ++d) xcv[d][k][c] = valid ? xnv[d] : 0.0;
+                } else l = lw_old[k][c] + scalar_step<MODEL>(mc, t == 0, xin[k][c], zn[k][c], in.y, in.z, in.zc, &xn, lds_etab);
                 xcur[k][c] = valid ? xn : 0.0;
                 lg[k][c] = valid ? l : -dinf();
                 if (valid) { nan = nan || (l != l); mx = (l > mx) ? l : mx; }
@@ -353,6 +449,8 @@ __global__ __launch_bounds__(NT) void k_filter_series_small(const StepArgs a, co
             const int i0 = (k * NT + tid) * 2;
             store_slots<2>(lds_cdf + i0, inc[k]);
             store_slots<2>(lds_x + i0, xcur[k]);
+#pragma unroll
+            for (int d = 1; d < DX; ++d) store_slots<2>(lds_x + d * P + i0, xcv[d][k]);
         }
         A_prev = total;
         mb_prev = mb;
@@ -360,7 +458,7 @@ __global__ __launch_bounds__(NT) void k_filter_series_small(const StepArgs a, co
     }
 
     series_accounting<NT>(a, r, T, ms, A_prev, mb_prev, lds_etab);
-    hand_over_state<NT, NK, 2>(a, rowoff, &xcur[0][0], &lwcur[0][0], lds_cdf, A_prev);
+    hand_over_state<NT, NK, 2, DX>(a, rowoff, &xcur[0][0], &xcv[0][0][0], &lwcur[0][0], lds_cdf, A_prev);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -373,7 +471,10 @@ __global__ __launch_bounds__(NT) void k_filter_series_small(const StepArgs a, co
 template <int MODEL, int NT>
 __global__ __launch_bounds__(NT) void k_filter_series_lane(const StepArgs a, const int T) {
     constexpr int P = NT;
-    __shared__ double lds_x[P];
+    // A vector user model: as in the pair kernel; the pair index of the d >= 1 draws is tid >> 1 and the lane keeps half tid & 1.
+    constexpr int DX = model_dx<MODEL>(), DY = model_dy<MODEL>();
+    constexpr bool VEC = DX > 1 || DY > 1;
+    __shared__ double lds_x[DX * P];
     __shared__ double lds_cdf[P];
     __shared__ double lds_seg[2][16];                 // the weights' scan and the spacings' scan, behind one barrier
     __shared__ double lds_d2[16];
@@ -395,8 +496,11 @@ __global__ __launch_bounds__(NT) void k_filter_series_lane(const StepArgs a, con
     double* ms = a.small_ms + (size_t)r * a.Tcap * 2;
 
     double xcur = 0.0, lwcur = 0.0;
+    double xcv[DX];                                   // components d >= 1 of the lane's particle (slot 0 unused)
+#pragma unroll
+    for (int d = 1; d < DX; ++d) xcv[d] = 0.0;
     double A_prev = 0.0, mb_prev = 0.0;
-    SeriesInputs<model_kcov<MODEL>()> in_n;
+    SeriesInputs<model_kcov<MODEL>(), DY> in_n;
     in_n.load_first(a, r);
 
     // The draws of a step do not depend on the filter's state, and at one or two waves per SIMD the step is a chain of dependent
@@ -404,7 +508,18 @@ __global__ __launch_bounds__(NT) void k_filter_series_lane(const StepArgs a, con
     // block that waits for the search's LDS reads, and the spacings' block scan shares the barrier of the weights' scan
     // (block_scan_lanes_f64).  Carried to the next iteration: the normal, the spacing's inclusive sum and the total.  Same arithmetic.
     double zn_n = 0.0, le_n = 0.0, se_n = 1.0, qe_n = 0.0;
+    double znv_n[DX];                                 // vector state: the lane's normals of components d >= 1, drawn with component 0's
+    auto draw_xdim = [&](int tn, double (&out)[DX]) {
+#pragma unroll
+        for (int d = 1; d < DX; ++d) {
+            const u32x4 o = xdim_words((uint32_t)(tid >> 1), (uint32_t)tn, rep, d, key0, key1);
+            double z0, z1;
+            pair_normals(o.v0, o.v1, &lds_dtab, &z0, &z1);
+            out[d] = c ? z1 : z0;
+        }
+    };
     auto draw_for = [&](int tn) {
+        if constexpr (DX > 1 && SSME_LANE_XDIM_AHEAD) draw_xdim(tn, znv_n);
         // the pair's Philox call: words 0-1 -> Box-Muller (this lane keeps cos or sin), words 2 / 3 -> this lane's spacing
         const u32x4 o = pair_words((uint32_t)(tid >> 1), (uint32_t)tn, rep, key0, key1);
         double z0, z1;
@@ -420,6 +535,15 @@ __global__ __launch_bounds__(NT) void k_filter_series_lane(const StepArgs a, con
         const auto in = in_n;
         in_n.request(a, r, t + 1, T);
         const double zn = zn_n, le = le_n, se = se_n;
+        double znv[DX], xinv[DX];
+        if constexpr (DX > 1) {
+            if constexpr (SSME_LANE_XDIM_AHEAD) {
+#pragma unroll
+                for (int d = 1; d < DX; ++d) znv[d] = znv_n[d];
+            }
+#pragma unroll
+            for (int d = 1; d < DX; ++d) xinv[d] = (t == 0) ? 0.0 : xcv[d];       // nothing is read at t = 0; the lane's own otherwise
+        }
         const bool resampled = (t > 0) && (t % a.resamp_sched == 0);
 
         // --- level-2 of step t-1: one_tile_level2's text, written out.  Called as the function (struct or reference results) this
@@ -468,11 +592,21 @@ __global__ __launch_bounds__(NT) void k_filter_series_lane(const StepArgs a, con
             const int anc = jj[0] < a.N - 1 ? jj[0] : a.N - 1;
             if (a.anc && valid) a.anc[rowoff + tid] = (uint32_t)anc;
             xin = lds_x[anc];
+            if constexpr (DX > 1) {                            // every plane at the one clamped ancestor
+#pragma unroll
+                for (int d = 1; d < DX; ++d) xinv[d] = lds_x[d * P + anc];
+            }
         }
 
         // --- fSamp / q1Samp, logGEv, tile max ---
-        double xn;
-        const double l = lw_old + scalar_step<MODEL>(mc, t == 0, xin, zn, in.y, in.z, in.zc, &xn, lds_etab);
+        double xn, l;
+        if constexpr (VEC) {
+            double xnv[DX];
+            if constexpr (DX > 1 && !SSME_LANE_XDIM_AHEAD) draw_xdim(t, znv);
+            l = lw_old + series_vector_step<MODEL>(mc, t == 0, xin, zn, xinv, znv, in, &xn, xnv, lds_etab);
+#pragma unroll
+            for (int d = 1; d < DX; ++d) xcv[d] = valid ? xnv[d] : 0.0;
+        } else l = lw_old + scalar_step<MODEL>(mc, t == 0, xin, zn, in.y, in.z, in.zc, &xn, lds_etab);
         xcur = valid ? xn : 0.0;
         const double lg = valid ? l : -dinf();
         lwcur = lg;
@@ -487,13 +621,15 @@ __global__ __launch_bounds__(NT) void k_filter_series_lane(const StepArgs a, con
         le_n = sinc[1]; se_n = stot[1];
         lds_cdf[tid] = sinc[0];
         lds_x[tid] = xcur;
+#pragma unroll
+        for (int d = 1; d < DX; ++d) lds_x[d * P + tid] = xcv[d];
         A_prev = stot[0];
         mb_prev = mb;
         __syncthreads();                                              // cdf / x of step t visible to step t+1
     }
 
     series_accounting<NT>(a, r, T, ms, A_prev, mb_prev, lds_etab);
-    hand_over_state<NT, 1, 1>(a, rowoff, &xcur, &lwcur, lds_cdf, A_prev);
+    hand_over_state<NT, 1, 1, DX>(a, rowoff, &xcur, xcv, &lwcur, lds_cdf, A_prev);
 }
 
 }  // namespace ssme

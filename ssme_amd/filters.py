@@ -106,8 +106,16 @@ class ParticleFilterBank:
         self._chk(capi.lib().ssme_pf_reset(self._h))
 
     def set_small_series(self, enable=True):
-        """One-tile filters (N <= 2048): whole series in one launch (default) or the tiled per-step kernel."""
+        """One-tile filters (N <= 2048): whole series in one launch (the default; vector user models included) or the tiled
+        per-step kernel.  series_route() says which one run_series takes."""
         self._chk(capi.lib().ssme_pf_set_small_series(self._h, 1 if enable else 0))
+
+    def series_route(self):
+        """(route, threads per block) of what run_series launches for this handle as it is configured now (ssme_pf_get_series_route):
+        ROUTE_TILED, ROUTE_SERIES_LANE (one particle per lane) or ROUTE_SERIES_PAIR (one pair per lane).  Needs no prior step."""
+        route, threads = C.c_int32(), C.c_int32()
+        self._chk(capi.lib().ssme_pf_get_series_route(self._h, C.byref(route), C.byref(threads)))
+        return route.value, threads.value
 
     def set_seed(self, seed):
         """New random stream for the next evaluation (a fresh likelihood estimate per PMMH proposal); resets the filters."""
