@@ -700,6 +700,16 @@ double log_like_eval_gpu(const Pack& theta, const Data& data, int nparts, int nu
     return out;
 }
 
+namespace detail {
+// rows 0 .. T-1 of the last recorded series of a handle: [(t * n + i) * R + r] (ssme_pf_get_series_[user_]expectations)
+inline std::vector<double> series_rows(ssme_pf_handle h, std::size_t T, std::size_t n, std::size_t R, bool user) {
+    std::vector<double> out(T * (n ? n : 1) * R);
+    check(user ? ssme_pf_get_series_user_expectations(h, out.data(), (std::int32_t)T)
+               : ssme_pf_get_series_expectations(h, out.data(), (std::int32_t)T), h);
+    return out;
+}
+}  // namespace detail
+
 // ---- persistent evaluator: one handle, one captured graph, a fresh random stream per call --------------------------
 // The PMMH caller evaluates log_like_eval once per MCMC iteration (ada_pmmh_mvn.h:344,363 through thread_pool::work).
 // Constructing a model per evaluation (estimate_univ_svol.h:119) costs device allocations and a graph capture; this
@@ -719,16 +729,26 @@ public:
         check(ssme_pf_set_seed(h_.get(), seed), h_.get());
         check(ssme_pf_set_params(h_.get(), th.data(), 3, 1), h_.get());
         check(ssme_pf_run_series(h_.get(), y_.data(), nullptr, (int)y_.size(), ll_.data()), h_.get());
+        n_run_ = n_rec_;                                   // what THIS series recorded: series_expectations() is sized from it
         double out = 0.0;
         check(ssme_pf_log_mean_exp(h_.get(), &out), h_.get());
         return out;
     }
     float device_ms() const { float ms = 0; ssme_pf_last_elapsed_ms(h_.get(), &ms); return ms; }
     ssme_pf_handle native() const { return h_.get(); }
+    // The filtered path: record E[h(x_t) | y_{1:t}] of the built-in functionals `ids` (SSME_H_*, at most 4; none: off) at every step of
+    // the evaluations that follow; series_expectations() is valid after operator(): [(t * ids + i) * num_pfilters + r].  It returns the
+    // rows of the LAST evaluation, with the ids that were set when it ran, whatever record_expectations was told since.
+    void record_expectations(const std::vector<std::int32_t>& ids) {
+        check(ssme_pf_set_series_expectations(h_.get(), ids.empty() ? nullptr : ids.data(), (std::int32_t)ids.size(), 0), h_.get());
+        n_rec_ = ids.size();                               // after the check: a rejected list changes nothing
+    }
+    std::vector<double> series_expectations() const { return detail::series_rows(h_.get(), y_.size(), n_run_, ll_.size(), false); }
 
 private:
     handle h_;
     std::vector<double> y_, ll_;
+    std::size_t n_rec_ = 0, n_run_ = 0;                    // built-in functionals set for the next evaluation / recorded by the last one
 };
 
 // The same for a model of the caller's own (the library built with a user model header, model_api.h): one handle of num_pfilters
@@ -757,6 +777,7 @@ public:
         check(ssme_pf_set_seed(h_.get(), seed), h_.get());
         check(ssme_pf_set_params(h_.get(), theta.data(), (std::int32_t)theta.size(), 1), h_.get());
         check(ssme_pf_run_series(h_.get(), y_.data(), dimcov > 0 ? z_.data() : nullptr, (std::int32_t)T_, ll_.data()), h_.get());
+        n_run_ = ids_.size();                              // what THIS series recorded: series_expectations() is sized from it
         double out = 0.0;
         check(ssme_pf_log_mean_exp(h_.get(), &out), h_.get());
         return out;
@@ -764,11 +785,28 @@ public:
     const std::vector<double>& logliks() const { return ll_; }          // the replicates' log-likelihoods of the last evaluation
     float device_ms() const { float ms = 0; ssme_pf_last_elapsed_ms(h_.get(), &ms); return ms; }
     ssme_pf_handle native() const { return h_.get(); }
+    // The filtered path, as svol_log_like_evaluator records it: the built-in functionals `ids` (they see component 0 of the state) and /
+    // or all n_h functionals of the model's header, which receive the covariates of row t.  Valid after operator():
+    // series_expectations()[(t * ids + i) * num_pfilters + r], series_user_expectations()[(t * n_h + k) * num_pfilters + r]: the rows of
+    // the LAST evaluation, with the ids that were set when it ran, whatever the two record calls were told since.
+    void record_expectations(const std::vector<std::int32_t>& ids) { apply_recording(ids, user_); }
+    void record_user_expectations(bool on = true) { apply_recording(ids_, on); }
+    std::vector<double> series_expectations() const { return detail::series_rows(h_.get(), T_, n_run_, ll_.size(), false); }
+    std::vector<double> series_user_expectations() const {
+        return detail::series_rows(h_.get(), T_, (std::size_t)ssme_pf_user_model_n_h(), ll_.size(), true);
+    }
 
 private:
+    void apply_recording(const std::vector<std::int32_t>& ids, bool user) {
+        check(ssme_pf_set_series_expectations(h_.get(), ids.empty() ? nullptr : ids.data(), (std::int32_t)ids.size(), user ? 1 : 0), h_.get());
+        const std::vector<std::int32_t> keep = ids;        // after the check: a rejected request changes nothing (ids may alias ids_)
+        ids_ = keep; user_ = user;
+    }
     handle h_;
     std::vector<double> y_, z_, ll_;
-    std::size_t T_ = 0;
+    std::vector<std::int32_t> ids_;                        // set for the next evaluation
+    bool user_ = false;
+    std::size_t T_ = 0, n_run_ = 0;                        // n_run_: built-in functionals the last evaluation recorded
 };
 
 // ---- svol_lw_1_par / svol_lw_2_par (Liu-West filters) ------------------------------------------------------------

@@ -193,6 +193,26 @@ int ssme_pf_swarm_aggregate_threads(ssme_pf_handle h, const int32_t* functionals
 int ssme_pf_user_model_n_h(void);
 int ssme_pf_get_user_expectations(ssme_pf_handle h, double* out /* [n_h][R] */);
 int ssme_pf_swarm_aggregate_user(ssme_pf_handle h, int32_t num_threads, double* mean_logcondlike /*1*/, double* mean_expectations /*n_h*/);
+/* The filtered PATH: E[h(x_t) | y_{1:t}] for every step t of ssme_pf_run_series (the reference calls filter(y_t, fs) and
+ * getExpectations() at every step, pswarm_filter.h:87-89,383-385), recorded by the series itself -- the whole-series kernels of
+ * one-tile filters form the rows in LDS, the tiled route queues the expectation kernels behind every step, graph or eager.
+ * ssme_pf_set_series_expectations: record the n built-in functionals (0 .. 4 ids SSME_H_X .. SSME_H_CONST42) and, with
+ * user != 0, all n_h functionals of the compiled-in user model at every step of the run_series calls that follow.  n = 0 and
+ * user = 0 switch recording off (the default of a new handle; nothing about a non-recording run changes).  The setting survives
+ * run_series, set_params, set_seed and reset; a cached graph of another recording configuration is dropped.  Validated before any
+ * HIP call: NULL handle, an id out of range, n < 0 or n > 4, n > 0 with NULL functionals: SSME_ERR_INVALID_ARG; user != 0 on a handle
+ * whose model is not SSME_MODEL_USER0 or in a library with n_h == 0: SSME_ERR_UNSUPPORTED; sharded handles: SSME_ERR_STATE.
+ * ssme_pf_get_series_expectations / ssme_pf_get_series_user_expectations: rows 0 .. T-1 of the last run_series,
+ * out[(t*n + i)*R + r] / out[(t*n_h + k)*R + r].  Row t is, to the bit, what ssme_pf_get_expectations_multi /
+ * ssme_pf_get_user_expectations return after step t of a handle stepped with ssme_pf_step: the pre-resampling weights of step t
+ * at any resamp_sched, the covariates of row t for the user model's h, NaN where the filter's weights are NaN, infinite or all
+ * zero (the call still returns SSME_OK).  NULL arguments, T < 1 or T beyond the last recorded series: SSME_ERR_INVALID_ARG; nothing
+ * recorded of that kind (recording off during the last run_series, or no run_series yet): SSME_ERR_STATE.  SSME_F32 handles round
+ * the rows to float.  ssme_pf_step neither records nor clears.  The trajectory (T (n + n_h) R doubles on the device) exists only
+ * while recording is on. */
+int ssme_pf_set_series_expectations(ssme_pf_handle h, const int32_t* functionals, int32_t n, int32_t user);
+int ssme_pf_get_series_expectations(ssme_pf_handle h, double* out /* [T][n][R] */, int32_t T);
+int ssme_pf_get_series_user_expectations(ssme_pf_handle h, double* out /* [T][n_h][R] */, int32_t T);
 /* Arbitrary host-side h (the reference's filt_func is a std::function, pswarm_filter.h:44,87-89): particles x (N,
  * nullable) and weights w (N) of one filter after the last step, w_j = exp(logw_j - max logw) in the 2^-41 fixed point
  * the resampler and ssme_pf_get_expectations use; the caller forms sum h(x_j) w_j / sum w_j.  Needs no debug mode. */

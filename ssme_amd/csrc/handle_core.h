@@ -101,16 +101,19 @@ static int fail(HandleCore* h, const char* what, hipError_t e) {
 // held is freed first (growth).
 enum class Mem { device, zeroed, pinned };   // pinned: host memory, device-mapped
 template <class T>
+static void own_free(HandleCore* h, T*& p) {
+    if (!p) return;
+    for (size_t i = 0; i < h->owned.size(); ++i)
+        if (h->owned[i].first == p) {
+            if (h->owned[i].second) hipHostFree(p); else hipFree(p);
+            h->owned.erase(h->owned.begin() + i);
+            break;
+        }
+    p = nullptr;
+}
+template <class T>
 static hipError_t own_alloc(HandleCore* h, T*& p, size_t bytes, Mem kind = Mem::device) {
-    if (p) {
-        for (size_t i = 0; i < h->owned.size(); ++i)
-            if (h->owned[i].first == p) {
-                if (h->owned[i].second) hipHostFree(p); else hipFree(p);
-                h->owned.erase(h->owned.begin() + i);
-                break;
-            }
-        p = nullptr;
-    }
+    own_free(h, p);
     void* q = nullptr;
     hipError_t e = kind == Mem::pinned ? hipHostMalloc(&q, bytes, hipHostMallocMapped) : hipMalloc(&q, bytes);
     if (e != hipSuccess) return e;

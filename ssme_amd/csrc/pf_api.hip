@@ -71,6 +71,14 @@ struct ssme_pf_s : HandleCore {
     // graph cache
     hipGraphExec_t gexec;
     int g_T, g_has_z, g_debug, g_logw, g_nt;
+    FunctionalIds g_rec_fs;      // ... and the recording configuration it was captured with
+    int g_rec_user;
+    // recorded series (ssme_pf_set_series_expectations): E[h(x_t) | y_{1:t}] of every step of a run_series
+    FunctionalIds rec_fs;        // built-in functionals to record (n = 0: none)
+    int rec_user;                // 1: the user model's n_h functionals too
+    double *traj, *utraj;        // [traj_cap][rec_fs.n][R], [traj_cap][n_h][R]; held only while recording is on
+    int traj_cap, traj_n;        // time rows both hold; built-in functionals traj was sized for
+    int rec_T, rec_n, rec_nh;    // what the last run_series recorded: rows, built-in functionals, user functionals
     std::vector<ModelConst> h_mc;
     // forecast (HandleCore::fc): fc.x0 is [dx][R][Npad], the samples fc.y / fc.x [R][H][dy][Ns] / [R][H][dx][Ns]
     std::vector<double> h_gscale;    // per filter: scale of the observation draw (set_params)
@@ -413,18 +421,21 @@ static SeriesRoute series_route(const ssme_pf_s* h) {
     if (h->N <= 512) return {SSME_ROUTE_SERIES_LANE, h->N <= 64 ? 64 : (h->N <= 128 ? 128 : (h->N <= 256 ? 256 : 512)), 0};
     return {SSME_ROUTE_SERIES_PAIR, 512, h->N <= 1024 ? 1 : 2};
 }
-template <int MODEL>
-static void launch_small_m(ssme_pf_handle h, const StepArgs& a, int T) {
+// rec: nothing, or the SeriesRec of a recording handle -- the third kernel argument of the recording instantiations (pf_small.h)
+template <int MODEL, class... REC>
+static void launch_small_m(ssme_pf_handle h, const StepArgs& a, int T, const REC&... rec) {
     const dim3 grid(h->R);
     const SeriesRoute s = series_route(h);
     if (s.route == SSME_ROUTE_SERIES_LANE) {
-        if (s.threads == 64) hipLaunchKernelGGL((k_filter_series_lane<MODEL, 64>), grid, dim3(64), 0, h->stream, a, T);
-        else if (s.threads == 128) hipLaunchKernelGGL((k_filter_series_lane<MODEL, 128>), grid, dim3(128), 0, h->stream, a, T);
-        else if (s.threads == 256) hipLaunchKernelGGL((k_filter_series_lane<MODEL, 256>), grid, dim3(256), 0, h->stream, a, T);
-        else hipLaunchKernelGGL((k_filter_series_lane<MODEL, 512>), grid, dim3(512), 0, h->stream, a, T);
-    } else if (s.pairs == 1) hipLaunchKernelGGL((k_filter_series_small<MODEL, 512, 1>), grid, dim3(512), 0, h->stream, a, T);
-    else hipLaunchKernelGGL((k_filter_series_small<MODEL, 512, 2>), grid, dim3(512), 0, h->stream, a, T);
+        if (s.threads == 64) hipLaunchKernelGGL((k_filter_series_lane<MODEL, 64, REC...>), grid, dim3(64), 0, h->stream, a, T, rec...);
+        else if (s.threads == 128) hipLaunchKernelGGL((k_filter_series_lane<MODEL, 128, REC...>), grid, dim3(128), 0, h->stream, a, T, rec...);
+        else if (s.threads == 256) hipLaunchKernelGGL((k_filter_series_lane<MODEL, 256, REC...>), grid, dim3(256), 0, h->stream, a, T, rec...);
+        else hipLaunchKernelGGL((k_filter_series_lane<MODEL, 512, REC...>), grid, dim3(512), 0, h->stream, a, T, rec...);
+    } else if (s.pairs == 1) hipLaunchKernelGGL((k_filter_series_small<MODEL, 512, 1, REC...>), grid, dim3(512), 0, h->stream, a, T, rec...);
+    else hipLaunchKernelGGL((k_filter_series_small<MODEL, 512, 2, REC...>), grid, dim3(512), 0, h->stream, a, T, rec...);
 }
+// is the handle recording the expectations of every step (ssme_pf_set_series_expectations)?
+static bool recording(const ssme_pf_s* h) { return h->rec_fs.n > 0 || h->rec_user; }
 static void enqueue_series_small(ssme_pf_handle h, int T, bool has_z) {
     launch_gamma(h, 0, T);
     h->cur = 0;
@@ -432,7 +443,10 @@ static void enqueue_series_small(ssme_pf_handle h, int T, bool has_z) {
     a.z = has_z ? h->zbuf : nullptr;
     a.per_step = h->per_step;
     a.small_ms = h->small_ms;
-    with_model(h->cfg.model, [&](auto m) { launch_small_m<decltype(m)::value>(h, a, T); });
+    if (recording(h)) {
+        const SeriesRec rec = {h->rec_fs, h->traj, h->rec_user ? h->utraj : nullptr};
+        with_model(h->cfg.model, [&](auto m) { launch_small_m<decltype(m)::value>(h, a, T, rec); });
+    } else with_model(h->cfg.model, [&](auto m) { launch_small_m<decltype(m)::value>(h, a, T); });
     h->cur = 1;
 }
 
@@ -513,6 +527,21 @@ static int enqueue_user_expectations(ssme_pf_handle h) {
     }
 }
 
+// Recorded series, tiled route: the same two launches behind step `row`, the covariates read from row `row` of zbuf on the device
+// (a captured graph is replayed for later series: nothing about the covariates may travel by value), the values into `out`
+// ([n_h][R]: slot `row` of the trajectory).  uexp_part exists (ensure_trajectory).
+template <class M>
+static void enqueue_user_expectations_row(ssme_pf_handle h, int row, bool has_z, double* out) {
+    constexpr int NH = user_nh<M>::n;
+    if constexpr (NH > 0) {
+        hipLaunchKernelGGL(k_user_expect_partials_row<M>, dim3(h->B, h->R), dim3(kThreads), 0, h->stream, (const double*)h->x[h->cur],
+                           (size_t)h->R * h->Npad, (const double*)h->cdf[h->cur], (const ModelConst*)h->mc,
+                           (const double*)(has_z ? h->zbuf : nullptr), row, h->N, h->Npad, h->Bs, h->tile, h->uexp_part);
+        hipLaunchKernelGGL(k_user_expect_final<NH>, dim3(h->R), dim3(kThreads), 0, h->stream, (const double*)h->uexp_part,
+                           (const double*)h->tsum[h->cur], (const double*)h->tmax[h->cur], h->B, h->Bs, h->R, out);
+    }
+}
+
 // what both entry points check first; SSME_OK: the expectations are queued on the handle's stream
 static int user_expectations_checked(ssme_pf_handle h) {
 #if SSME_HAS_USER_MODEL
@@ -529,9 +558,35 @@ static int user_expectations_checked(ssme_pf_handle h) {
 // does the compiled-in user model declare its observation draw (model_api.h: gsamp / gsamp_vec)?
 #if SSME_HAS_USER_MODEL
 constexpr bool kUserHasGsamp = user_gsamp<ssme_user_model0>::has;
+constexpr int kUserNH = user_nh<ssme_user_model0>::n;      // functionals the compiled-in header declares
 #else
 constexpr bool kUserHasGsamp = false;
+constexpr int kUserNH = 0;
 #endif
+
+// Recorded series: the trajectory buffers for T time rows of the current recording configuration, and the per-tile numerators of the
+// user functionals (the tiled route launches inside a stream capture, where nothing may be allocated).  Recording off: no buffers.
+static int ensure_trajectory(ssme_pf_handle h, int T) {
+    if (!recording(h)) {
+        if (h->traj || h->utraj) { drop_graph(h); own_free(h, h->traj); own_free(h, h->utraj); }
+        h->traj_cap = 0; h->traj_n = 0;
+        return SSME_OK;
+    }
+    const bool want_u = h->rec_user != 0;
+    if (T > h->traj_cap || h->rec_fs.n != h->traj_n || want_u != (h->utraj != nullptr)) {
+        drop_graph(h);
+        own_free(h, h->traj); own_free(h, h->utraj);
+        h->traj_cap = 0;
+        if (h->rec_fs.n > 0) HIPCHK(own_alloc(h, h->traj, sizeof(double) * (size_t)T * h->rec_fs.n * h->R));
+        if (want_u) HIPCHK(own_alloc(h, h->utraj, sizeof(double) * (size_t)T * kUserNH * h->R));
+        h->traj_cap = T; h->traj_n = h->rec_fs.n;
+    }
+    if (want_u && !h->uexp_part) {
+        HIPCHK(own_alloc(h, h->uexp_part, sizeof(double) * (size_t)h->R * h->Bs * kUserNH));
+        HIPCHK(own_alloc(h, h->uexp_out, sizeof(double) * (size_t)kUserNH * h->R));
+    }
+    return SSME_OK;
+}
 
 // the start population of a forecast (forecast.h), every state plane gathered at the ancestor's index (DX = 1: the built-in models),
 // and the event of the horizon kernel's start
@@ -1115,9 +1170,27 @@ static void set_last_z(ssme_pf_handle h, const double* z, int T) {
     h->last_z = h->last_zv[0];
 }
 
+// Recorded series, tiled route: behind step t the partial and final expectation kernels of the step API, writing slot t of the
+// trajectories instead of exp_out / uexp_out.  They read the buffers the step wrote (now `cur`), as after ssme_pf_step.
+static void enqueue_step_expectations(ssme_pf_handle h, int t, bool has_z) {
+    if (h->rec_fs.n > 0) {
+        hipLaunchKernelGGL(k_expect_partials, dim3(h->B, h->R), dim3(kThreads), 0, h->stream, h->x[h->cur], h->cdf[h->cur], h->N,
+                           h->Npad, h->Bs, h->tile, h->rec_fs, h->exp_part);
+        hipLaunchKernelGGL(k_expect_final, dim3(h->R), dim3(kThreads), 0, h->stream, h->exp_part, h->tsum[h->cur], h->tmax[h->cur],
+                           h->B, h->Bs, h->R, h->rec_fs, h->traj + (size_t)t * h->rec_fs.n * h->R);
+    }
+#if SSME_HAS_USER_MODEL
+    if (h->rec_user) enqueue_user_expectations_row<ssme_user_model0>(h, t, has_z, h->utraj + (size_t)t * kUserNH * h->R);
+#endif
+}
+
 static void enqueue_series(ssme_pf_handle h, int T, bool has_z) {
     launch_gamma(h, 0, T);
-    for (int t = 0; t < T; ++t) enqueue_step(h, t, t, t, has_z, /*finalize_prev=*/t > 0, /*per_step=*/true);
+    const bool rec = recording(h);
+    for (int t = 0; t < T; ++t) {
+        enqueue_step(h, t, t, t, has_z, /*finalize_prev=*/t > 0, /*per_step=*/true);
+        if (rec) enqueue_step_expectations(h, t, has_z);
+    }
     launch_kf(h, T - 1, true);
 }
 
@@ -1127,7 +1200,9 @@ int ssme_pf_run_series(ssme_pf_handle h, const double* y, const double* z, int32
     if (T < 1) return SSME_ERR_LENGTH;
     if (!h->params_set) return SSME_ERR_STATE;
     HIPCHK(hipSetDevice(h->cfg.device));
+    h->rec_T = 0;                                      // rows are valid once the series is queued; a failure below leaves none
     int rc = ensure_series_capacity(h, T);
+    if (rc == SSME_OK) rc = ensure_trajectory(h, T);
     if (rc != SSME_OK) return rc;
     std::vector<double> y32, z32;
     if (h->cfg.dtype == SSME_F32) {
@@ -1150,7 +1225,7 @@ int ssme_pf_run_series(ssme_pf_handle h, const double* y, const double* z, int32
         HIPCHK(hipEventRecord(h->ev1, h->stream));
     } else if (h->graph_mode) {
         if (!h->gexec || h->g_T != T || h->g_has_z != (int)has_z || h->g_debug != h->debug_anc || h->g_logw != lw ||
-            h->g_nt != h->nt) {
+            h->g_nt != h->nt || h->g_rec_user != h->rec_user || std::memcmp(&h->g_rec_fs, &h->rec_fs, sizeof(FunctionalIds)) != 0) {
             if (h->gexec) { hipGraphExecDestroy(h->gexec); h->gexec = nullptr; }
             hipGraph_t g = nullptr;
             HIPCHK(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
@@ -1160,6 +1235,7 @@ int ssme_pf_run_series(ssme_pf_handle h, const double* y, const double* z, int32
             HIPCHK(hipGraphInstantiate(&h->gexec, g, nullptr, nullptr, 0));
             HIPCHK(hipGraphDestroy(g));
             h->g_T = T; h->g_has_z = has_z; h->g_debug = h->debug_anc; h->g_logw = lw; h->g_nt = h->nt;
+            h->g_rec_fs = h->rec_fs; h->g_rec_user = h->rec_user;
         }
         HIPCHK(hipEventRecord(h->ev0, h->stream));
         HIPCHK(hipGraphLaunch(h->gexec, h->stream));
@@ -1173,11 +1249,53 @@ int ssme_pf_run_series(ssme_pf_handle h, const double* y, const double* z, int32
     }
     HIPCHK(hipGetLastError());
     h->t = T;
+    h->rec_T = recording(h) ? T : 0; h->rec_n = h->rec_fs.n; h->rec_nh = h->rec_user ? kUserNH : 0;
     rc = read_loglik(h, loglik_out);
     if (rc != SSME_OK) return rc;
     HIPCHK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
     round_out(h, loglik_out, h->R);
     return SSME_OK;
+}
+
+// ---- recorded series: the expectations of every step of ssme_pf_run_series (kernels: pf_small.h, enqueue_step_expectations) ----
+int ssme_pf_set_series_expectations(ssme_pf_handle h, const int32_t* functionals, int32_t n, int32_t user) {
+    if (!h || n < 0 || n > kMaxFunctionals || (n > 0 && !functionals)) return SSME_ERR_INVALID_ARG;
+    for (int i = 0; i < n; ++i)
+        if (functionals[i] < SSME_H_X || functionals[i] > SSME_H_CONST42) return SSME_ERR_INVALID_ARG;
+    if (user && (h->cfg.model != SSME_MODEL_USER0 || kUserNH == 0)) return SSME_ERR_UNSUPPORTED;
+    if (h->shard_world > 0) return SSME_ERR_STATE;
+    FunctionalIds fs{};
+    fs.n = n;
+    for (int i = 0; i < n; ++i) fs.id[i] = functionals[i];
+    h->rec_fs = fs;
+    h->rec_user = user ? 1 : 0;
+    // a cached graph of another recording configuration is not replayed (the cache key of ssme_pf_run_series holds both); the
+    // trajectory buffers follow at the next run_series (ensure_trajectory), which also frees them once recording is off
+    if (h->gexec && (h->g_rec_user != h->rec_user || std::memcmp(&h->g_rec_fs, &h->rec_fs, sizeof(FunctionalIds)) != 0)) {
+        HIPCHK(hipSetDevice(h->cfg.device));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        drop_graph(h);
+    }
+    return SSME_OK;
+}
+
+// rows 0 .. T-1 of a trajectory of `n` functionals per row ([rows][n][R] on the device), rounded for SSME_F32 handles
+static int read_trajectory(ssme_pf_handle h, const double* dev, int n, double* out, int T) {
+    if (!h || !out || T < 1) return SSME_ERR_INVALID_ARG;
+    if (h->rec_T < 1 || n < 1 || !dev) return SSME_ERR_STATE;
+    if (T > h->rec_T) return SSME_ERR_INVALID_ARG;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const size_t cnt = (size_t)T * n * h->R;
+    HIPCHK(hipMemcpyAsync(out, dev, sizeof(double) * cnt, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    round_out(h, out, cnt);
+    return SSME_OK;
+}
+int ssme_pf_get_series_expectations(ssme_pf_handle h, double* out, int32_t T) {
+    return read_trajectory(h, h ? h->traj : nullptr, h ? h->rec_n : 0, out, T);
+}
+int ssme_pf_get_series_user_expectations(ssme_pf_handle h, double* out, int32_t T) {
+    return read_trajectory(h, h ? h->utraj : nullptr, h ? h->rec_nh : 0, out, T);
 }
 
 int ssme_pf_get_per_step(ssme_pf_handle h, double* out, int32_t T) {

@@ -20,6 +20,10 @@
 // workgroup per CU), their normals (xdim_words) and the DY values of an observation row; component 0 and everything about the weights
 // is the scalar text.  Shapes are the scalar models' (512 threads x 1 or 2 pairs; lanes up to 512): no instantiation of the four test
 // headers spills a VGPR (profiles/vector_series_kernels.txt).
+//
+// Recording instantiations (ssme_pf_set_series_expectations): the same two kernels with a third argument,
+// SeriesRec, write E[h(x_t) | y_{1:t}] of every step from LDS (record_step_expectations) with the bits of the step API's
+// expectation kernels.  The instantiations without it are untouched by that code.
 #pragma once
 #include "pf_kernels.h"
 
@@ -260,13 +264,124 @@ __device__ __forceinline__ void hand_over_state(const StepArgs& a, size_t rowoff
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Recorded series (ssme_pf_set_series_expectations): the filtered expectations of EVERY step, E[h(x_t) | y_{1:t}], written by the
+// series kernels themselves.  After the closing barrier of step t the workgroup holds what k_expect_partials / k_user_expect_partials
+// and the two final kernels read from memory after a step of the step API -- the particles of step t (all planes) and their
+// tile-local cdf in LDS, the tile sum A and the tile maximum mb -- and it forms the same numbers by THEIR summation trees, not by
+// its own thread layout, so a row has the bits of the two-launch path:
+//   built-ins  virtual thread v of 256 adds particles v, v + 256, ... < N in this order (q_j = cdf_j - cdf_{j-1}, as there);
+//   user h     virtual thread v adds 2v, 2v + 1, 2v + 512, 2v + 513, ... (valid ones only), all n_h outputs in one pass;
+//   combining  the 64 virtual lanes of a wave by the xor butterfly 32 .. 1, the four waves as ((w0 + w1) + w2) + w3;
+//   final      one tile: s = dexp(mb - m) with m = mb (NaN if mb is), E = (num s + 0) / (A s + 0), NaN where m is NaN.  The + 0 is
+//              what the final kernels' sums over 255 idle threads amount to (-0 becomes +0); s is evaluated, not taken as 1:
+//              mb = +-inf gives s = NaN and a NaN row, as the two launches do.
+// The first 256 threads play the virtual threads (a workgroup of 64 or 128 takes them in 4 or 2 passes).  Nothing is staged: LDS
+// grows by the wave sums alone ((4 + n_h) x 4 doubles).  One more barrier per step.  Thread f writes row t of functional f.
+// ---------------------------------------------------------------------------------------------------------------------
+struct SeriesRec {
+    FunctionalIds fs;          // built-in functionals to record (n = 0: none)
+    double* traj;              // [T][fs.n][R]
+    double* utraj;             // [T][n_h][R] the user model's own functionals, or null
+};
+#if SSME_HAS_USER_MODEL
+template <int MODEL> constexpr int model_nh() { return MODEL == MODEL_USER0 ? user_nh<ssme_user_model0>::n : 0; }
+#else
+template <int MODEL> constexpr int model_nh() { return 0; }
+#endif
+
+__device__ __forceinline__ const SeriesRec& the_rec(const SeriesRec& rec) { return rec; }      // the one element of RECARG...
+
+template <int MODEL, int NT, class IN>
+__device__ __forceinline__ void record_step_expectations(const SeriesRec& rec, const StepArgs& a, const ModelConst& mc, const IN& in, int r,
+                                                         int t, const double* lds_x, int xstride, const double* lds_cdf, double A,
+                                                         double mb, const ExpTabEntry* etab, double (*lds_red)[4]) {
+    constexpr int NH = model_nh<MODEL>();
+    [[maybe_unused]] constexpr int DX = model_dx<MODEL>();
+    constexpr int PASSES = NT >= kThreads ? 1 : kThreads / NT;
+    const int tid = threadIdx.x, N = a.N;
+#pragma unroll
+    for (int p = 0; p < PASSES; ++p) {
+        const int v = p * NT + tid;                                    // the virtual thread this lane plays (whole waves: v >> 6 is uniform)
+        if (v < kThreads) {
+            if (rec.fs.n > 0) {
+                double num[kMaxFunctionals] = {0.0, 0.0, 0.0, 0.0};
+                for (int j = v; j < N; j += kThreads) {
+                    const double q = lds_cdf[j] - (j ? lds_cdf[j - 1] : 0.0);
+                    const double xv = lds_x[j];
+#pragma unroll
+                    for (int f = 0; f < kMaxFunctionals; ++f)
+                        if (f < rec.fs.n) num[f] = num[f] + builtin_h(rec.fs.id[f], xv) * q;
+                }
+#pragma unroll
+                for (int f = 0; f < kMaxFunctionals; ++f) {
+                    num[f] = wave_sum_xor(num[f]);
+                    if ((v & 63) == 0) lds_red[f][v >> 6] = num[f];
+                }
+            }
+#if SSME_HAS_USER_MODEL
+            if constexpr (NH > 0) {
+                if (rec.utraj) {
+                    using M = typename user_model_of<MODEL>::type;
+                    double num[NH];
+#pragma unroll
+                    for (int k = 0; k < NH; ++k) num[k] = 0.0;
+                    for (int j = 2 * v; j < N; j += 2 * kThreads) {
+                        const double c0 = lds_cdf[j], c1 = lds_cdf[j + 1];     // j + 1 < P: P is even
+                        const double prev = j ? lds_cdf[j - 1] : 0.0;
+                        const double q0 = c0 - prev, q1 = c1 - c0;
+                        double xs[DX], hv[NH];
+                        {
+#pragma unroll
+                            for (int d = 0; d < DX; ++d) xs[d] = lds_x[d * xstride + j];
+                            if constexpr (model_kcov<MODEL>() > 0) M::h(mc, xs, in.zc.v, etab, hv);
+                            else M::h(mc, xs, in.z, etab, hv);
+#pragma unroll
+                            for (int k = 0; k < NH; ++k) num[k] = num[k] + hv[k] * q0;
+                        }
+                        if (j + 1 < N) {
+#pragma unroll
+                            for (int d = 0; d < DX; ++d) xs[d] = lds_x[d * xstride + j + 1];
+                            if constexpr (model_kcov<MODEL>() > 0) M::h(mc, xs, in.zc.v, etab, hv);
+                            else M::h(mc, xs, in.z, etab, hv);
+#pragma unroll
+                            for (int k = 0; k < NH; ++k) num[k] = num[k] + hv[k] * q1;
+                        }
+                    }
+#pragma unroll
+                    for (int k = 0; k < NH; ++k) {
+                        num[k] = wave_sum_xor(num[k]);
+                        if ((v & 63) == 0) lds_red[kMaxFunctionals + k][v >> 6] = num[k];
+                    }
+                }
+            }
+#endif
+        }
+    }
+    __syncthreads();
+    const int nrec = kMaxFunctionals + ((NH > 0 && rec.utraj) ? NH : 0);
+    if (tid < nrec && (tid >= kMaxFunctionals || tid < rec.fs.n)) {
+        const double part = ((lds_red[tid][0] + lds_red[tid][1]) + lds_red[tid][2]) + lds_red[tid][3];
+        const double m = (mb != mb) ? dnan() : mb;
+        const double sc = dexp(mb - m);
+        const double n4 = part * sc + 0.0;
+        const double d4 = A * sc + 0.0;
+        const double e = (m != m) ? dnan() : n4 / d4;
+        if (tid < kMaxFunctionals) rec.traj[((size_t)t * rec.fs.n + tid) * a.R + r] = e;
+        else rec.utraj[((size_t)t * NH + (tid - kMaxFunctionals)) * a.R + r] = e;
+    }
+}
+
 // One particle PAIR per lane.
 // grid = (R filters), block = NT, covers P = 2*NT*NK >= N particle slots (P a power of two, 256 .. 2048).
 // a.x_out / cdf_out / tsum_out / tmax_out / logw receive the state after the last step (as k_filter_step
 // leaves it), a.scal the accumulated log-likelihood; a.t / yi / gi are ignored (t = yi = gi = 0 .. T-1).
 // a.small_ms: [R][Tcap][2] scratch.
-template <int MODEL, int NT, int NK>
-__global__ __launch_bounds__(NT) void k_filter_series_small(const StepArgs a, const int T) {
+// RECARG: empty, or SeriesRec for the recording instantiation, which takes it as a third kernel argument; `if constexpr` keeps every
+// line of the recording out of the other instantiation, whose arguments and code are what they were without it.
+template <int MODEL, int NT, int NK, class... RECARG>
+__global__ __launch_bounds__(NT) void k_filter_series_small(const StepArgs a, const int T, const RECARG... recarg) {
+    constexpr bool REC = sizeof...(RECARG) > 0;
     constexpr int P = 2 * NT * NK;
     // A vector user model (model_api.h): component 0 travels the scalar path below unchanged; components d >= 1 live in planes
     // lds_x + d P, are gathered at the same ancestor, and draw their normals from stream STREAM_XDIM + d (xdim_words) for the
@@ -280,6 +395,11 @@ __global__ __launch_bounds__(NT) void k_filter_series_small(const StepArgs a, co
     __shared__ double lds_d2[16];
     __shared__ __attribute__((aligned(16))) DrawTabs lds_dtab;
     __shared__ __attribute__((aligned(16))) ExpTabEntry lds_etab[SSME_EXP_TABLE_SIZE];
+    double (*lds_red)[4] = nullptr;                    // recording: the wave sums of the expectations' numerators
+    if constexpr (REC) {
+        __shared__ double red[kMaxFunctionals + model_nh<MODEL>()][4];
+        lds_red = red;
+    }
 
     const int tid = threadIdx.x;
     load_log_table<NT>(&lds_dtab);
@@ -455,6 +575,7 @@ __global__ __launch_bounds__(NT) void k_filter_series_small(const StepArgs a, co
         A_prev = total;
         mb_prev = mb;
         __syncthreads();                                              // cdf / x of step t visible to step t+1
+        if constexpr (REC) record_step_expectations<MODEL, NT>(the_rec(recarg...), a, mc, in, r, t, lds_x, P, lds_cdf, A_prev, mb_prev, lds_etab, lds_red);
     }
 
     series_accounting<NT>(a, r, T, ms, A_prev, mb_prev, lds_etab);
@@ -468,8 +589,9 @@ __global__ __launch_bounds__(NT) void k_filter_series_small(const StepArgs a, co
 // its own half, so a wave's chain per step is ~55 % of the pair kernel's and twice as many waves share a SIMD.
 // grid = (R), block = NT = P particle slots (64 .. 512); a.small_ms: [R][Tcap][2] scratch.
 // ---------------------------------------------------------------------------------------------------------------------
-template <int MODEL, int NT>
-__global__ __launch_bounds__(NT) void k_filter_series_lane(const StepArgs a, const int T) {
+template <int MODEL, int NT, class... RECARG>
+__global__ __launch_bounds__(NT) void k_filter_series_lane(const StepArgs a, const int T, const RECARG... recarg) {
+    constexpr bool REC = sizeof...(RECARG) > 0;                // the recording instantiation: RECARG = SeriesRec (see k_filter_series_small)
     constexpr int P = NT;
     // A vector user model: as in the pair kernel; the pair index of the d >= 1 draws is tid >> 1 and the lane keeps half tid & 1.
     constexpr int DX = model_dx<MODEL>(), DY = model_dy<MODEL>();
@@ -480,6 +602,11 @@ __global__ __launch_bounds__(NT) void k_filter_series_lane(const StepArgs a, con
     __shared__ double lds_d2[16];
     __shared__ __attribute__((aligned(16))) DrawTabs lds_dtab;
     __shared__ __attribute__((aligned(16))) ExpTabEntry lds_etab[SSME_EXP_TABLE_SIZE];
+    double (*lds_red)[4] = nullptr;                    // recording: the wave sums of the expectations' numerators
+    if constexpr (REC) {
+        __shared__ double red[kMaxFunctionals + model_nh<MODEL>()][4];
+        lds_red = red;
+    }
 
     const int tid = threadIdx.x;
     load_log_table<NT>(&lds_dtab);
@@ -626,6 +753,7 @@ __global__ __launch_bounds__(NT) void k_filter_series_lane(const StepArgs a, con
         A_prev = stot[0];
         mb_prev = mb;
         __syncthreads();                                              // cdf / x of step t visible to step t+1
+        if constexpr (REC) record_step_expectations<MODEL, NT>(the_rec(recarg...), a, mc, in, r, t, lds_x, P, lds_cdf, A_prev, mb_prev, lds_etab, lds_red);
     }
 
     series_accounting<NT>(a, r, T, ms, A_prev, mb_prev, lds_etab);

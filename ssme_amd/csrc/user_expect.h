@@ -6,6 +6,7 @@
 // w_j = q_j exp(m_tile - m), q_j = cdf_j - cdf_{j-1} (tile-local, integer valued), so sum_j q_j of a tile is its exact tile sum A_b.
 //   k_user_expect_partials  grid (B tiles, R), 256 threads: per tile sum_j h_k(x_j) q_j for ALL n_h outputs in one pass; the dim_x
 //                           planes and the cdf are read once, two neighbouring particles (16 bytes) per lane and access
+//   k_user_expect_partials_row  the same with the covariates read from a row of the series' covariates on the device (recorded series)
 //   k_user_expect_final     grid (R), 256 threads: E_k = sum_b num_{b,k} e^{m_b - m} / sum_b A_b e^{m_b - m}; m NaN => NaN
 // The swarm means over the R members come from k_swarm_means (pf_kernels.h), whose row count is a launch argument.
 //
@@ -20,10 +21,10 @@
 namespace ssme {
 
 template <class M>
-__global__ __launch_bounds__(kThreads) void k_user_expect_partials(const double* x, size_t xplane, const double* cdf, const ModelConst* mcs,
-                                                                   double zcov, const CovVals<user_cov<M>::k> zc /*dim_cov headers*/,
-                                                                   int N, int Npad, int Bs, int tile,
-                                                                   double* part /*[R][Bs][n_h]*/) {
+__device__ __forceinline__ void user_expect_partials_tile(const double* x, size_t xplane, const double* cdf, const ModelConst* mcs,
+                                                          double zcov, const CovVals<user_cov<M>::k>& zc /*dim_cov headers*/,
+                                                          int N, int Npad, int Bs, int tile,
+                                                          double* part /*[R][Bs][n_h]*/) {
     constexpr int NH = user_nh<M>::n, DX = user_dims<M>::dx, KC = user_cov<M>::k;
     __shared__ ExpTabEntry lds_etab[SSME_EXP_TABLE_SIZE];
     __shared__ double lds[NH][4];
@@ -73,6 +74,33 @@ __global__ __launch_bounds__(kThreads) void k_user_expect_partials(const double*
     }
     __syncthreads();
     if (tid < NH) part[((size_t)r * Bs + b) * NH + tid] = ((lds[tid][0] + lds[tid][1]) + lds[tid][2]) + lds[tid][3];
+}
+
+template <class M>
+__global__ __launch_bounds__(kThreads) void k_user_expect_partials(const double* x, size_t xplane, const double* cdf, const ModelConst* mcs,
+                                                                   double zcov, const CovVals<user_cov<M>::k> zc /*dim_cov headers*/,
+                                                                   int N, int Npad, int Bs, int tile,
+                                                                   double* part /*[R][Bs][n_h]*/) {
+    user_expect_partials_tile<M>(x, xplane, cdf, mcs, zcov, zc, N, Npad, Bs, tile, part);
+}
+
+// The same for step `row` of a recorded series (ssme_pf_set_series_expectations): the covariates are READ from row `row` of the series'
+// uploaded covariates z ([T][max(dim_cov, 1)]; null: zeros), not passed by value -- a captured graph is replayed for later series, whose
+// covariates differ, and a value baked into the launch would be those of the series that was captured.
+template <class M>
+__global__ __launch_bounds__(kThreads) void k_user_expect_partials_row(const double* x, size_t xplane, const double* cdf, const ModelConst* mcs,
+                                                                       const double* z, int row, int N, int Npad, int Bs, int tile,
+                                                                       double* part /*[R][Bs][n_h]*/) {
+    constexpr int KC = user_cov<M>::k;
+    double zcov = 0.0;
+    CovVals<KC> zc;
+#pragma unroll
+    for (int j = 0; j < (KC > 0 ? KC : 1); ++j) zc.v[j] = 0.0;
+    if (z) {
+        if constexpr (KC > 0) zc.load(z, (size_t)row);
+        else zcov = z[row];
+    }
+    user_expect_partials_tile<M>(x, xplane, cdf, mcs, zcov, zc, N, Npad, Bs, tile, part);
 }
 
 template <int NH>

@@ -78,6 +78,7 @@ class ParticleFilterBank:
         self._h = C.c_void_p()
         self.model, self.n, self.r = int(model), int(n_particles), int(n_filters)
         self._last_T = 0
+        self._rec_n = self._run_rec_n = 0      # built-in functionals set for the next run_series / recorded by the last one
         cfg = capi.Config(model=model, n_particles=n_particles, n_filters=n_filters, dtype=dtype,
                           resampler=resampler, resamp_sched=resamp_sched, seed=seed, device=device,
                           first_filter_id=first_filter_id, tile_particles=tile, n_filters_total=n_filters_total)
@@ -179,6 +180,7 @@ class ParticleFilterBank:
         out = np.empty(self.r)
         self._chk(capi.lib().ssme_pf_run_series(self._h, capi.dptr(yv), capi.dptr(zv), T, capi.dptr(out)))
         self._last_T = T
+        self._run_rec_n = self._rec_n       # built-in functionals this series recorded
         return out
 
     def per_step(self):
@@ -226,6 +228,29 @@ class ParticleFilterBank:
         loaded library has none."""
         out = np.empty((max(int(capi.lib().ssme_pf_user_model_n_h()), 1), self.r))
         self._chk(capi.lib().ssme_pf_get_user_expectations(self._h, capi.dptr(out)))
+        return out
+
+    def record_series_expectations(self, functionals=(), user=False):
+        """Record E[h(x_t) | y_{1:t}] at EVERY step of the run_series calls that follow (ssme_pf_set_series_expectations): up to 4
+        built-in functionals and, with user=True, the n_h functionals of the user model's header.  No functionals and user=False
+        switch recording off (the default).  Sticky across run_series, set_params, set_seed and reset."""
+        fs = np.ascontiguousarray(functionals, dtype=np.int32)
+        self._chk(capi.lib().ssme_pf_set_series_expectations(self._h, fs.ctypes.data_as(C.POINTER(C.c_int32)) if fs.size else None,
+                                                             fs.size, 1 if user else 0))
+        self._rec_n = fs.size
+
+    def series_expectations(self):
+        """The recorded built-in functionals of the last run_series: [T, n, R]; row t is what expectations_multi returns after
+        step t of a stepped handle, to the bit."""
+        out = np.empty((self._last_T, max(self._run_rec_n, 1), self.r))
+        self._chk(capi.lib().ssme_pf_get_series_expectations(self._h, capi.dptr(out), self._last_T))
+        return out
+
+    def series_user_expectations(self):
+        """The recorded functionals of the user model's header of the last run_series: [T, n_h, R]; row t is what
+        user_expectations returns after step t of a stepped handle (h receives the covariates of row t), to the bit."""
+        out = np.empty((self._last_T, max(int(capi.lib().ssme_pf_user_model_n_h()), 1), self.r))
+        self._chk(capi.lib().ssme_pf_get_series_user_expectations(self._h, capi.dptr(out), self._last_T))
         return out
 
     def swarm_aggregate_user(self, num_threads=0):
