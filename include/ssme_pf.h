@@ -252,7 +252,8 @@ int ssme_pf_set_small_series(ssme_pf_handle h, int32_t enable);
 /* What ssme_pf_run_series launches for this handle as it is configured now: the tiled step kernel (threads per tile), or one of
  * the two whole-series kernels of one-tile filters -- one particle per lane (N <= 512) or one particle pair per lane -- and the
  * threads of its one workgroup per filter.  Needs no prior step.  Sharded handles: SSME_ERR_STATE, as for ssme_pf_run_series. */
-enum { SSME_ROUTE_TILED = 0, SSME_ROUTE_SERIES_LANE = 1, SSME_ROUTE_SERIES_PAIR = 2 };
+enum { SSME_ROUTE_TILED = 0, SSME_ROUTE_SERIES_LANE = 1, SSME_ROUTE_SERIES_PAIR = 2,
+       SSME_ROUTE_LW_SERIES = 3 /* Liu-West handles: ssme_lw_get_series_route */ };
 int ssme_pf_get_series_route(ssme_pf_handle h, int32_t* route, int32_t* threads_per_block);
 /* Execution policy of run_series: 0 = eager launches, 1 = one hipGraph per series (default). */
 int ssme_pf_set_graph_mode(ssme_pf_handle h, int32_t mode);
@@ -414,6 +415,17 @@ int ssme_lw_step(ssme_lw_handle h, const double* y, const double* z, double* log
 /* T steps; loglik_out (R values) = sum of the log conditional likelihoods */
 int ssme_lw_run_series(ssme_lw_handle h, const double* y, const double* z, int32_t T, double* loglik_out);
 int ssme_lw_get_per_step(ssme_lw_handle h, double* out, int32_t T);
+/* Liu-West filters of one tile (N <= 2048) can run ssme_lw_run_series as k_lw_init plus ONE launch that loops over steps
+ * 1 .. T-1 with the population, the parameter records and the integer cdf in LDS, one workgroup of 512 threads per filter
+ * (ssme_amd/csrc/lw_small.h).  enable = 1 takes that kernel where it applies (unsharded handle, N <= 2048), 0 forces the tiled
+ * launches (two per step).  Results are bit-identical either way, and so is every call that follows the series.  The setting
+ * survives ssme_lw_reset and ssme_lw_run_series.  NULL handle: SSME_ERR_INVALID_ARG; sharded handle: SSME_ERR_STATE.
+ * Default of a new handle: see profiles/lw_series_timing.txt. */
+int ssme_lw_set_small_series(ssme_lw_handle h, int32_t enable);
+/* What ssme_lw_run_series launches for this handle as it is configured now: SSME_ROUTE_TILED or SSME_ROUTE_LW_SERIES, and the
+ * threads per workgroup (512 on both).  Needs no prior step and makes no HIP call.  NULL arguments: SSME_ERR_INVALID_ARG;
+ * sharded handle: SSME_ERR_STATE. */
+int ssme_lw_get_series_route(ssme_lw_handle h, int32_t* route, int32_t* threads_per_block);
 /* weighted means of the untransformed parameters under the last step's weights: out[r*4 + d] */
 int ssme_lw_get_param_means(ssme_lw_handle h, double* out);
 /* E[h | y_{1:t}] under the last step's (pre-resampling) weights for built-in functionals (the reference takes

@@ -4,6 +4,6 @@ Python host mirror of the reference's filter interface over the C ABI (include/s
 """
 from .filters import *  # noqa: F401,F403
 from . import _capi  # noqa: F401
-from ._capi import ROUTE_TILED, ROUTE_SERIES_LANE, ROUTE_SERIES_PAIR  # noqa: F401  (ParticleFilterBank.series_route)
+from ._capi import ROUTE_TILED, ROUTE_SERIES_LANE, ROUTE_SERIES_PAIR, ROUTE_LW_SERIES  # noqa: F401  (series_route() of the banks and the Liu-West filters)
 
 __version__ = "0.1.0"

@@ -17,7 +17,7 @@ MODEL_SVOL, MODEL_SVOL_LEVERAGE, MODEL_LIN_GAUSS, MODEL_USER0 = 0, 1, 2, 3
 RESAMP_MULTINOMIAL, RESAMP_SYSTEMATIC, RESAMP_STRATIFIED, RESAMP_MULTINOMIAL_IID = 0, 1, 2, 3
 F64, F32 = 0, 1
 H_X, H_X2, H_VOL, H_CONST42 = 0, 1, 2, 3
-ROUTE_TILED, ROUTE_SERIES_LANE, ROUTE_SERIES_PAIR = 0, 1, 2
+ROUTE_TILED, ROUTE_SERIES_LANE, ROUTE_SERIES_PAIR, ROUTE_LW_SERIES = 0, 1, 2, 3
 
 EXPORTS = [
     "ssme_pf_create", "ssme_pf_destroy", "ssme_pf_default_tile", "ssme_pf_user_model_n_theta", "ssme_pf_user_model_dims", "ssme_pf_user_model_n_h", "ssme_pf_user_model_has_gsamp", "ssme_pf_user_model_dim_cov", "ssme_pf_user_model_has_first", "ssme_pf_get_user_expectations", "ssme_pf_swarm_aggregate_user", "ssme_pf_set_series_expectations", "ssme_pf_get_series_expectations", "ssme_pf_get_series_user_expectations", "ssme_pf_set_params", "ssme_pf_reset", "ssme_pf_set_seed", "ssme_pf_set_small_series", "ssme_pf_get_series_route", "ssme_pf_shard_create", "ssme_pf_set_stream",
@@ -32,7 +32,7 @@ EXPORTS = [
     "ssme_pf_version",
     "ssme_lw_create", "ssme_lw_destroy", "ssme_lw_reset", "ssme_lw_step", "ssme_lw_run_series", "ssme_lw_get_per_step",
     "ssme_lw_get_param_means", "ssme_lw_get_expectations", "ssme_lw_download_weights", "ssme_lw_download_state", "ssme_lw_set_debug", "ssme_lw_last_elapsed_ms", "ssme_lw_sim_future_obs", "ssme_lw_forecast_elapsed_ms",
-    "ssme_lw_last_error",
+    "ssme_lw_last_error", "ssme_lw_set_small_series", "ssme_lw_get_series_route",
     "ssme_lw_shard_create", "ssme_lw_set_stream", "ssme_lw_shard_prepare", "ssme_lw_shard_init", "ssme_lw_shard_plan",
     "ssme_lw_shard_stage1", "ssme_lw_shard_mid", "ssme_lw_shard_stage2", "ssme_lw_shard_finalize", "ssme_lw_get_loglik", "ssme_lw_shard_run_series", "ssme_lw_shard_download", "ssme_lw_shard_stats", "ssme_lw_shard_layout",
 ]
@@ -158,6 +158,8 @@ def lib():
         L.ssme_lw_download_weights.argtypes = [H, C.c_int32, dp, dp, dp]
         L.ssme_lw_download_state.argtypes = [H, C.c_int32, dp, dp, u32p, u32p, dp, dp]
         L.ssme_lw_set_debug.argtypes = [H, C.c_int32]
+        L.ssme_lw_set_small_series.argtypes = [H, C.c_int32]
+        L.ssme_lw_get_series_route.argtypes = [H, i32p, i32p]
         L.ssme_lw_last_elapsed_ms.argtypes = [H, C.POINTER(C.c_float)]
         L.ssme_lw_sim_future_obs.argtypes = [H, C.c_int32, dp, dp, dp, u32p, dp]
         L.ssme_lw_forecast_elapsed_ms.argtypes = [H, C.POINTER(C.c_float), C.POINTER(C.c_float)]

@@ -5,6 +5,7 @@
 #include "pf_kernels.h"
 #include "lw_kernels.h"
 #include "pf_small.h"
+#include "lw_small.h"
 #include "user_expect.h"
 #include "forecast.h"
 #include "handle_core.h"
@@ -1814,6 +1815,7 @@ struct ssme_lw_s : HandleCore {
     uint32_t *anc, *kidx;
     uint32_t* ancbuf;        // unsharded handles: this step's resampling ancestors, stage 1 -> stage 2 (compose mode, lw_kernels.h)
     int fixed_trans;                 // the transform set is (logit, null, log, twice_fisher): stage kernels with it compiled in (lw_trans_kind)
+    int small_series;                // 1: one-tile filters run steps 1 .. T-1 of a series in one launch (lw_small.h; lw_series_route decides)
     // C++ shard driver (ssme_lw_shard_run_series): halo buffers ([margin | own | margin] rows of 2048 doubles; theta rows of 8192),
     // this rank's stage outputs for the gathers, the gathered arrays
     double *sh_xB, *sh_thB, *sh_cdfB, *sh_xr, *sh_thr, *sh_g1, *sh_cdfA;
@@ -1953,6 +1955,23 @@ static void lw_enqueue_finalize(ssme_lw_handle h, int t, bool record, double* ll
         hipLaunchKernelGGL(k_lw_finalize<false>, dim3(h->R), dim3(kThreads), 0, h->stream, a);
 }
 
+// The one place that decides what ssme_lw_run_series launches (it and ssme_lw_get_series_route ask here): the whole-series kernel
+// for an unsharded handle of one tile with small series enabled, the tiled stage launches otherwise.
+constexpr int kLwSmallSeriesDefault = 1;     // the default route of a new handle, by the rule and the figures of profiles/lw_series_timing.txt
+static int lw_series_route(const ssme_lw_s* h) {
+    return (h->shard_world == 0 && h->B == 1 && h->small_series) ? SSME_ROUTE_LW_SERIES : SSME_ROUTE_TILED;
+}
+static const void* lw_series_kernel(bool ft) {
+    return ft ? reinterpret_cast<const void*>(&k_lw_series<true>) : reinterpret_cast<const void*>(&k_lw_series<false>);
+}
+// steps 1 .. T-1, the accounting of every step and the hand-over, behind k_lw_init
+static void lw_launch_series(ssme_lw_handle h, int T) {
+    LwArgs a = lw_args(h);
+    a.per_step = h->per_step;
+    void* args[] = {&a, &T};
+    hipLaunchKernel(lw_series_kernel(h->fixed_trans), dim3(h->R), dim3(kLwNT), args, kLwSeriesLdsBytes, h->stream);
+}
+
 static int lw_reset(ssme_lw_handle h) {
     std::vector<LwScalars> sc(h->R);
     const double logN = dlog((double)h->N);
@@ -1990,6 +2009,7 @@ static int lw_create_impl(const ssme_lw_config* cfg, int shard_rank, int shard_w
     if (h->B > kMaxTilesSplit) { delete h; return SSME_ERR_UNSUPPORTED; }          // N <= 2^25
     h->cfg = *cfg;
     h->form = cfg->form; h->rs = cfg->resamp_sched < 1 ? 1 : cfg->resamp_sched;
+    h->small_series = kLwSmallSeriesDefault;
     h->fixed_trans = (cfg->transforms[0] == TR_LOGIT && cfg->transforms[1] == TR_NULL && cfg->transforms[2] == TR_LOG && cfg->transforms[3] == TR_TWICE_FISHER) ? 1 : 0;
     if (hipSetDevice(cfg->device) != hipSuccess) { delete h; return SSME_ERR_HIP; }
     int rc = [&]() -> int {
@@ -2009,6 +2029,8 @@ static int lw_create_impl(const ssme_lw_config* cfg, int shard_rank, int shard_w
             for (int big = 0; big < 2; ++big)
                 for (int ft = 0; ft < 2; ++ft)
                     HIPCHK(grant_lds(lw_stage_kernel(stage, big, ft), big ? h->lds_bytes_big : h->lds_bytes, cfg->device));
+        if (h->shard_world == 0 && h->B == 1)
+            for (int ft = 0; ft < 2; ++ft) HIPCHK(grant_lds(lw_series_kernel(ft), kLwSeriesLdsBytes, cfg->device));
         if (h->shard_world == 0) {               // a sharded handle works on the caller's buffers
             for (double** p : {&h->xB, &h->xr, &h->lw1, &h->cdfA, &h->cdfB}) HIPCHK(own_alloc(h, *p, sizeof(double) * np, Mem::zeroed));
             if (h->rs > 1) HIPCHK(own_alloc(h, h->lwB, sizeof(double) * np, Mem::zeroed));
@@ -2322,6 +2344,21 @@ int ssme_lw_set_debug(ssme_lw_handle h, int32_t flags) {
     return SSME_OK;
 }
 
+int ssme_lw_set_small_series(ssme_lw_handle h, int32_t enable) {
+    if (!h || enable < 0 || enable > 1) return SSME_ERR_INVALID_ARG;
+    if (h->shard_world > 0) return SSME_ERR_STATE;     // sharded handles are driven by ssme_lw_shard_*
+    h->small_series = enable;
+    return SSME_OK;
+}
+
+int ssme_lw_get_series_route(ssme_lw_handle h, int32_t* route, int32_t* threads_per_block) {
+    if (!h || !route || !threads_per_block) return SSME_ERR_INVALID_ARG;
+    if (h->shard_world > 0) return SSME_ERR_STATE;
+    *route = lw_series_route(h);
+    *threads_per_block = kLwNT;
+    return SSME_OK;
+}
+
 int ssme_lw_step(ssme_lw_handle h, const double* y, const double* z, double* out) {
     if (!h || !y) return SSME_ERR_INVALID_ARG;
     if (h->shard_world > 0) return SSME_ERR_STATE;     // sharded handles own no particle buffers: ssme_lw_shard_* drives them
@@ -2359,8 +2396,13 @@ int ssme_lw_run_series(ssme_lw_handle h, const double* y, const double* z, int32
     if (rc != SSME_OK) return rc;
     HIPCHK(hipEventRecord(h->ev0, h->stream));
     lw_launch_gamma(h, 0, T);
-    for (int t = 0; t < T; ++t) lw_enqueue_step(h, t, t, t, true, /*finalize_prev=*/t > 0);
-    lw_enqueue_finalize(h, T - 1, true);
+    if (lw_series_route(h) == SSME_ROUTE_LW_SERIES) {
+        lw_enqueue_step(h, 0, 0, 0, true, false);             // k_lw_init
+        lw_launch_series(h, T);
+    } else {
+        for (int t = 0; t < T; ++t) lw_enqueue_step(h, t, t, t, true, /*finalize_prev=*/t > 0);
+        lw_enqueue_finalize(h, T - 1, true);
+    }
     HIPCHK(hipEventRecord(h->ev1, h->stream));
     HIPCHK(hipGetLastError());
     h->t = T;

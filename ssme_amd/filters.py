@@ -545,6 +545,18 @@ class svol_lw_1_par:
     def reset(self):
         self._chk(capi.lib().ssme_lw_reset(self._h))
 
+    def set_small_series(self, enable=True):
+        """Filters of at most 2048 particles: run_series as k_lw_init plus one launch that loops over the remaining steps (True), or
+        the tiled stage launches (False).  Same bits either way; series_route() says which one run_series takes."""
+        self._chk(capi.lib().ssme_lw_set_small_series(self._h, 1 if enable else 0))
+
+    def series_route(self):
+        """(route, threads per block) of what run_series launches for this handle as it is configured now
+        (ssme_lw_get_series_route): ROUTE_TILED or ROUTE_LW_SERIES.  Needs no prior step."""
+        route, threads = C.c_int32(), C.c_int32()
+        self._chk(capi.lib().ssme_lw_get_series_route(self._h, C.byref(route), C.byref(threads)))
+        return route.value, threads.value
+
     def filter(self, y, z=0.0, fs=()):
         """filter(obs, cov, fs) of LWFilterWithCovs / LWFilter2WithCovs (liu_west_filter.h:840, :2050); without z it is
         the no-covariate LWFilter / LWFilter2 call (:238, :1447; the same model with the covariate term at zero).
