@@ -432,6 +432,24 @@ int ssme_lw_get_param_means(ssme_lw_handle h, double* out);
  * std::function h(x, z, theta), liu_west_filter.h:1054-1075 / :2267-2290): ids 0-3 = SSME_H_X, SSME_H_X2, SSME_H_VOL,
  * SSME_H_CONST42 of the state; 4-7 = the untransformed parameters phi, mu, sigma, rho.  out[i*R + r]. */
 int ssme_lw_get_expectations(ssme_lw_handle h, const int32_t* functionals, int32_t n, double* out);
+/* Recorded series: with enable = 1 every following ssme_lw_run_series also stores, for every step t = 0 .. T-1 and every filter,
+ * the eight values ssme_lw_get_expectations can return (E[x], E[x^2], E[exp(x/2)], E[42], E[phi], E[mu], E[sigma], E[rho] under
+ * the pre-resampling second-stage weights of step t) -- the path of the parameter means and of the filtered state.  A switch with
+ * no list of functionals: the read-out forms all eight in one pass.  The device buffer ([T][R][8] doubles) belongs to the handle,
+ * is allocated by run_series while recording is on and freed by the first run_series with recording off.  enable is 0 or 1; the
+ * default of a new handle is 0; the setting survives ssme_lw_reset, ssme_lw_run_series and ssme_lw_step (which neither records
+ * nor clears).  Recording changes nothing else that any call returns.  Makes no HIP call.
+ * NULL handle or enable outside {0, 1}: SSME_ERR_INVALID_ARG; sharded handle: SSME_ERR_STATE. */
+int ssme_lw_set_series_expectations(ssme_lw_handle h, int32_t enable);
+/* Rows 0 .. T-1 of the last recorded series: out[(t*n + i)*R + r] = E[functionals[i]] of filter r after step t, ids as for
+ * ssme_lw_get_expectations (chosen here, at read time).  Row t equals, bit for bit and NaN for NaN, what
+ * ssme_lw_get_expectations returns after step t of a handle of the same configuration and seed stepped with ssme_lw_step: for
+ * both forms, any resamp_sched, and on both routes of ssme_lw_get_series_route.  Where a filter's weights are NaN, infinite or
+ * all zero its rows are NaN and the call returns SSME_OK.
+ * Checked before any HIP call: NULL handle, out or functionals, n outside 1..8, an id outside 0..7, T < 1 or T beyond the last
+ * recorded series: SSME_ERR_INVALID_ARG; sharded handle: SSME_ERR_STATE; nothing recorded (recording was off during the last
+ * ssme_lw_run_series, or there has been none): SSME_ERR_STATE. */
+int ssme_lw_get_series_expectations(ssme_lw_handle h, const int32_t* functionals, int32_t n, double* out /* [T][n][R] */, int32_t T);
 /* Arbitrary host-side h: particles x (N), UNTRANSFORMED parameters theta[d*N + i] (4N) and weights w (N) of one filter
  * after the last step, w_i = exp(logw_i - max logw) in the resampler's fixed point; any pointer but w may be NULL. */
 int ssme_lw_download_weights(ssme_lw_handle h, int32_t filter, double* x, double* theta_untrans, double* w);

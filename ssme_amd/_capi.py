@@ -32,7 +32,7 @@ EXPORTS = [
     "ssme_pf_version",
     "ssme_lw_create", "ssme_lw_destroy", "ssme_lw_reset", "ssme_lw_step", "ssme_lw_run_series", "ssme_lw_get_per_step",
     "ssme_lw_get_param_means", "ssme_lw_get_expectations", "ssme_lw_download_weights", "ssme_lw_download_state", "ssme_lw_set_debug", "ssme_lw_last_elapsed_ms", "ssme_lw_sim_future_obs", "ssme_lw_forecast_elapsed_ms",
-    "ssme_lw_last_error", "ssme_lw_set_small_series", "ssme_lw_get_series_route",
+    "ssme_lw_last_error", "ssme_lw_set_small_series", "ssme_lw_get_series_route", "ssme_lw_set_series_expectations", "ssme_lw_get_series_expectations",
     "ssme_lw_shard_create", "ssme_lw_set_stream", "ssme_lw_shard_prepare", "ssme_lw_shard_init", "ssme_lw_shard_plan",
     "ssme_lw_shard_stage1", "ssme_lw_shard_mid", "ssme_lw_shard_stage2", "ssme_lw_shard_finalize", "ssme_lw_get_loglik", "ssme_lw_shard_run_series", "ssme_lw_shard_download", "ssme_lw_shard_stats", "ssme_lw_shard_layout",
 ]
@@ -160,6 +160,8 @@ def lib():
         L.ssme_lw_set_debug.argtypes = [H, C.c_int32]
         L.ssme_lw_set_small_series.argtypes = [H, C.c_int32]
         L.ssme_lw_get_series_route.argtypes = [H, i32p, i32p]
+        L.ssme_lw_set_series_expectations.argtypes = [H, C.c_int32]
+        L.ssme_lw_get_series_expectations.argtypes = [H, i32p, C.c_int32, dp, C.c_int32]
         L.ssme_lw_last_elapsed_ms.argtypes = [H, C.POINTER(C.c_float)]
         L.ssme_lw_sim_future_obs.argtypes = [H, C.c_int32, dp, dp, dp, u32p, dp]
         L.ssme_lw_forecast_elapsed_ms.argtypes = [H, C.POINTER(C.c_float), C.POINTER(C.c_float)]

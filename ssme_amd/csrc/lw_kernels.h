@@ -822,6 +822,28 @@ __global__ __launch_bounds__(kThreads) void k_lw_finalize(const LwArgs a) {
 // w = q_j exp(m_tile - m), into the moment scratch mom[r][b][0..7]; k_lw_param_means, grid = (R): adds the tile partials
 // in tile order and divides: out[r][0..3] = E[theta_d], [4] = E[x], [5] = E[x^2], [6] = E[exp(x/2)], [7] = E[42].
 constexpr int kLwNExp = 8;
+// The arithmetic of the two kernels, stated once: the whole-series kernel's recording (lw_small.h, lw_record_expectations) calls the
+// same two functions, so a recorded row has the bits of the two launches (-ffp-contract=off: equal expressions give equal bits).
+// One particle's terms onto the running sums Q0 .. Q1-1 of the eight: [0..3] w theta_d (untransformed), [4] w, [5] w x, [6] w x^2,
+// [7] w exp(x/2).  (A caller short of registers takes the eight in several passes: every sum is its own chain.)
+template <int Q0, int Q1, class KIND>
+__device__ __forceinline__ void lw_expect_terms(double (&acc)[kLwNExp], double w, double xv, const double (&trec)[kDP], KIND kind,
+                                                const ExpTabEntry* etab) {
+    if constexpr (Q0 <= kDP && kDP < Q1) acc[kDP] += w;
+#pragma unroll
+    for (int d = 0; d < kDP; ++d)
+        if (Q0 <= d && d < Q1) acc[d] += w * tr_inv(kind(d), trec[d], etab);
+    if constexpr (Q0 <= 5 && 5 < Q1) acc[5] += w * xv;
+    if constexpr (Q0 <= 6 && 6 < Q1) acc[6] += w * (xv * xv);
+    if constexpr (Q0 <= 7 && 7 < Q1) acc[7] += w * dexp(0.5 * xv);
+}
+// Sum q of a filter (t) and its weight total (den) into the filter's row out[0..7]: [0..3] E[theta_d], [4] E[x], [5] E[x^2],
+// [6] E[exp(x/2)], [7] E[42]
+__device__ __forceinline__ void lw_expect_store(double* out, int q, double t, double den) {
+    if (q < kDP) out[q] = t / den;
+    else if (q == kDP) out[7] = 42.0 * (den / den);          // NaN weights stay NaN
+    else if (q < kLwNExp) out[q - 1] = t / den;               // x, x^2, exp(x/2) -> slots 4, 5, 6
+}
 __global__ __launch_bounds__(kThreads) void k_lw_param_partials(const LwArgs a) {
     __shared__ double lds_n[4][kLwNExp];
     __shared__ double lds_m[16];
@@ -838,13 +860,9 @@ __global__ __launch_bounds__(kThreads) void k_lw_param_partials(const LwArgs a) 
         const double c0 = (i & (kTile - 1)) ? a.cdfB[(size_t)r * a.Npad + i - 1] : 0.0;
         const double w = (c1 - c0) * scale;
         const double xv = a.xB[(size_t)r * a.Npad + i];
-        acc[kDP] += w;
         double trec[kDP];
         th_load(a.thB, (size_t)r * a.Npad + i, trec);
-        for (int d = 0; d < kDP; ++d) acc[d] += w * tr_inv(a.trans[d], trec[d], kExpTable);
-        acc[5] += w * xv;
-        acc[6] += w * (xv * xv);
-        acc[7] += w * dexp(0.5 * xv);
+        lw_expect_terms<0, kLwNExp>(acc, w, xv, trec, [&](int d) { return a.trans[d]; }, kExpTable);
     }
     for (int q = 0; q < kLwNExp; ++q) {
         double v = acc[q];
@@ -870,9 +888,7 @@ __global__ __launch_bounds__(kWave) void k_lw_param_means(const LwArgs a, double
         }
     }
     const double den = __shfl(t, kDP, kWave);
-    if (q < kDP) out[(size_t)r * kLwNExp + q] = t / den;
-    else if (q == kDP) out[(size_t)r * kLwNExp + 7] = 42.0 * (den / den);          // NaN weights stay NaN
-    else if (q < kLwNExp) out[(size_t)r * kLwNExp + q - 1] = t / den;               // x, x^2, exp(x/2) -> slots 4, 5, 6
+    lw_expect_store(out + (size_t)r * kLwNExp, q, t, den);
 }
 
 // weights w_j = q_j exp(m_tile - m) 2^-41 and UNTRANSFORMED parameters of one filter, for host-side functionals.

@@ -14,6 +14,10 @@
 // log-weight).  There is one copy of the population: a thread reads all of its sources into registers, passes a barrier, then
 // stores (the resampling gather and the k gather alike).  The second-stage log-weights stay in registers (schedules m_rs > 1
 // carry them).  After the loop the kernel accounts step T-1 as k_lw_finalize does and writes back what a later call reads.
+//
+// Recording instantiations (ssme_lw_set_series_expectations): the same kernel with a third argument,
+// LwSeriesRec, writes the eight filtered expectations of EVERY step (lw_record_expectations) with the bits of the step API's
+// read-out, k_lw_param_partials + k_lw_param_means.  The instantiations without it are untouched by that code.
 #pragma once
 #include "lw_kernels.h"
 #include "pf_small.h"
@@ -64,11 +68,78 @@ __device__ __forceinline__ void lw_cdf_to_lds(const double (&lg)[2][2], double* 
     for (int k = 0; k < NK; ++k) *reinterpret_cast<double2*>(lds_cdf + (k * NT + tid) * 2) = make_double2(inc[k][0], inc[k][1]);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Recorded series: row t of the trajectory is what k_lw_param_partials + k_lw_param_means form from memory after step t of the
+// step API.  At the recording points LDS holds what they read -- the particles, the transformed theta records and the tile-local
+// integer cdf of step t -- and mb is the tile maximum.  The sums follow THEIR trees at B = 1, not this kernel's 512 x 2 x 2 map:
+//   terms      virtual thread v of 256 adds particles v, v + 256, ... < N in this order, w = (cdf_j - cdf_{j-1}) dexp(mb - m) with
+//              m = mb through the NaN-propagating maximum (the scale is evaluated: mb = +-inf gives NaN rows there and here);
+//              lw_expect_terms is the one statement of the eight terms
+//   combining  the 64 virtual lanes of a wave by the xor butterfly 32 .. 1, the four waves as ((w0 + w1) + w2) + w3
+//   final      one tile: 0.0 + partial, then lw_expect_store (the quotients and 42 (den / den))
+// The first 256 threads play the virtual threads.  One barrier in front of the reads (the cdf stores of this step), one before the
+// wave sums are combined; every later store to lds_x / lds_th / lds_cdf lies behind the second one.  LDS grows by 4 x 8 doubles.
+// ---------------------------------------------------------------------------------------------------------------------
+struct LwSeriesRec {
+    double* traj;              // [T][R][8]
+};
+__device__ __forceinline__ const LwSeriesRec& the_lw_rec(const LwSeriesRec& rec) { return rec; }      // the one element of RECARG...
+
+// the wave sums of the running sums Q0 .. Q1-1 (the first 256 threads)
+template <bool FT, int Q0, int Q1>
+__device__ __forceinline__ void lw_record_pass(const LwArgs& a, const double* lds_x, const double* lds_th, const double* lds_cdf, double mb,
+                                               const ExpTabEntry* etab, double (*lds_n)[kLwNExp]) {
+    int tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));          // opaque: the pass's addresses are formed here, not hoisted out of the time loop (6 VGPRs spill otherwise)
+    const double m = (mb != mb) ? dnan() : mb;
+    const double scale = dexp(mb - m);
+    double acc[kLwNExp] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int j = tid; j < a.N; j += kThreads) {
+        const double c1 = lds_cdf[j];
+        const double c0 = j ? lds_cdf[j - 1] : 0.0;
+        const double w = (c1 - c0) * scale;
+        const double xv = lds_x[j];
+        double trec[kDP];
+        th_load(lds_th, (size_t)j, trec);
+        lw_expect_terms<Q0, Q1>(acc, w, xv, trec, [&](int d) { return lw_trans_kind<FT>(a.trans, d); }, etab);
+    }
+#pragma unroll
+    for (int q = Q0; q < Q1; ++q) {
+        const double v = wave_sum_xor(acc[q]);
+        if ((tid & 63) == 0) lds_n[tid >> 6][q] = v;
+    }
+}
+
+template <bool FT>
+__device__ __forceinline__ void lw_record_expectations(const LwSeriesRec& rec, const LwArgs& a, int r, int t, const double* lds_x,
+                                                       const double* lds_th, const double* lds_cdf, double mb, const ExpTabEntry* etab,
+                                                       double (*lds_n)[kLwNExp]) {
+    const int tid = threadIdx.x;
+    __syncthreads();
+    if (tid < kThreads) {
+        // three passes (phi, mu | sigma, rho, the weight total | the state): the kernel has no registers to spare, and in one pass
+        // or two the FT instantiation spills 2 VGPRs (profiles/lw_series_expectations_kernels.txt).  Every sum is its own chain, so
+        // the passes change no bit.
+        lw_record_pass<FT, 0, 2>(a, lds_x, lds_th, lds_cdf, mb, etab, lds_n);
+        lw_record_pass<FT, 2, kDP + 1>(a, lds_x, lds_th, lds_cdf, mb, etab, lds_n);
+        lw_record_pass<FT, kDP + 1, kLwNExp>(a, lds_x, lds_th, lds_cdf, mb, etab, lds_n);
+    }
+    __syncthreads();
+    if (tid < kLwNExp) {
+        const double part = ((lds_n[0][tid] + lds_n[1][tid]) + lds_n[2][tid]) + lds_n[3][tid];
+        const double wsum = ((lds_n[0][kDP] + lds_n[1][kDP]) + lds_n[2][kDP]) + lds_n[3][kDP];
+        lw_expect_store(rec.traj + ((size_t)t * a.R + r) * kLwNExp, tid, 0.0 + part, 0.0 + wsum);
+    }
+}
+
 // grid = (R), block = 512, dynamic LDS = kLwSeriesLdsBytes.  a.t / yi / gi are ignored (t = yi = gi = 1 .. T-1); a.per_step
 // receives the T log conditional likelihoods, a.scal the sums; a.xB / thB / cdfB / tsumB / tmaxB (/ lwB) hold step 0 on entry
 // (k_lw_init) and the population after step T-1 on exit.
-template <bool FT>
-__global__ __launch_bounds__(kLwNT) void k_lw_series(const LwArgs a, const int T) {
+// RECARG: empty, or LwSeriesRec for the recording instantiation, which takes it as a third kernel argument; `if constexpr` keeps every
+// line of the recording out of the other instantiation, whose arguments and code are what they were without it.
+template <bool FT, class... RECARG>
+__global__ __launch_bounds__(kLwNT) void k_lw_series(const LwArgs a, const int T, const RECARG... recarg) {
+    constexpr bool REC = sizeof...(RECARG) > 0;
     constexpr int NT = kLwNT, NK = 2;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     double* lds_th = reinterpret_cast<double*>(smem);       // [2048][4]
@@ -87,6 +158,11 @@ __global__ __launch_bounds__(kLwNT) void k_lw_series(const LwArgs a, const int T
     __shared__ double lds_ms[2];
     __shared__ __attribute__((aligned(16))) DrawTabs lds_dtab;
     __shared__ ExpTabEntry lds_etab[SSME_EXP_TABLE_SIZE];
+    double (*lds_n)[kLwNExp] = nullptr;                     // recording: the wave sums of the eight expectation sums
+    if constexpr (REC) {
+        __shared__ double red[4][kLwNExp];
+        lds_n = red;
+    }
     load_log_table<NT>(&lds_dtab);
     load_exp_table<NT>(lds_etab);
 
@@ -117,6 +193,7 @@ __global__ __launch_bounds__(kLwNT) void k_lw_series(const LwArgs a, const int T
     in_n.y = 0.0; in_n.z = 0.0; in_n.gamB = 0.0; in_n.pgamB = 0.0; in_n.GB = 1.0; in_n.gamA = 0.0; in_n.pgamA = 0.0; in_n.GA = 1.0;
     in_n.load(a, r, 1, T);
     __syncthreads();
+    if constexpr (REC) lw_record_expectations<FT>(the_lw_rec(recarg...), a, r, 0, lds_x, lds_th, lds_cdf, mb_prev, lds_etab, lds_n);
 
     for (int t = 1; t < T; ++t) {
         const LwSeriesInputs in = in_n;
@@ -331,6 +408,7 @@ __global__ __launch_bounds__(kLwNT) void k_lw_series(const LwArgs a, const int T
         lw_cdf_to_lds(lgB, lds_cdf, lds_dB, lds_seg_cB, lds_etab, A_prev, mb_prev, []() {});
         // (no closing barrier: the next step's first use of these stores is behind the barrier of its resampling draw's scan, or
         // the one it passes instead)
+        if constexpr (REC) lw_record_expectations<FT>(the_lw_rec(recarg...), a, r, t, lds_x, lds_th, lds_cdf, mb_prev, lds_etab, lds_n);
     }
     __syncthreads();
 

@@ -1816,6 +1816,10 @@ struct ssme_lw_s : HandleCore {
     uint32_t* ancbuf;        // unsharded handles: this step's resampling ancestors, stage 1 -> stage 2 (compose mode, lw_kernels.h)
     int fixed_trans;                 // the transform set is (logit, null, log, twice_fisher): stage kernels with it compiled in (lw_trans_kind)
     int small_series;                // 1: one-tile filters run steps 1 .. T-1 of a series in one launch (lw_small.h; lw_series_route decides)
+    // recorded series (ssme_lw_set_series_expectations): the eight filtered expectations of every step of a run_series
+    int rec_series;                  // the switch; survives reset, run_series and step
+    double* traj;                    // [traj_cap][R][8]; held only while recording is on
+    int traj_cap, traj_T;            // time rows traj holds; rows the last run_series recorded (0: none)
     // C++ shard driver (ssme_lw_shard_run_series): halo buffers ([margin | own | margin] rows of 2048 doubles; theta rows of 8192),
     // this rank's stage outputs for the gathers, the gathered arrays
     double *sh_xB, *sh_thB, *sh_cdfB, *sh_xr, *sh_thr, *sh_g1, *sh_cdfA;
@@ -1961,15 +1965,42 @@ constexpr int kLwSmallSeriesDefault = 1;     // the default route of a new handl
 static int lw_series_route(const ssme_lw_s* h) {
     return (h->shard_world == 0 && h->B == 1 && h->small_series) ? SSME_ROUTE_LW_SERIES : SSME_ROUTE_TILED;
 }
-static const void* lw_series_kernel(bool ft) {
-    return ft ? reinterpret_cast<const void*>(&k_lw_series<true>) : reinterpret_cast<const void*>(&k_lw_series<false>);
+static const void* lw_series_kernel(bool ft, bool rec) {
+    static const void* const tab[2][2] = {
+        {reinterpret_cast<const void*>(&k_lw_series<false>), reinterpret_cast<const void*>(&k_lw_series<true>)},
+        {reinterpret_cast<const void*>(&k_lw_series<false, LwSeriesRec>), reinterpret_cast<const void*>(&k_lw_series<true, LwSeriesRec>)}};
+    return tab[rec][ft];
 }
-// steps 1 .. T-1, the accounting of every step and the hand-over, behind k_lw_init
+// steps 1 .. T-1, the accounting of every step and the hand-over, behind k_lw_init; a recording handle: rows 0 .. T-1 of the trajectory
 static void lw_launch_series(ssme_lw_handle h, int T) {
     LwArgs a = lw_args(h);
     a.per_step = h->per_step;
-    void* args[] = {&a, &T};
-    hipLaunchKernel(lw_series_kernel(h->fixed_trans), dim3(h->R), dim3(kLwNT), args, kLwSeriesLdsBytes, h->stream);
+    LwSeriesRec rec = {h->traj};
+    void* args[] = {&a, &T, &rec};           // (the non-recording instantiations take the first two)
+    hipLaunchKernel(lw_series_kernel(h->fixed_trans, h->rec_series), dim3(h->R), dim3(kLwNT), args, kLwSeriesLdsBytes, h->stream);
+}
+// The trajectory buffer for T time rows while recording is on; the first non-recording run_series frees it.  Nothing counts as
+// recorded until the series has been queued.
+static int lw_ensure_trajectory(ssme_lw_handle h, int T) {
+    h->traj_T = 0;
+    if (!h->rec_series) {
+        own_free(h, h->traj);
+        h->traj_cap = 0;
+        return SSME_OK;
+    }
+    if (T > h->traj_cap) {
+        h->traj_cap = 0;                     // capacity 0 while the buffer is replaced: a failed allocation leaves none
+        HIPCHK(own_alloc(h, h->traj, sizeof(double) * (size_t)T * h->R * kLwNExp));
+        h->traj_cap = T;
+    }
+    return SSME_OK;
+}
+// tiled route, recording: the step API's read-out behind step t, with row t of the trajectory as its output.  The per-tile moment
+// scratch is free between steps (stage 1 rewrites it before k_lw_mid reads it), and the buffers of step t are `xB` / `thB` by now.
+static void lw_enqueue_expect_row(ssme_lw_handle h, int t) {
+    LwArgs a = lw_args(h);
+    hipLaunchKernelGGL(k_lw_param_partials, dim3(h->B, h->R), dim3(kThreads), 0, h->stream, a);
+    hipLaunchKernelGGL(k_lw_param_means, dim3(h->R), dim3(kWave), 0, h->stream, a, h->traj + (size_t)t * h->R * kLwNExp);
 }
 
 static int lw_reset(ssme_lw_handle h) {
@@ -2030,7 +2061,8 @@ static int lw_create_impl(const ssme_lw_config* cfg, int shard_rank, int shard_w
                 for (int ft = 0; ft < 2; ++ft)
                     HIPCHK(grant_lds(lw_stage_kernel(stage, big, ft), big ? h->lds_bytes_big : h->lds_bytes, cfg->device));
         if (h->shard_world == 0 && h->B == 1)
-            for (int ft = 0; ft < 2; ++ft) HIPCHK(grant_lds(lw_series_kernel(ft), kLwSeriesLdsBytes, cfg->device));
+            for (int ft = 0; ft < 2; ++ft)
+                for (int rec = 0; rec < 2; ++rec) HIPCHK(grant_lds(lw_series_kernel(ft, rec), kLwSeriesLdsBytes, cfg->device));
         if (h->shard_world == 0) {               // a sharded handle works on the caller's buffers
             for (double** p : {&h->xB, &h->xr, &h->lw1, &h->cdfA, &h->cdfB}) HIPCHK(own_alloc(h, *p, sizeof(double) * np, Mem::zeroed));
             if (h->rs > 1) HIPCHK(own_alloc(h, h->lwB, sizeof(double) * np, Mem::zeroed));
@@ -2388,6 +2420,7 @@ int ssme_lw_run_series(ssme_lw_handle h, const double* y, const double* z, int32
     if (T < 1) return SSME_ERR_LENGTH;
     HIPCHK(hipSetDevice(h->cfg.device));
     int rc = lw_ensure_capacity(h, T);
+    if (rc == SSME_OK) rc = lw_ensure_trajectory(h, T);
     if (rc != SSME_OK) return rc;
     HIPCHK(hipMemcpyAsync(h->ybuf, y, sizeof(double) * T, hipMemcpyHostToDevice, h->stream));
     if (z) HIPCHK(hipMemcpyAsync(h->zbuf, z, sizeof(double) * T, hipMemcpyHostToDevice, h->stream));
@@ -2400,12 +2433,16 @@ int ssme_lw_run_series(ssme_lw_handle h, const double* y, const double* z, int32
         lw_enqueue_step(h, 0, 0, 0, true, false);             // k_lw_init
         lw_launch_series(h, T);
     } else {
-        for (int t = 0; t < T; ++t) lw_enqueue_step(h, t, t, t, true, /*finalize_prev=*/t > 0);
+        for (int t = 0; t < T; ++t) {
+            lw_enqueue_step(h, t, t, t, true, /*finalize_prev=*/t > 0);
+            if (h->rec_series) lw_enqueue_expect_row(h, t);
+        }
         lw_enqueue_finalize(h, T - 1, true);
     }
     HIPCHK(hipEventRecord(h->ev1, h->stream));
     HIPCHK(hipGetLastError());
     h->t = T;
+    if (h->rec_series) h->traj_T = T;
     rc = read_loglik(h, loglik_out);
     if (rc != SSME_OK) return rc;
     HIPCHK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
@@ -2414,6 +2451,8 @@ int ssme_lw_run_series(ssme_lw_handle h, const double* y, const double* z, int32
 
 int ssme_lw_get_per_step(ssme_lw_handle h, double* out, int32_t T) { return read_per_step(h, out, T); }
 
+// the table's slot of a functional id: ids 0-3: x, x^2, exp(x/2), 42; 4-7: phi, mu, sigma, rho
+static const int kLwExpectSlot[8] = {4, 5, 6, 7, 0, 1, 2, 3};
 // [R][8] on the host: E[theta_d] (4), E[x], E[x^2], E[exp(x/2)], E[42] under the last step's weights
 static int lw_expect_table(ssme_lw_handle h, std::vector<double>& tab) {
     LwArgs a = lw_args(h);
@@ -2448,8 +2487,33 @@ int ssme_lw_get_expectations(ssme_lw_handle h, const int32_t* functionals, int32
     std::vector<double> tab;
     int rc = lw_expect_table(h, tab);
     if (rc != SSME_OK) return rc;
-    static const int slot[8] = {4, 5, 6, 7, 0, 1, 2, 3};      // ids 0-3: x, x^2, exp(x/2), 42; 4-7: phi, mu, sigma, rho
-    for (int i = 0; i < n; ++i) for (int r = 0; r < h->R; ++r) out[(size_t)i * h->R + r] = tab[(size_t)r * kLwNExp + slot[functionals[i]]];
+    for (int i = 0; i < n; ++i) for (int r = 0; r < h->R; ++r) out[(size_t)i * h->R + r] = tab[(size_t)r * kLwNExp + kLwExpectSlot[functionals[i]]];
+    return SSME_OK;
+}
+
+int ssme_lw_set_series_expectations(ssme_lw_handle h, int32_t enable) {
+    if (!h || enable < 0 || enable > 1) return SSME_ERR_INVALID_ARG;
+    if (h->shard_world > 0) return SSME_ERR_STATE;     // sharded handles are driven by ssme_lw_shard_*
+    // the trajectory buffer follows at the next run_series (lw_ensure_trajectory), which also frees it once recording is off
+    h->rec_series = enable;
+    return SSME_OK;
+}
+
+int ssme_lw_get_series_expectations(ssme_lw_handle h, const int32_t* functionals, int32_t n, double* out, int32_t T) {
+    if (!h || !out || !functionals || n < 1 || n > kLwNExp) return SSME_ERR_INVALID_ARG;
+    for (int i = 0; i < n; ++i) if (functionals[i] < 0 || functionals[i] > 7) return SSME_ERR_INVALID_ARG;
+    if (T < 1) return SSME_ERR_INVALID_ARG;
+    if (h->shard_world > 0) return SSME_ERR_STATE;
+    if (h->traj_T < 1) { h->err = "no recorded series: ssme_lw_set_series_expectations(1), then ssme_lw_run_series"; return SSME_ERR_STATE; }
+    if (T > h->traj_T) return SSME_ERR_INVALID_ARG;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    std::vector<double> tab((size_t)T * h->R * kLwNExp);
+    HIPCHK(hipMemcpyAsync(tab.data(), h->traj, sizeof(double) * tab.size(), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (int t = 0; t < T; ++t)
+        for (int i = 0; i < n; ++i)
+            for (int r = 0; r < h->R; ++r)
+                out[((size_t)t * n + i) * h->R + r] = tab[((size_t)t * h->R + r) * kLwNExp + kLwExpectSlot[functionals[i]]];
     return SSME_OK;
 }
 

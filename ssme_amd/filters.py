@@ -620,6 +620,24 @@ class svol_lw_1_par:
         self._chk(capi.lib().ssme_lw_get_expectations(self._h, fs.ctypes.data_as(C.POINTER(C.c_int32)), fs.size, capi.dptr(out)))
         return out
 
+    def record_series_expectations(self, on=True):
+        """Have every following run_series record the eight values expectations() can return at EVERY step
+        (ssme_lw_set_series_expectations); on=False switches it off again.  Survives reset / run_series / filter."""
+        self._chk(capi.lib().ssme_lw_set_series_expectations(self._h, 1 if on else 0))
+
+    def series_expectations(self, functionals=range(8)):
+        """[T, n, R]: row t = what expectations(functionals) returns after step t of a stepped twin, to the bit, for the last
+        recorded run_series (ids as for expectations())."""
+        fs = np.ascontiguousarray(list(functionals), dtype=np.int32)
+        T = max(self._T, 1)                      # before any run_series: one row, so that the library answers (nothing recorded)
+        out = np.empty((T, fs.size, self.r))
+        self._chk(capi.lib().ssme_lw_get_series_expectations(self._h, fs.ctypes.data_as(C.POINTER(C.c_int32)), fs.size, capi.dptr(out), T))
+        return out
+
+    def series_param_means(self):
+        """[T, R, 4]: param_means() after every step of the last recorded run_series (E[phi], E[mu], E[sigma], E[rho])."""
+        return np.ascontiguousarray(self.series_expectations((4, 5, 6, 7)).transpose(0, 2, 1))
+
     def weights(self, f=0):
         """(x, untransformed theta [4, N], w) of filter f after the last step, for host-side functionals h(x, z, theta)."""
         x, th, w = np.empty(self.n), np.empty((4, self.n)), np.empty(self.n)
