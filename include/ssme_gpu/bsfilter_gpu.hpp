@@ -708,6 +708,18 @@ inline std::vector<double> series_rows(ssme_pf_handle h, std::size_t T, std::siz
                : ssme_pf_get_series_expectations(h, out.data(), (std::int32_t)T), h);
     return out;
 }
+// Smoothing (ssme_pf_set_series_history; ssme_pf.h): K trajectories per filter drawn from the final weights and traced back through the
+// resampling ancestors, [((r * K + k) * T + t) * dimx + d], and the smoothed means of built-in functionals, [(t * ids + i) * R + r]
+inline std::vector<double> sampled_trajectories(ssme_pf_handle h, std::size_t K, std::size_t T, std::size_t R, std::size_t dimx) {
+    std::vector<double> out(R * K * T * dimx);
+    check(ssme_pf_sample_trajectories(h, (std::int32_t)K, nullptr, out.data(), nullptr, (std::int32_t)T), h);
+    return out;
+}
+inline std::vector<double> smoothed_rows(ssme_pf_handle h, const std::vector<std::int32_t>& ids, std::size_t T, std::size_t R) {
+    std::vector<double> out(T * (ids.empty() ? 1 : ids.size()) * R);
+    check(ssme_pf_get_smoothed_expectations(h, ids.data(), (std::int32_t)ids.size(), out.data(), (std::int32_t)T), h);
+    return out;
+}
 }  // namespace detail
 
 // ---- persistent evaluator: one handle, one captured graph, a fresh random stream per call --------------------------
@@ -744,6 +756,14 @@ public:
         n_rec_ = ids.size();                               // after the check: a rejected list changes nothing
     }
     std::vector<double> series_expectations() const { return detail::series_rows(h_.get(), y_.size(), n_run_, ll_.size(), false); }
+    // Smoothing: record_history(true) makes the evaluations that follow keep every step's particles and ancestors on the device
+    // (ssme_pf_set_series_history).  Valid after operator(), until the next one: sample_trajectories(K)[(r * K + k) * T + t], K state
+    // paths per replicate from p(x_{0:T-1} | y_{0:T-1}) -- a PMMH iteration that accepts theta picks replicate r with probability
+    // proportional to exp(logliks()[r]) and takes trajectory 0 of it -- and smoothed_expectations(ids)[(t * ids + i) * num_pfilters + r].
+    void record_history(bool on = true) { check(ssme_pf_set_series_history(h_.get(), on ? 1 : 0), h_.get()); }
+    std::vector<double> sample_trajectories(std::size_t K) const { return detail::sampled_trajectories(h_.get(), K, y_.size(), ll_.size(), 1); }
+    std::vector<double> smoothed_expectations(const std::vector<std::int32_t>& ids) const { return detail::smoothed_rows(h_.get(), ids, y_.size(), ll_.size()); }
+    const std::vector<double>& logliks() const { return ll_; }          // the replicates' log-likelihoods of the last evaluation
 
 private:
     handle h_;
@@ -795,6 +815,11 @@ public:
     std::vector<double> series_user_expectations() const {
         return detail::series_rows(h_.get(), T_, (std::size_t)ssme_pf_user_model_n_h(), ll_.size(), true);
     }
+    // Smoothing, as svol_log_like_evaluator offers it: sample_trajectories(K)[((r * K + k) * T + t) * dimx + d] (all state components),
+    // smoothed_expectations(ids) of built-in functionals (component 0 of the state); the header's own functionals are not smoothed.
+    void record_history(bool on = true) { check(ssme_pf_set_series_history(h_.get(), on ? 1 : 0), h_.get()); }
+    std::vector<double> sample_trajectories(std::size_t K) const { return detail::sampled_trajectories(h_.get(), K, T_, ll_.size(), dimx); }
+    std::vector<double> smoothed_expectations(const std::vector<std::int32_t>& ids) const { return detail::smoothed_rows(h_.get(), ids, T_, ll_.size()); }
 
 private:
     void apply_recording(const std::vector<std::int32_t>& ids, bool user) {

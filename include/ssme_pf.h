@@ -213,6 +213,53 @@ int ssme_pf_swarm_aggregate_user(ssme_pf_handle h, int32_t num_threads, double* 
 int ssme_pf_set_series_expectations(ssme_pf_handle h, const int32_t* functionals, int32_t n, int32_t user);
 int ssme_pf_get_series_expectations(ssme_pf_handle h, double* out /* [T][n][R] */, int32_t T);
 int ssme_pf_get_series_user_expectations(ssme_pf_handle h, double* out /* [T][n_h][R] */, int32_t T);
+/* SMOOTHING: the distribution p(x_{0:T-1} | y_{0:T-1}) of a series, as sampled state trajectories and as smoothed means (what a
+ * particle-marginal Metropolis-Hastings caller needs to sample the latent states jointly with theta; the reference has no
+ * counterpart: its filters keep no genealogy).  DESIGN.md section 12; kernels in ssme_amd/csrc/smooth.h.
+ * Definitions.  The population of step t is x_t[j], pre-resampling, as ssme_pf_download_state returns it (dim_x planes for a vector
+ * model).  A step t >= 1 with t % resamp_sched == 0 drew anc_t[j], an index into the population of step t - 1; on every other step
+ * anc_t is the identity.  The lineage of final particle j is B_{T-1}(j) = j, B_{t-1}(j) = anc_t[B_t(j)].  The smoothing weights are
+ * the final step's fixed-point weights (q_j of the integer cdf, tile scales e^{m_b - m}): exactly the weights
+ * ssme_pf_get_expectations_multi and the start draw of ssme_pf_sim_future_obs use.
+ * ssme_pf_set_series_history: with enable = 1 the ssme_pf_run_series calls that follow keep every step's population (all planes) and
+ * ancestors on the device -- T R Npad (8 dim_x + 4) bytes, Npad = tiles x tile_particles (ssme_pf_get_layout), which
+ * ssme_pf_series_history_bytes reports before the run.  On the tiled route (graph or eager) the step kernel writes its particles
+ * straight into the history rows (no extra traffic) and runs its general instantiation, as under set_debug(1); one-tile filters
+ * (N <= 2048) keep their whole-series kernels, in a recording instantiation that also serves ssme_pf_set_series_expectations.  A
+ * recording run returns the log-likelihoods, per-step values, final state and recorded expectations of a non-recording run, to the
+ * bit; a run that records neither the history nor series expectations launches the kernels it launched before this setting existed,
+ * instruction for instruction (profiles/series_history_stock_kernels.txt, which also lists what moved in the recording kernels).
+ * With set_debug(1) as well, ssme_pf_download_state's ancestors after a recording run are those of the last step that resampled, as
+ * after a non-recording run.
+ * The setting (default 0) survives run_series, set_params, set_seed and reset; a cached graph of the other configuration is dropped;
+ * the rows are allocated by run_series (a refused allocation: SSME_ERR_HIP with ssme_pf_last_error; the handle stays usable, holds no
+ * rows and no history is in force: the smoothing calls answer SSME_ERR_STATE until a recording run_series has succeeded) and
+ * freed by the first run_series with the setting off.  NULL handle, enable outside {0, 1}: SSME_ERR_INVALID_ARG; sharded: SSME_ERR_STATE.
+ * ssme_pf_series_history_bytes: NULL handle or bytes, T < 1: SSME_ERR_INVALID_ARG; sharded: SSME_ERR_STATE.  Makes no HIP call.
+ * ssme_pf_sample_trajectories: K (1 .. N) trajectories per filter, traced back on the device in ONE launch.  terminal[r * K + k]:
+ * the final particle trajectory k of filter r ends at; NULL: drawn from the smoothing weights by the forecast's start draw
+ * (counter (k, t0 = T, filter id, start stream), the same search), so index_out[(r K + k) T + T - 1] == start_out[r N + k] of
+ * ssme_pf_sim_future_obs from the same origin -- a sampled path and its simulated continuation join.
+ * x_out[((r K + k) T + t) dim_x + d] = component d of x_t[B_t]; index_out[(r K + k) T + t] = B_t, or NULL.
+ * ssme_pf_get_smoothed_expectations: out[(t n + i) R + r] = sum_j h_i(x_t[B_t(j)]) w_j / sum_j w_j over all N final particles, for
+ * n = 1 .. 4 built-in functionals (SSME_H_*; component 0 of a vector state), by the summation trees of the filtered expectations:
+ * row T - 1 is ssme_pf_get_expectations_multi after the series, to the bit.  One backward launch and one finishing launch.
+ * Both: a filter without weight (all weights zero, -inf or NaN, e.g. `bad` parameters) gets NaN states / NaN rows and the call
+ * returns SSME_OK; two calls from one history return the same bits; SSME_F32 handles round x_out / out to float.
+ * Validated before any HIP call -- SSME_ERR_INVALID_ARG: NULL handle or x_out / out / functionals, K < 1 or K > N, a terminal index
+ * >= N, n < 1 or n > 4, a functional id out of range, T different from the recorded series' length; SSME_ERR_STATE: a sharded
+ * handle (as ssme_pf_run_series answers), or no history in force -- recording off during the last ssme_pf_run_series, no
+ * ssme_pf_run_series yet, a ssme_pf_run_series that failed, or any later ssme_pf_step, ssme_pf_run_series, ssme_pf_profile_series, ssme_pf_reset, ssme_pf_set_params
+ * or ssme_pf_set_seed on the handle (they change or discard the state the smoothing weights live in).  Forecasts, expectation
+ * getters and downloads do not invalidate the history.
+ * ssme_pf_smoothing_elapsed_ms: HIP-event times of the last of the two calls: its kernels alone, and the call without the download.
+ * Out of scope: the functionals of a user header, fixed-lag smoothing, Liu-West handles and sharded handles. */
+int ssme_pf_set_series_history(ssme_pf_handle h, int32_t enable);
+int ssme_pf_series_history_bytes(ssme_pf_handle h, int32_t T, uint64_t* bytes);
+int ssme_pf_sample_trajectories(ssme_pf_handle h, int32_t K, const uint32_t* terminal /*[R][K] or NULL: drawn as above*/,
+                                double* x_out /*[((r*K + k)*T + t)*dim_x + d]*/, uint32_t* index_out /*[(r*K + k)*T + t] or NULL*/, int32_t T);
+int ssme_pf_get_smoothed_expectations(ssme_pf_handle h, const int32_t* functionals, int32_t n, double* out /*[(t*n + i)*R + r]*/, int32_t T);
+int ssme_pf_smoothing_elapsed_ms(ssme_pf_handle h, float* kernel_ms, float* call_ms);
 /* Arbitrary host-side h (the reference's filt_func is a std::function, pswarm_filter.h:44,87-89): particles x (N,
  * nullable) and weights w (N) of one filter after the last step, w_j = exp(logw_j - max logw) in the 2^-41 fixed point
  * the resampler and ssme_pf_get_expectations use; the caller forms sum h(x_j) w_j / sum w_j.  Needs no debug mode. */

@@ -20,7 +20,7 @@ H_X, H_X2, H_VOL, H_CONST42 = 0, 1, 2, 3
 ROUTE_TILED, ROUTE_SERIES_LANE, ROUTE_SERIES_PAIR, ROUTE_LW_SERIES = 0, 1, 2, 3
 
 EXPORTS = [
-    "ssme_pf_create", "ssme_pf_destroy", "ssme_pf_default_tile", "ssme_pf_user_model_n_theta", "ssme_pf_user_model_dims", "ssme_pf_user_model_n_h", "ssme_pf_user_model_has_gsamp", "ssme_pf_user_model_dim_cov", "ssme_pf_user_model_has_first", "ssme_pf_get_user_expectations", "ssme_pf_swarm_aggregate_user", "ssme_pf_set_series_expectations", "ssme_pf_get_series_expectations", "ssme_pf_get_series_user_expectations", "ssme_pf_set_params", "ssme_pf_reset", "ssme_pf_set_seed", "ssme_pf_set_small_series", "ssme_pf_get_series_route", "ssme_pf_shard_create", "ssme_pf_set_stream",
+    "ssme_pf_create", "ssme_pf_destroy", "ssme_pf_default_tile", "ssme_pf_user_model_n_theta", "ssme_pf_user_model_dims", "ssme_pf_user_model_n_h", "ssme_pf_user_model_has_gsamp", "ssme_pf_user_model_dim_cov", "ssme_pf_user_model_has_first", "ssme_pf_get_user_expectations", "ssme_pf_swarm_aggregate_user", "ssme_pf_set_series_expectations", "ssme_pf_get_series_expectations", "ssme_pf_get_series_user_expectations", "ssme_pf_set_series_history", "ssme_pf_series_history_bytes", "ssme_pf_sample_trajectories", "ssme_pf_get_smoothed_expectations", "ssme_pf_smoothing_elapsed_ms", "ssme_pf_set_params", "ssme_pf_reset", "ssme_pf_set_seed", "ssme_pf_set_small_series", "ssme_pf_get_series_route", "ssme_pf_shard_create", "ssme_pf_set_stream",
     "ssme_pf_shard_prepare", "ssme_shard_comm_get_unique_id", "ssme_shard_comm_init", "ssme_shard_comm_destroy", "ssme_pf_shard_run_series",
     "ssme_pf_shard_download", "ssme_pf_shard_stats", "ssme_pf_shard_layout", "ssme_pf_shard_plan", "ssme_pf_shard_step", "ssme_pf_shard_finalize", "ssme_pf_step",
     "ssme_pf_run_series", "ssme_pf_get_per_step", "ssme_pf_get_loglik", "ssme_pf_get_expectations", "ssme_pf_get_expectations_multi", "ssme_pf_swarm_aggregate", "ssme_pf_swarm_aggregate_threads", "ssme_pf_download_weights", "ssme_pf_get_layout",
@@ -113,6 +113,11 @@ def lib():
         L.ssme_pf_set_series_expectations.argtypes = [H, i32p, C.c_int32, C.c_int32]
         L.ssme_pf_get_series_expectations.argtypes = [H, dp, C.c_int32]
         L.ssme_pf_get_series_user_expectations.argtypes = [H, dp, C.c_int32]
+        L.ssme_pf_set_series_history.argtypes = [H, C.c_int32]
+        L.ssme_pf_series_history_bytes.argtypes = [H, C.c_int32, u64p]
+        L.ssme_pf_sample_trajectories.argtypes = [H, C.c_int32, u32p, dp, u32p, C.c_int32]
+        L.ssme_pf_get_smoothed_expectations.argtypes = [H, i32p, C.c_int32, dp, C.c_int32]
+        L.ssme_pf_smoothing_elapsed_ms.argtypes = [H, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         L.ssme_pf_download_state.argtypes = [H, C.c_int32, dp, dp, u64p, u32p]
         L.ssme_pf_download_scalars.argtypes = [H, C.c_int32, dp, u64p, u64p, dp, i32p]
         L.ssme_pf_set_debug.argtypes = [H, C.c_int32]

@@ -269,15 +269,25 @@ static int elapsed_ms(const HandleCore* h, float* ms) {
 // ---- forecast: what ssme_pf_sim_future_obs and ssme_lw_sim_future_obs do around their own kernels ---------------------------
 // The common buffers and the events on first use (x0: x0_planes planes of [R][Npad]), the samples grown to ny / nx doubles (nx = 0:
 // no states asked for), the event of the call's start, and fc.h_last_obs (filled by the caller) on its way to the device.
+// what forecast_plan writes: the level-2 tables and S' of the start draw, on first use (also the smoothing calls', which draw their
+// terminal particles as the forecast draws its start population and need nothing else of it)
+static int forecast_tables(HandleCore* h) {
+    Forecast& f = h->fc;
+    const size_t R = h->R, nb = R * h->Bs;
+    if (!f.T) HIPCHK(own_alloc(h, f.T, sizeof(double) * nb));
+    if (!f.R) HIPCHK(own_alloc(h, f.R, sizeof(double) * nb));
+    if (!f.scal) HIPCHK(own_alloc(h, f.scal, sizeof(FilterScalars) * R, Mem::zeroed));
+    return SSME_OK;
+}
+
 template <class H>
 static int forecast_prepare(H* h, int x0_planes, size_t ny, size_t nx) {
     Forecast& f = h->fc;
     HIPCHK(hipSetDevice(h->cfg.device));
-    const size_t R = h->R, nb = R * h->Bs, np = R * h->Npad;
-    if (!f.T) {
-        HIPCHK(own_alloc(h, f.T, sizeof(double) * nb));
-        HIPCHK(own_alloc(h, f.R, sizeof(double) * nb));
-        HIPCHK(own_alloc(h, f.scal, sizeof(FilterScalars) * R, Mem::zeroed));
+    const size_t R = h->R, np = R * h->Npad;
+    const int rc = forecast_tables(h);
+    if (rc != SSME_OK) return rc;
+    if (!f.last) {
         HIPCHK(own_alloc(h, f.last, sizeof(double) * R));
         HIPCHK(own_alloc(h, f.x0, sizeof(double) * np * x0_planes));
         HIPCHK(own_alloc(h, f.start, sizeof(uint32_t) * np));

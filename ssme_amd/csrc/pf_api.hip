@@ -8,6 +8,8 @@
 #include "lw_small.h"
 #include "user_expect.h"
 #include "forecast.h"
+#include "smooth.h"
+#include "series_history.h"
 #include "handle_core.h"
 #include "shard_driver.h"
 
@@ -80,6 +82,18 @@ struct ssme_pf_s : HandleCore {
     double *traj, *utraj;        // [traj_cap][rec_fs.n][R], [traj_cap][n_h][R]; held only while recording is on
     int traj_cap, traj_n;        // time rows both hold; built-in functionals traj was sized for
     int rec_T, rec_n, rec_nh;    // what the last run_series recorded: rows, built-in functionals, user functionals
+    // series history and smoothing (ssme_pf_set_series_history; smooth.h): the populations and ancestors of every step of a run_series
+    SeriesHistoryState hist;     // the setting, the rows the buffers hold, the history in force (series_history.h)
+    double* hist_x;              // [hist_cap][dx][R][Npad]
+    uint32_t* hist_anc;          // [hist_cap][R][Npad]
+    int hist_live;               // enqueue_step is queuing a recording series: x and the ancestors go to the history rows
+    int g_hist;                  // the cached graph was captured with the history on
+    double* sm_x;                // [R][K][T][dx] sampled trajectories, sm_cap_x doubles
+    uint32_t *sm_idx, *sm_term;  // [R][K][T] their lineage indices, [R][K] given terminal indices
+    size_t sm_cap_x, sm_cap_idx, sm_cap_term, sm_cap_part;
+    double *sm_part, *sm_out;    // [T][R][Bs][4] per-tile numerators of the sweep, [T][4][R] its rows
+    hipEvent_t sm_ev[3];         // call start, backward kernel start, kernels' end
+    float sm_ms_kernel, sm_ms_call;
     std::vector<ModelConst> h_mc;
     // forecast (HandleCore::fc): fc.x0 is [dx][R][Npad], the samples fc.y / fc.x [R][H][dy][Ns] / [R][H][dx][Ns]
     std::vector<double> h_gscale;    // per filter: scale of the observation draw (set_params)
@@ -389,6 +403,9 @@ static void launch_kf(ssme_pf_handle h, int t, bool record_per_step, double* ll_
     hipLaunchKernelGGL(kf_finalize, dim3(h->R), dim3(kThreads), 0, h->stream, a);
 }
 
+// row t of the series history: the dx planes of the population of step t
+static double* hist_row(const ssme_pf_s* h, int t) { return h->hist_x + (size_t)t * h->dx * h->R * h->Npad; }
+
 // enqueue one filter step at time index t reading y[yi] and gamma-table row gi
 static void enqueue_step(ssme_pf_handle h, int t, int yi, int gi, bool has_z, bool finalize_prev, bool record_per_step,
                          bool from_step_staging = false, bool results_to_host = true) {
@@ -402,6 +419,12 @@ static void enqueue_step(ssme_pf_handle h, int t, int yi, int gi, bool has_z, bo
     }
     a.per_step = record_per_step ? h->per_step : nullptr;
     a.t = t; a.yi = yi; a.gi = gi; a.finalize_prev = finalize_prev ? 1 : 0;
+    if (h->hist_live) {
+        // a recording series: the step reads the population of row t - 1 and writes row t of the history in place of the ping-pong
+        // buffers (no extra traffic), and its ancestors go to row t -- which selects the general instantiation, as the debug flag does
+        a.x_in = hist_row(h, t > 0 ? t - 1 : 0); a.x_out = hist_row(h, t);
+        a.anc = h->hist_anc + (size_t)t * h->R * h->Npad;
+    }
     if (h->split_l2 && t > 0) launch_plan(h, t, gi, true, finalize_prev, record_per_step);
     launch_step(h, a);
     h->cur ^= 1;
@@ -444,7 +467,12 @@ static void enqueue_series_small(ssme_pf_handle h, int T, bool has_z) {
     a.z = has_z ? h->zbuf : nullptr;
     a.per_step = h->per_step;
     a.small_ms = h->small_ms;
-    if (recording(h)) {
+    if (h->hist.on) {
+        SeriesHist hs{};
+        hs.fs = h->rec_fs; hs.traj = h->traj; hs.utraj = h->rec_user ? h->utraj : nullptr;
+        hs.hx = h->hist_x; hs.hanc = h->hist_anc;
+        with_model(h->cfg.model, [&](auto m) { launch_small_m<decltype(m)::value>(h, a, T, hs); });
+    } else if (recording(h)) {
         const SeriesRec rec = {h->rec_fs, h->traj, h->rec_user ? h->utraj : nullptr};
         with_model(h->cfg.model, [&](auto m) { launch_small_m<decltype(m)::value>(h, a, T, rec); });
     } else with_model(h->cfg.model, [&](auto m) { launch_small_m<decltype(m)::value>(h, a, T); });
@@ -500,6 +528,7 @@ static int do_reset(ssme_pf_handle h) {
     if (h->l2_ticket) HIPCHK(hipMemsetAsync(h->l2_ticket, 0, sizeof(int32_t) * h->R, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));   // sc is a temporary
     h->t = 0; h->cur = 0;
+    h->hist.moved_on();                         // the smoothing weights live in the state that is discarded here
     h->gamma_rows = 0;                          // tables are redrawn for the new stream / the new series
     return SSME_OK;
 }
@@ -535,7 +564,7 @@ template <class M>
 static void enqueue_user_expectations_row(ssme_pf_handle h, int row, bool has_z, double* out) {
     constexpr int NH = user_nh<M>::n;
     if constexpr (NH > 0) {
-        hipLaunchKernelGGL(k_user_expect_partials_row<M>, dim3(h->B, h->R), dim3(kThreads), 0, h->stream, (const double*)h->x[h->cur],
+        hipLaunchKernelGGL(k_user_expect_partials_row<M>, dim3(h->B, h->R), dim3(kThreads), 0, h->stream, (const double*)(h->hist_live ? hist_row(h, row) : h->x[h->cur]),
                            (size_t)h->R * h->Npad, (const double*)h->cdf[h->cur], (const ModelConst*)h->mc,
                            (const double*)(has_z ? h->zbuf : nullptr), row, h->N, h->Npad, h->Bs, h->tile, h->uexp_part);
         hipLaunchKernelGGL(k_user_expect_final<NH>, dim3(h->R), dim3(kThreads), 0, h->stream, (const double*)h->uexp_part,
@@ -586,6 +615,31 @@ static int ensure_trajectory(ssme_pf_handle h, int T) {
         HIPCHK(own_alloc(h, h->uexp_part, sizeof(double) * (size_t)h->R * h->Bs * kUserNH));
         HIPCHK(own_alloc(h, h->uexp_out, sizeof(double) * (size_t)kUserNH * h->R));
     }
+    return SSME_OK;
+}
+
+// Series history: the rows for T steps while the setting is on (a failed allocation leaves none and the handle usable); off: no buffers.
+static int ensure_history(ssme_pf_handle h, int T) {
+    if (!h->hist.on) {
+        if (h->hist_x || h->hist_anc) { drop_graph(h); own_free(h, h->hist_x); own_free(h, h->hist_anc); }
+        h->hist.rows_dropped();
+        return SSME_OK;
+    }
+    if (T <= h->hist.cap) return SSME_OK;
+    // the rows are replaced: whatever history they held is no longer in force, whether or not the new allocation succeeds
+    drop_graph(h);
+    own_free(h, h->hist_x); own_free(h, h->hist_anc);
+    h->hist.rows_dropped();
+    const size_t np = (size_t)h->R * h->Npad;
+    hipError_t e = own_alloc(h, h->hist_x, sizeof(double) * (size_t)T * h->dx * np);
+    if (e == hipSuccess) e = own_alloc(h, h->hist_anc, sizeof(uint32_t) * (size_t)T * np);
+    if (e != hipSuccess) {
+        own_free(h, h->hist_x); own_free(h, h->hist_anc);
+        (void)hipGetLastError();                       // the refused allocation is reported here, not by the next call's launch check
+        h->err = std::string("series history (ssme_pf_series_history_bytes): ") + hipGetErrorString(e);
+        return SSME_ERR_HIP;
+    }
+    h->hist.rows_ready(T);
     return SSME_OK;
 }
 
@@ -716,6 +770,7 @@ int ssme_pf_destroy(ssme_pf_handle h) {
     if (!h) return SSME_ERR_INVALID_ARG;
     hipSetDevice(h->cfg.device);
     if (h->gexec) { hipStreamSynchronize(h->stream); hipGraphExecDestroy(h->gexec); }
+    for (hipEvent_t& e : h->sm_ev) if (e) hipEventDestroy(e);
     release_core(h);
     delete h;
     return SSME_OK;
@@ -1159,6 +1214,7 @@ int ssme_pf_step(ssme_pf_handle h, const double* y, const double* z, double* out
     if (h->split_l2) launch_kf(h, h->t, false, want ? h->pin_dev + PinLayout::results : nullptr);
     HIPCHK(hipGetLastError());
     h->t += 1;
+    h->hist.moved_on();                                // the final weights of the recorded series are gone
     if (want) HIPCHK(wait_results(h->stream, res, h->R));
     if (out) for (int r = 0; r < h->R; ++r) out[r] = res[r];
     round_out(h, out, h->R);
@@ -1173,9 +1229,11 @@ static void set_last_z(ssme_pf_handle h, const double* z, int T) {
 
 // Recorded series, tiled route: behind step t the partial and final expectation kernels of the step API, writing slot t of the
 // trajectories instead of exp_out / uexp_out.  They read the buffers the step wrote (now `cur`), as after ssme_pf_step.
+// the particles step t of the series being queued wrote: the ping-pong buffer, or row t of the history
+static const double* series_x(const ssme_pf_s* h, int t) { return h->hist_live ? hist_row(h, t) : h->x[h->cur]; }
 static void enqueue_step_expectations(ssme_pf_handle h, int t, bool has_z) {
     if (h->rec_fs.n > 0) {
-        hipLaunchKernelGGL(k_expect_partials, dim3(h->B, h->R), dim3(kThreads), 0, h->stream, h->x[h->cur], h->cdf[h->cur], h->N,
+        hipLaunchKernelGGL(k_expect_partials, dim3(h->B, h->R), dim3(kThreads), 0, h->stream, series_x(h, t), h->cdf[h->cur], h->N,
                            h->Npad, h->Bs, h->tile, h->rec_fs, h->exp_part);
         hipLaunchKernelGGL(k_expect_final, dim3(h->R), dim3(kThreads), 0, h->stream, h->exp_part, h->tsum[h->cur], h->tmax[h->cur],
                            h->B, h->Bs, h->R, h->rec_fs, h->traj + (size_t)t * h->rec_fs.n * h->R);
@@ -1185,14 +1243,27 @@ static void enqueue_step_expectations(ssme_pf_handle h, int t, bool has_z) {
 #endif
 }
 
-static void enqueue_series(ssme_pf_handle h, int T, bool has_z) {
+static hipError_t enqueue_series(ssme_pf_handle h, int T, bool has_z) {
     launch_gamma(h, 0, T);
     const bool rec = recording(h);
+    h->hist_live = h->hist.on;
     for (int t = 0; t < T; ++t) {
         enqueue_step(h, t, t, t, has_z, /*finalize_prev=*/t > 0, /*per_step=*/true);
         if (rec) enqueue_step_expectations(h, t, has_z);
     }
     launch_kf(h, T - 1, true);
+    hipError_t e = hipSuccess;
+    if (h->hist_live) {
+        // the final population where every later call looks for it, and the debug ancestors as a non-recording run leaves them: the
+        // indices of the LAST DRAW, i.e. of the last step that resampled (a step that did not wrote no row; no draw at all: untouched)
+        const size_t np = (size_t)h->R * h->Npad;
+        const int t_draw = ((T - 1) / h->cfg.resamp_sched) * h->cfg.resamp_sched;
+        e = hipMemcpyAsync(h->x[h->cur], hist_row(h, T - 1), sizeof(double) * np * h->dx, hipMemcpyDeviceToDevice, h->stream);
+        if (e == hipSuccess && h->debug_anc && t_draw >= 1)
+            e = hipMemcpyAsync(h->anc, h->hist_anc + (size_t)t_draw * np, sizeof(uint32_t) * np, hipMemcpyDeviceToDevice, h->stream);
+    }
+    h->hist_live = 0;
+    return e;
 }
 
 int ssme_pf_run_series(ssme_pf_handle h, const double* y, const double* z, int32_t T, double* loglik_out) {
@@ -1202,8 +1273,10 @@ int ssme_pf_run_series(ssme_pf_handle h, const double* y, const double* z, int32
     if (!h->params_set) return SSME_ERR_STATE;
     HIPCHK(hipSetDevice(h->cfg.device));
     h->rec_T = 0;                                      // rows are valid once the series is queued; a failure below leaves none
+    h->hist.moved_on();                                // ... and no history in force: the one of an earlier series ends here
     int rc = ensure_series_capacity(h, T);
     if (rc == SSME_OK) rc = ensure_trajectory(h, T);
+    if (rc == SSME_OK) rc = ensure_history(h, T);
     if (rc != SSME_OK) return rc;
     std::vector<double> y32, z32;
     if (h->cfg.dtype == SSME_F32) {
@@ -1226,17 +1299,18 @@ int ssme_pf_run_series(ssme_pf_handle h, const double* y, const double* z, int32
         HIPCHK(hipEventRecord(h->ev1, h->stream));
     } else if (h->graph_mode) {
         if (!h->gexec || h->g_T != T || h->g_has_z != (int)has_z || h->g_debug != h->debug_anc || h->g_logw != lw ||
-            h->g_nt != h->nt || h->g_rec_user != h->rec_user || std::memcmp(&h->g_rec_fs, &h->rec_fs, sizeof(FunctionalIds)) != 0) {
+            h->g_nt != h->nt || h->g_hist != h->hist.on || h->g_rec_user != h->rec_user || std::memcmp(&h->g_rec_fs, &h->rec_fs, sizeof(FunctionalIds)) != 0) {
             if (h->gexec) { hipGraphExecDestroy(h->gexec); h->gexec = nullptr; }
             hipGraph_t g = nullptr;
             HIPCHK(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
             h->cur = 0;
-            enqueue_series(h, T, has_z);
+            const hipError_t queued = enqueue_series(h, T, has_z);
             HIPCHK(hipStreamEndCapture(h->stream, &g));
+            if (queued != hipSuccess) { hipGraphDestroy(g); return fail(h, "enqueue_series (capture)", queued); }
             HIPCHK(hipGraphInstantiate(&h->gexec, g, nullptr, nullptr, 0));
             HIPCHK(hipGraphDestroy(g));
             h->g_T = T; h->g_has_z = has_z; h->g_debug = h->debug_anc; h->g_logw = lw; h->g_nt = h->nt;
-            h->g_rec_fs = h->rec_fs; h->g_rec_user = h->rec_user;
+            h->g_rec_fs = h->rec_fs; h->g_rec_user = h->rec_user; h->g_hist = h->hist.on;
         }
         HIPCHK(hipEventRecord(h->ev0, h->stream));
         HIPCHK(hipGraphLaunch(h->gexec, h->stream));
@@ -1245,7 +1319,7 @@ int ssme_pf_run_series(ssme_pf_handle h, const double* y, const double* z, int32
     } else {
         HIPCHK(hipEventRecord(h->ev0, h->stream));
         h->cur = 0;
-        enqueue_series(h, T, has_z);
+        HIPCHK(enqueue_series(h, T, has_z));
         HIPCHK(hipEventRecord(h->ev1, h->stream));
     }
     HIPCHK(hipGetLastError());
@@ -1254,6 +1328,7 @@ int ssme_pf_run_series(ssme_pf_handle h, const double* y, const double* z, int32
     rc = read_loglik(h, loglik_out);
     if (rc != SSME_OK) return rc;
     HIPCHK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
+    h->hist.recorded(T);                               // in force until the handle moves on (run_series, do_reset, ssme_pf_step)
     round_out(h, loglik_out, h->R);
     return SSME_OK;
 }
@@ -1297,6 +1372,153 @@ int ssme_pf_get_series_expectations(ssme_pf_handle h, double* out, int32_t T) {
 }
 int ssme_pf_get_series_user_expectations(ssme_pf_handle h, double* out, int32_t T) {
     return read_trajectory(h, h ? h->utraj : nullptr, h ? h->rec_nh : 0, out, T);
+}
+
+// ---- series history and smoothing (kernels: smooth.h; recording: enqueue_step, enqueue_series_small) ----
+int ssme_pf_set_series_history(ssme_pf_handle h, int32_t enable) {
+    if (!h || enable < 0 || enable > 1) return SSME_ERR_INVALID_ARG;
+    if (h->shard_world > 0) return SSME_ERR_STATE;
+    h->hist.on = enable;
+    // a cached graph of the other configuration is not replayed (the cache key of ssme_pf_run_series holds the setting); the history
+    // rows follow at the next run_series (ensure_history), which also frees them once the setting is off
+    if (h->gexec && h->g_hist != h->hist.on) {
+        HIPCHK(hipSetDevice(h->cfg.device));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        drop_graph(h);
+    }
+    return SSME_OK;
+}
+
+int ssme_pf_series_history_bytes(ssme_pf_handle h, int32_t T, uint64_t* bytes) {
+    if (!h || !bytes || T < 1) return SSME_ERR_INVALID_ARG;
+    if (h->shard_world > 0) return SSME_ERR_STATE;
+    *bytes = (uint64_t)T * (uint64_t)h->R * (uint64_t)h->Npad * (uint64_t)(8 * h->dx + 4);
+    return SSME_OK;
+}
+
+// What both smoothing calls check after their own arguments, and what they share: the level-2 tables of the final weights (the
+// forecast's, by the forecast's code), the events, the start event.  SSME_OK: `a` describes the history in force.
+static int smoothing_begin(ssme_pf_handle h, int T, SmArgs* a) {
+    if (h->shard_world > 0) { h->err = "smoothing of particle-sharded filters is not implemented"; return SSME_ERR_STATE; }
+    switch (h->hist.query(h->hist_x && h->hist_anc, T)) {
+        case SeriesHistoryState::none: h->err = "no series history in force: ssme_pf_set_series_history, then ssme_pf_run_series"; return SSME_ERR_STATE;
+        case SeriesHistoryState::other_length: return SSME_ERR_INVALID_ARG;
+        default: break;
+    }
+    HIPCHK(hipSetDevice(h->cfg.device));
+    int rc = forecast_tables(h);                       // the level-2 tables and S' alone: nothing else of the forecast is touched
+    if (rc != SSME_OK) return rc;
+    for (hipEvent_t& e : h->sm_ev) if (!e) HIPCHK(hipEventCreate(&e));
+    HIPCHK(hipEventRecord(h->sm_ev[0], h->stream));
+    StepArgs p = step_args(h);
+    p.t = h->t;
+    forecast_plan(h, p);
+    SmArgs s{};
+    s.hx = h->hist_x; s.hanc = h->hist_anc; s.cdf = h->cdf[h->cur]; s.l2_T = h->fc.T; s.l2_R = h->fc.R; s.scal = h->fc.scal;
+    s.keyp = h->keybuf; s.first_filter = h->cfg.first_filter_id;
+    s.N = h->N; s.Npad = h->Npad; s.B = h->B; s.Bs = h->Bs; s.Bpow2 = h->Bpow2; s.tile = h->tile; s.R = h->R; s.T = T;
+    s.resamp_sched = h->cfg.resamp_sched; s.dx = h->dx;
+    *a = s;
+    HIPCHK(hipEventRecord(h->sm_ev[1], h->stream));
+    return SSME_OK;
+}
+// ... and after their downloads are queued: the wait and the two times
+static int smoothing_end(ssme_pf_handle h) {
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipEventElapsedTime(&h->sm_ms_kernel, h->sm_ev[1], h->sm_ev[2]));
+    HIPCHK(hipEventElapsedTime(&h->sm_ms_call, h->sm_ev[0], h->sm_ev[2]));
+    return SSME_OK;
+}
+extern "C++" {
+// a device buffer of the smoothing calls grown to n elements (capacity 0 while it is replaced: a failed allocation leaves none)
+template <class T>
+static int sm_grow(ssme_pf_handle h, T*& p, size_t& cap, size_t n) {
+    if (n <= cap) return SSME_OK;
+    cap = 0;
+    const hipError_t e = own_alloc(h, p, sizeof(T) * n);
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail(h, "smoothing output buffer", e); }
+    cap = n;
+    return SSME_OK;
+}
+
+template <int DX>
+static void launch_sm_trajectories(ssme_pf_handle h, const SmArgs& a, int K, const uint32_t* term, uint32_t* idx) {
+    hipLaunchKernelGGL((k_sm_trajectories<DX>), dim3((K + kSmChains * kThreads - 1) / (kSmChains * kThreads), h->R), dim3(kThreads), 0, h->stream,
+                       a, K, term, h->sm_x, idx);
+}
+}  // extern "C++"
+
+int ssme_pf_sample_trajectories(ssme_pf_handle h, int32_t K, const uint32_t* terminal, double* x_out, uint32_t* index_out, int32_t T) {
+    if (!h || !x_out || K < 1 || K > h->N || T < 1) return SSME_ERR_INVALID_ARG;
+    if (terminal)
+        for (size_t i = 0; i < (size_t)h->R * K; ++i)
+            if (terminal[i] >= (uint32_t)h->N) return SSME_ERR_INVALID_ARG;
+    SmArgs a;
+    int rc = smoothing_begin(h, T, &a);
+    if (rc != SSME_OK) return rc;
+    const size_t nk = (size_t)h->R * K, ni = nk * T, nx = ni * h->dx;
+    rc = sm_grow(h, h->sm_x, h->sm_cap_x, nx);
+    if (rc == SSME_OK && index_out) rc = sm_grow(h, h->sm_idx, h->sm_cap_idx, ni);
+    if (rc == SSME_OK && terminal) rc = sm_grow(h, h->sm_term, h->sm_cap_term, nk);
+    if (rc != SSME_OK) return rc;
+    if (terminal) HIPCHK(hipMemcpyAsync(h->sm_term, terminal, sizeof(uint32_t) * nk, hipMemcpyHostToDevice, h->stream));
+    const uint32_t* term = terminal ? h->sm_term : nullptr;
+    uint32_t* idx = index_out ? h->sm_idx : nullptr;
+    switch (h->dx) {
+        case 1: launch_sm_trajectories<1>(h, a, K, term, idx); break;
+        case 2: launch_sm_trajectories<2>(h, a, K, term, idx); break;
+        case 3: launch_sm_trajectories<3>(h, a, K, term, idx); break;
+        default: launch_sm_trajectories<4>(h, a, K, term, idx); break;
+    }
+    HIPCHK(hipEventRecord(h->sm_ev[2], h->stream));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(x_out, h->sm_x, sizeof(double) * nx, hipMemcpyDeviceToHost, h->stream));
+    if (index_out) HIPCHK(hipMemcpyAsync(index_out, h->sm_idx, sizeof(uint32_t) * ni, hipMemcpyDeviceToHost, h->stream));
+    rc = smoothing_end(h);
+    if (rc != SSME_OK) return rc;
+    round_out(h, x_out, nx);
+    return SSME_OK;
+}
+
+int ssme_pf_get_smoothed_expectations(ssme_pf_handle h, const int32_t* functionals, int32_t n, double* out, int32_t T) {
+    if (!h || !out || !functionals || n < 1 || n > kMaxFunctionals || T < 1) return SSME_ERR_INVALID_ARG;
+    FunctionalIds fs{};
+    fs.n = n;
+    for (int i = 0; i < n; ++i) {
+        if (functionals[i] < SSME_H_X || functionals[i] > SSME_H_CONST42) return SSME_ERR_INVALID_ARG;
+        fs.id[i] = functionals[i];
+    }
+    SmArgs a;
+    int rc = smoothing_begin(h, T, &a);
+    if (rc != SSME_OK) return rc;
+    const size_t npart = (size_t)T * h->R * h->Bs * kMaxFunctionals, nout = (size_t)T * n * h->R;
+    if (npart > h->sm_cap_part) {
+        h->sm_cap_part = 0;
+        hipError_t e = own_alloc(h, h->sm_part, sizeof(double) * npart);
+        if (e == hipSuccess) e = own_alloc(h, h->sm_out, sizeof(double) * (size_t)T * kMaxFunctionals * h->R);
+        if (e != hipSuccess) { (void)hipGetLastError(); return fail(h, "smoothing sweep buffers", e); }
+        h->sm_cap_part = npart;
+    }
+    const dim3 grid(h->B, h->R);
+    if (h->tile == kTileSmall) hipLaunchKernelGGL((k_sm_sweep<kTileSmall / kThreads>), grid, dim3(kThreads), 0, h->stream, a, fs, h->sm_part);
+    else if (h->tile == kTileMid) hipLaunchKernelGGL((k_sm_sweep<kTileMid / kThreads>), grid, dim3(kThreads), 0, h->stream, a, fs, h->sm_part);
+    else hipLaunchKernelGGL((k_sm_sweep<kTile / kThreads>), grid, dim3(kThreads), 0, h->stream, a, fs, h->sm_part);
+    hipLaunchKernelGGL(k_sm_final, dim3((unsigned)((size_t)T * h->R)), dim3(kThreads), 0, h->stream, (const double*)h->sm_part,
+                       (const double*)h->tsum[h->cur], (const double*)h->tmax[h->cur], h->B, h->Bs, h->R, fs, h->sm_out);
+    HIPCHK(hipEventRecord(h->sm_ev[2], h->stream));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, h->sm_out, sizeof(double) * nout, hipMemcpyDeviceToHost, h->stream));
+    rc = smoothing_end(h);
+    if (rc != SSME_OK) return rc;
+    round_out(h, out, nout);
+    return SSME_OK;
+}
+
+int ssme_pf_smoothing_elapsed_ms(ssme_pf_handle h, float* kernel_ms, float* call_ms) {
+    if (!h) return SSME_ERR_INVALID_ARG;
+    if (kernel_ms) *kernel_ms = h->sm_ms_kernel;
+    if (call_ms) *call_ms = h->sm_ms_call;
+    return SSME_OK;
 }
 
 int ssme_pf_get_per_step(ssme_pf_handle h, double* out, int32_t T) {

@@ -1871,6 +1871,22 @@ __device__ __forceinline__ double wave_sum_xor(double v) {
     return v;
 }
 
+// The pieces of k_expect_partials' summation tree (shared with the smoothing sweep, smooth.h): one particle into a thread's
+// numerators, the wave sums of a thread's numerators into lds[f][wave], and functional f's tile sum from them (after a barrier).
+__device__ __forceinline__ void expect_add(double (&num)[kMaxFunctionals], const FunctionalIds& fs, double xv, double q) {
+#pragma unroll
+    for (int f = 0; f < kMaxFunctionals; ++f)
+        if (f < fs.n) num[f] = num[f] + builtin_h(fs.id[f], xv) * q;
+}
+__device__ __forceinline__ void expect_wave_sums(double (&num)[kMaxFunctionals], double (*lds)[4], int tid) {
+#pragma unroll
+    for (int f = 0; f < kMaxFunctionals; ++f) {
+        num[f] = wave_sum_xor(num[f]);
+        if ((tid & 63) == 0) lds[f][tid >> 6] = num[f];
+    }
+}
+__device__ __forceinline__ double expect_tile_sum(const double (*lds)[4], int f) { return ((lds[f][0] + lds[f][1]) + lds[f][2]) + lds[f][3]; }
+
 __global__ __launch_bounds__(kThreads) void k_expect_partials(const double* x, const double* cdf, int N, int Npad, int Bs, int tile,
                                                               FunctionalIds fs, double* part /*[R][Bs][kMaxFunctionals]*/) {
     __shared__ double lds[kMaxFunctionals][4];
@@ -1880,29 +1896,21 @@ __global__ __launch_bounds__(kThreads) void k_expect_partials(const double* x, c
     const int nvalid = (N - b * tile) < tile ? (N - b * tile) : tile;
     double num[kMaxFunctionals] = {0.0, 0.0, 0.0, 0.0};
     for (int j = tid; j < nvalid; j += kThreads) {
-        {
-            const double q = cr[j] - (j ? cr[j - 1] : 0.0);
-            const double xv = xr[j];
-#pragma unroll
-            for (int f = 0; f < kMaxFunctionals; ++f)
-                if (f < fs.n) num[f] = num[f] + builtin_h(fs.id[f], xv) * q;
-        }
+        const double q = cr[j] - (j ? cr[j - 1] : 0.0);
+        expect_add(num, fs, xr[j], q);
     }
-#pragma unroll
-    for (int f = 0; f < kMaxFunctionals; ++f) {
-        num[f] = wave_sum_xor(num[f]);
-        if ((tid & 63) == 0) lds[f][tid >> 6] = num[f];
-    }
+    expect_wave_sums(num, lds, tid);
     __syncthreads();
-    if (tid < kMaxFunctionals)
-        part[((size_t)r * Bs + b) * kMaxFunctionals + tid] = ((lds[tid][0] + lds[tid][1]) + lds[tid][2]) + lds[tid][3];
+    if (tid < kMaxFunctionals) part[((size_t)r * Bs + b) * kMaxFunctionals + tid] = expect_tile_sum(lds, tid);
 }
 
-__global__ __launch_bounds__(kThreads) void k_expect_final(const double* part, const double* tsum, const double* tmax, int B, int Bs,
-                                                           int R, FunctionalIds fs, double* out /*[n][R]*/) {
+// k_expect_final's work for filter r: E_f from the per-tile numerators part[(r Bs + b) 4 + f] and the tile sums / maxima, into
+// out[f R + r].  Called by every thread of a kThreads workgroup (also by the smoothing rows, smooth.h).
+__device__ __forceinline__ void expect_final_filter(const double* part, const double* tsum, const double* tmax, int B, int Bs, int R, int r,
+                                                    const FunctionalIds& fs, double* out /*[n][R]*/) {
     __shared__ double lds[kMaxFunctionals + 1][4];
     __shared__ double lds_m[16];
-    const int tid = threadIdx.x, r = blockIdx.x;
+    const int tid = threadIdx.x;
     double mx = -dinf();
     bool nan = false;
     for (int j = tid; j < B; j += kThreads) { const double v = tmax[(size_t)r * Bs + j]; nan = nan || (v != v); mx = (v > mx) ? v : mx; }
@@ -1926,6 +1934,11 @@ __global__ __launch_bounds__(kThreads) void k_expect_final(const double* part, c
         const double d4 = ((lds[kMaxFunctionals][0] + lds[kMaxFunctionals][1]) + lds[kMaxFunctionals][2]) + lds[kMaxFunctionals][3];
         out[(size_t)tid * R + r] = (m != m) ? dnan() : n4 / d4;
     }
+}
+
+__global__ __launch_bounds__(kThreads) void k_expect_final(const double* part, const double* tsum, const double* tmax, int B, int Bs,
+                                                           int R, FunctionalIds fs, double* out /*[n][R]*/) {
+    expect_final_filter(part, tsum, tmax, B, Bs, R, blockIdx.x, fs, out);
 }
 
 // Swarm aggregation in one launch: block f < n: mean over the R members of expectation row f ([n][R] in exp_rows);

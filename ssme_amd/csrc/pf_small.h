@@ -27,6 +27,8 @@
 #pragma once
 #include "pf_kernels.h"
 
+#include <type_traits>
+
 #ifndef SSME_LANE_XDIM_AHEAD
 #define SSME_LANE_XDIM_AHEAD 1             // lane kernel, vector models: the d >= 1 normals of step t + 1 are drawn during step t, as
 #endif                                     // component 0's are (0: at the model step).  Same bits.  Measured both ways: within 0.06 us per
@@ -292,6 +294,17 @@ template <int MODEL> constexpr int model_nh() { return 0; }
 
 __device__ __forceinline__ const SeriesRec& the_rec(const SeriesRec& rec) { return rec; }      // the one element of RECARG...
 
+// Series history (ssme_pf_set_series_history; smooth.h): a third kind of instantiation, RECARG = SeriesHist,
+// that also keeps every step's population (all planes, as hand_over_state lays them out) and the ancestors of every resampling draw:
+// hx row t is [DX][R][Npad] (plane stride a.xplane), hanc row t [R][Npad].  A step that does not resample writes no ancestors: the
+// backward pass reads the schedule.  The expectations are recorded as in the SeriesRec instantiation when any are asked for.
+struct SeriesHist : SeriesRec {
+    double* hx;                // [T][DX][R][Npad]
+    uint32_t* hanc;            // [T][R][Npad]
+};
+template <class... RECARG> constexpr bool series_hist_v = (std::is_same<RECARG, SeriesHist>::value || ...);
+__device__ __forceinline__ const SeriesHist& the_hist(const SeriesHist& hs) { return hs; }
+
 template <int MODEL, int NT, class IN>
 __device__ __forceinline__ void record_step_expectations(const SeriesRec& rec, const StepArgs& a, const ModelConst& mc, const IN& in, int r,
                                                          int t, const double* lds_x, int xstride, const double* lds_cdf, double A,
@@ -382,6 +395,7 @@ __device__ __forceinline__ void record_step_expectations(const SeriesRec& rec, c
 template <int MODEL, int NT, int NK, class... RECARG>
 __global__ __launch_bounds__(NT) void k_filter_series_small(const StepArgs a, const int T, const RECARG... recarg) {
     constexpr bool REC = sizeof...(RECARG) > 0;
+    [[maybe_unused]] constexpr bool HIST = series_hist_v<RECARG...>;       // ... and the one that also keeps the series history
     constexpr int P = 2 * NT * NK;
     // A vector user model (model_api.h): component 0 travels the scalar path below unchanged; components d >= 1 live in planes
     // lds_x + d P, are gathered at the same ancestor, and draw their normals from stream STREAM_XDIM + d (xdim_words) for the
@@ -510,6 +524,7 @@ __global__ __launch_bounds__(NT) void k_filter_series_small(const StepArgs a, co
                 for (int c = 0; c < 2; ++c) {
                     const int anc = jj[c] < a.N - 1 ? jj[c] : a.N - 1;
                     if (a.anc && (i0 + c) < a.N) a.anc[rowoff + i0 + c] = (uint32_t)anc;
+                    if constexpr (HIST) { if ((i0 + c) < a.N) the_hist(recarg...).hanc[(size_t)t * a.xplane + rowoff + i0 + c] = (uint32_t)anc; }
                     xin[k][c] = lds_x[anc];
                     if constexpr (DX > 1) {            // every plane at the one clamped ancestor
 #pragma unroll
@@ -571,11 +586,20 @@ __global__ __launch_bounds__(NT) void k_filter_series_small(const StepArgs a, co
             store_slots<2>(lds_x + i0, xcur[k]);
 #pragma unroll
             for (int d = 1; d < DX; ++d) store_slots<2>(lds_x + d * P + i0, xcv[d][k]);
+            if constexpr (HIST) {                                     // row t of the history: slots i0, i0 + 1 < P <= Npad of every plane
+                double* hx = the_hist(recarg...).hx + (size_t)t * DX * a.xplane + rowoff + i0;
+                store_slots<2>(hx, xcur[k]);
+#pragma unroll
+                for (int d = 1; d < DX; ++d) store_slots<2>(hx + (size_t)d * a.xplane, xcv[d][k]);
+            }
         }
         A_prev = total;
         mb_prev = mb;
         __syncthreads();                                              // cdf / x of step t visible to step t+1
-        if constexpr (REC) record_step_expectations<MODEL, NT>(the_rec(recarg...), a, mc, in, r, t, lds_x, P, lds_cdf, A_prev, mb_prev, lds_etab, lds_red);
+        if constexpr (HIST) {
+            if (the_rec(recarg...).fs.n > 0 || the_rec(recarg...).utraj)
+                record_step_expectations<MODEL, NT>(the_rec(recarg...), a, mc, in, r, t, lds_x, P, lds_cdf, A_prev, mb_prev, lds_etab, lds_red);
+        } else if constexpr (REC) record_step_expectations<MODEL, NT>(the_rec(recarg...), a, mc, in, r, t, lds_x, P, lds_cdf, A_prev, mb_prev, lds_etab, lds_red);
     }
 
     series_accounting<NT>(a, r, T, ms, A_prev, mb_prev, lds_etab);
@@ -592,6 +616,7 @@ __global__ __launch_bounds__(NT) void k_filter_series_small(const StepArgs a, co
 template <int MODEL, int NT, class... RECARG>
 __global__ __launch_bounds__(NT) void k_filter_series_lane(const StepArgs a, const int T, const RECARG... recarg) {
     constexpr bool REC = sizeof...(RECARG) > 0;                // the recording instantiation: RECARG = SeriesRec (see k_filter_series_small)
+    [[maybe_unused]] constexpr bool HIST = series_hist_v<RECARG...>;
     constexpr int P = NT;
     // A vector user model: as in the pair kernel; the pair index of the d >= 1 draws is tid >> 1 and the lane keeps half tid & 1.
     constexpr int DX = model_dx<MODEL>(), DY = model_dy<MODEL>();
@@ -718,6 +743,7 @@ __global__ __launch_bounds__(NT) void k_filter_series_lane(const StepArgs a, con
             draw_for(t + 1);                                   // fills the waits of the descent's LDS reads and of the gather
             const int anc = jj[0] < a.N - 1 ? jj[0] : a.N - 1;
             if (a.anc && valid) a.anc[rowoff + tid] = (uint32_t)anc;
+            if constexpr (HIST) { if (valid) the_hist(recarg...).hanc[(size_t)t * a.xplane + rowoff + tid] = (uint32_t)anc; }
             xin = lds_x[anc];
             if constexpr (DX > 1) {                            // every plane at the one clamped ancestor
 #pragma unroll
@@ -750,10 +776,19 @@ __global__ __launch_bounds__(NT) void k_filter_series_lane(const StepArgs a, con
         lds_x[tid] = xcur;
 #pragma unroll
         for (int d = 1; d < DX; ++d) lds_x[d * P + tid] = xcv[d];
+        if constexpr (HIST) {                                         // row t of the history: slot tid < P <= Npad of every plane
+            double* hx = the_hist(recarg...).hx + (size_t)t * DX * a.xplane + rowoff + tid;
+            *hx = xcur;
+#pragma unroll
+            for (int d = 1; d < DX; ++d) hx[(size_t)d * a.xplane] = xcv[d];
+        }
         A_prev = stot[0];
         mb_prev = mb;
         __syncthreads();                                              // cdf / x of step t visible to step t+1
-        if constexpr (REC) record_step_expectations<MODEL, NT>(the_rec(recarg...), a, mc, in, r, t, lds_x, P, lds_cdf, A_prev, mb_prev, lds_etab, lds_red);
+        if constexpr (HIST) {
+            if (the_rec(recarg...).fs.n > 0 || the_rec(recarg...).utraj)
+                record_step_expectations<MODEL, NT>(the_rec(recarg...), a, mc, in, r, t, lds_x, P, lds_cdf, A_prev, mb_prev, lds_etab, lds_red);
+        } else if constexpr (REC) record_step_expectations<MODEL, NT>(the_rec(recarg...), a, mc, in, r, t, lds_x, P, lds_cdf, A_prev, mb_prev, lds_etab, lds_red);
     }
 
     series_accounting<NT>(a, r, T, ms, A_prev, mb_prev, lds_etab);

@@ -253,6 +253,48 @@ class ParticleFilterBank:
         self._chk(capi.lib().ssme_pf_get_series_user_expectations(self._h, capi.dptr(out), self._last_T))
         return out
 
+    def record_series_history(self, on=True):
+        """Keep every step's population and resampling ancestors of the run_series calls that follow on the device
+        (ssme_pf_set_series_history): what sample_trajectories and smoothed_expectations trace back.  series_history_bytes(T) says
+        what a series of T steps keeps.  Sticky across run_series, set_params, set_seed and reset; changes nothing a run returns."""
+        self._chk(capi.lib().ssme_pf_set_series_history(self._h, 1 if on else 0))
+
+    def series_history_bytes(self, T):
+        """Device bytes the history of a T-step series takes: T R Npad (8 dim_x + 4)."""
+        b = C.c_uint64()
+        self._chk(capi.lib().ssme_pf_series_history_bytes(self._h, int(T), C.byref(b)))
+        return int(b.value)
+
+    def sample_trajectories(self, K, terminal=None, indices=False):
+        """K state trajectories per filter from the smoothing distribution p(x_{0:T-1} | y_{0:T-1}) of the last run_series (recorded
+        with record_series_history), traced back through the resampling ancestors on the device: x[R, K, T, dim_x].  terminal: [R, K]
+        final-particle indices the trajectories end at; None: drawn from the final weights by the forecast's start draw, so
+        trajectory k ends at start[r, k] of sim_future_obs from the same origin.  indices=True: (x, index[R, K, T]), the lineage."""
+        K, T, dx = int(K), self._last_T, self._dims()[0]
+        term = None
+        if terminal is not None:
+            term = np.ascontiguousarray(terminal, dtype=np.uint32)
+            assert term.size == self.r * K, "terminal: [R, K]"
+        x = np.empty((self.r, K, T, dx))
+        idx = np.empty((self.r, K, T), dtype=np.uint32) if indices else None
+        self._chk(capi.lib().ssme_pf_sample_trajectories(self._h, K, capi.u32ptr(term), capi.dptr(x), capi.u32ptr(idx), T))
+        return (x, idx) if indices else x
+
+    def smoothed_expectations(self, functionals):
+        """E[h_i(x_t) | y_{0:T-1}] for every step t of the last run_series (recorded with record_series_history) over all N lineages
+        under the final weights, up to 4 built-in functionals: [T, n, R].  Row T-1 is expectations_multi, to the bit."""
+        fs = np.ascontiguousarray(functionals, dtype=np.int32)
+        out = np.empty((self._last_T, max(fs.size, 1), self.r))
+        self._chk(capi.lib().ssme_pf_get_smoothed_expectations(self._h, fs.ctypes.data_as(C.POINTER(C.c_int32)), fs.size, capi.dptr(out),
+                                                               self._last_T))
+        return out
+
+    def smoothing_elapsed_ms(self):
+        """HIP-event times (ms) of the last sample_trajectories / smoothed_expectations: (kernels alone, call without the download)."""
+        k, c = C.c_float(), C.c_float()
+        self._chk(capi.lib().ssme_pf_smoothing_elapsed_ms(self._h, C.byref(k), C.byref(c)))
+        return k.value, c.value
+
     def swarm_aggregate_user(self, num_threads=0):
         """swarm_aggregate for the user model's own functionals: (mean over filters of the last log conditional likelihoods,
         mean_exp[n_h]) reduced on the device; num_threads as in swarm_aggregate."""
