@@ -25,8 +25,9 @@
 using namespace ssme;
 
 // k_filter_step of one (model, tile): fn[BIG][WL2][RS + 1] at the tile's own workgroup size nt (no BIG + WL2 kernel), and the
-// general 2048-particle kernel at 256 / 1024 threads (ssme_pf_set_tuning)
-struct StepKernels { const void* fn[2][2][3]; const void* wide[2]; int nt; };
+// general 2048-particle kernel at 256 / 1024 threads (ssme_pf_set_tuning); resident[RS]: fn[0][0][RS + 1] of 2048-particle tiles
+// with the schedule and store policy of a grid that is resident at once compiled in (select_step_kernel)
+struct StepKernels { const void* fn[2][2][3]; const void* wide[2]; const void* resident[2]; int nt; };
 
 struct ssme_pf_s : HandleCore {
     ssme_pf_config cfg;
@@ -336,6 +337,10 @@ static StepKernels step_kernels(int tile) {
         fill_step_kernels<MODEL, 512, kTile>(k);
         k.wide[0] = reinterpret_cast<const void*>(&k_filter_step<MODEL, 256, false, kTile, -1>);
         k.wide[1] = reinterpret_cast<const void*>(&k_filter_step<MODEL, 1024, false, kTile, -1>);
+        // the RS >= 0 kernels of filters of more than 128 tiles once more, with the schedule and store policy of a grid that is
+        // resident at once compiled in (step_args: prio_mode 1, streaming stores) -- the flagship shape
+        k.resident[0] = reinterpret_cast<const void*>(&k_filter_step<MODEL, 512, false, kTile, 0, false, true>);
+        k.resident[1] = reinterpret_cast<const void*>(&k_filter_step<MODEL, 512, false, kTile, 1, false, true>);
     }
     return k;
 }
@@ -348,6 +353,8 @@ static hipError_t grant_step_lds(const ssme_pf_s* h) {
                 if (fn && e == hipSuccess) e = grant_lds(fn, big ? h->lds_bytes_big : h->lds_bytes, h->cfg.device);
     for (const void* fn : h->kern.wide)
         if (fn && e == hipSuccess) e = grant_lds(fn, h->lds_bytes, h->cfg.device);
+    for (const void* fn : h->kern.resident)
+        if (fn && e == hipSuccess) e = grant_lds(fn, h->lds_bytes, h->cfg.device);
     return e;
 }
 
@@ -359,6 +366,7 @@ static StepLaunch select_step_kernel(const ssme_pf_s* h, const StepArgs& a) {
         rs = h->cfg.resampler == SSME_RESAMP_MULTINOMIAL ? 0 : (h->cfg.resampler == SSME_RESAMP_SYSTEMATIC ? 1 : -1);
     if (h->split_l2) return {h->kern.fn[1][0][rs + 1], h->kern.nt, h->lds_bytes_big};
     if (h->tile == kTile && h->nt != 512) return {h->kern.wide[h->nt == 1024], h->nt, h->lds_bytes};      // ssme_pf_set_tuning
+    if (rs >= 0 && a.B > 128 && a.prio_mode == 1 && a.stream_stores == 1 && h->kern.resident[rs]) return {h->kern.resident[rs], h->kern.nt, h->lds_bytes};
     return {h->kern.fn[0][a.B <= 128 ? 1 : 0][rs + 1], h->kern.nt, h->lds_bytes};
 }
 static void launch_step_on(ssme_pf_handle h, const StepArgs& a, dim3 grid) {

@@ -175,7 +175,6 @@ __device__ __forceinline__ double row16_incl_scan(double v) {
     v = v + dpp_f64_zero<0x118, 0xF>(v);
     return v;
 }
-__device__ __forceinline__ double wave_shr1_f64(double v) { return dpp_f64_zero<0x138, 0xF>(v); }
 __device__ __forceinline__ double readlane_f64(double v, int lane) {
     const u64 b = d2bits(v);
     const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)b, lane);
@@ -262,6 +261,11 @@ __device__ __forceinline__ double block_max_nanprop(double m, bool nan, double* 
 // Thread tid holds NK pairs: q[k][c] = value[(k*NT + tid)*2 + c].
 // incl[k][c] = sum of all values up to and including that position; total = sum of all.
 // lds_seg: 16 doubles private to this call (no trailing barrier).  One __syncthreads().
+// The first element of a pair is the pair's inclusive sum MINUS the second element, not a second chain of additions from a
+// lane-shifted copy of the wave scan: q is finite, non-negative and integer-valued and every partial sum is an integer below
+// 2^53, so the sum, the difference and the sum built the other way round are the same exactly representable integer -- the same
+// bits (a zero is +0 either way: x - x = +0 in round-to-nearest).  q must be finite: inf - inf would be NaN where the additive
+// form gave inf.
 // ---------------------------------------------------------------------------------------
 template <int NT, int NK>
 __device__ __forceinline__ void block_scan_f64(const double (&q)[NK][2], double (&incl)[NK][2], double& total, double* lds_seg) {
@@ -269,14 +273,11 @@ __device__ __forceinline__ void block_scan_f64(const double (&q)[NK][2], double 
     static_assert(NSEG <= 16, "segment totals are scanned inside one 16-lane row");
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    double s0[NK], s1[NK], exc[NK];
+    double inc[NK];
 #pragma unroll
     for (int k = 0; k < NK; ++k) {
-        s0[k] = q[k][0];
-        s1[k] = s0[k] + q[k][1];
-        const double inc = wave_incl_scan_f64(s1[k]);
-        exc[k] = wave_shr1_f64(inc);
-        if (lane == 63) lds_seg[k * WPR + wave] = inc;
+        inc[k] = wave_incl_scan_f64(q[k][0] + q[k][1]);
+        if (lane == 63) lds_seg[k * WPR + wave] = inc[k];
     }
     __syncthreads();
     const double sv = row16_incl_scan((lane & 15) < NSEG ? lds_seg[lane & 15] : 0.0);
@@ -285,9 +286,8 @@ __device__ __forceinline__ void block_scan_f64(const double (&q)[NK][2], double 
     for (int k = 0; k < NK; ++k) {
         const int seg = k * WPR + wave;
         const double pre = seg ? readlane_f64(sv, seg - 1) : 0.0;
-        const double base = pre + exc[k];
-        incl[k][0] = base + s0[k];
-        incl[k][1] = base + s1[k];
+        incl[k][1] = pre + inc[k];
+        incl[k][0] = incl[k][1] - q[k][1];
     }
 }
 
@@ -631,7 +631,7 @@ __device__ __forceinline__ void prio_at(int mode, int idx) {
         if (idx == 0) __builtin_amdgcn_s_setprio(1); else if (idx == 6) __builtin_amdgcn_s_setprio(0);
     }
 }
-#define PRIO_AT(i) prio_at(a.prio_mode, i)
+#define PRIO_AT(i) prio_at(RESIDENT ? 1 : a.prio_mode, i)        // (k_filter_step only)
 
 // ---------------------------------------------------------------------------------------
 // k_filter_step: one bootstrap-filter step for every tile of every filter.
@@ -640,6 +640,9 @@ __device__ __forceinline__ void prio_at(int mode, int idx) {
 // RS >= 0 compiles the reference's configuration in (resampler RS, resampling every step, t > 0, no debug outputs): the
 // uniform branches of the general kernel disappear and the compiler schedules across what they separated; RS = -1 is
 // the general kernel (any resampler / schedule / t = 0 / ancestor and log-weight recording).  Same arithmetic, same bits.
+// RESIDENT (RS >= 0 only) compiles in what the host chooses for a grid that is resident at once -- prio_mode 1 and streaming
+// stores: each of the twelve PRIO_AT sites is then one s_setprio or nothing instead of a chain of scalar compares and
+// branches on a.prio_mode, and store_pair does not branch.  Scheduling and cache policy only.
 // Phase order is chosen so that arithmetic hides memory latency: the cdf tiles are requested,
 // then the Box-Muller radii are computed while they arrive; the ancestor states are requested,
 // then the Box-Muller angles are computed while they arrive.
@@ -672,47 +675,87 @@ struct lds_count_search<0, NQ> {
 };
 
 // The staged search of one thread: targets tau (integers in the filter's global fixed point) -> positions among the `span`
-// (<= 3) cdf tiles staged in LDS at lds_stage, returned as ELEMENT offsets from the first staged tile (0 .. span TILE - 1).
+// (<= 3) cdf tiles staged in LDS at lds_stage.  staged_search_pos returns them as they are held during the search, ABSOLUTE LDS
+// BYTE ADDRESSES pos = lds_addr(lds_stage) + 8 * (element offset from the first staged tile, 0 .. span TILE - 1): k_filter_step
+// turns one into the gather's byte offset with a single add of a uniform; staged_search returns the element offsets (the
+// Liu-West selection, lw_select, which indexes several arrays with them).
 // Pm / T0 / T1: inclusive prefixes T' of the tile before the first staged tile and of the first two staged tiles;
-// R0..R2: A / A' of the staged tiles.  Shared by k_filter_step and the Liu-West selection (lw_select).
-// A position is an absolute LDS byte address with the tile select folded in, so a probe is ds_read_b64 (constant offset
-// field) + compare + add + select.  The target's tile is a uniform case split on `span`: two staged tiles (the common case)
-// need one compare and three selects per particle instead of two and nine.
+// R0..R2: A / A' of the staged tiles.
+// A position has the tile select folded in, so a probe is ds_read_b64 (constant offset field) + compare + add + select.  The
+// target's tile is a uniform case split on `span`; with two or three staged tiles a WAVE whose targets all fall into one of them
+// (a ballot over the thread's targets: the targets of a workgroup are sorted, so at most span - 1 of its waves contain a
+// crossing) takes a uniform branch with scalar operands and no selects; a wave with a crossing pays one compare and five selects
+// per particle (two staged tiles) or two and nine (three).  The same values either way.
+__device__ __forceinline__ uint32_t lds_addr(const double* p) {
+    typedef __attribute__((address_space(3))) const double lds_cdouble;
+    return (uint32_t)(__UINTPTR_TYPE__)(lds_cdouble*)p;
+}
 template <int TILE, int NK>
-__device__ __forceinline__ void staged_search(const double (&tau)[NK][2], int span, double Pm, double T0, double T1, double R0, double R1,
-                                              double R2, const double* lds_stage, int (&off)[NK][2]) {
+__device__ __forceinline__ void staged_search_pos(const double (&tau)[NK][2], int span, double Pm, double T0, double T1, double R0, double R1,
+                                                  double R2, const double* lds_stage, uint32_t (&pos)[NK][2]) {
     double tloc[NK][2];
     uint32_t pb[NK][2];
-    typedef __attribute__((address_space(3))) const double lds_cdouble;
-    const uint32_t stage_a = (uint32_t)(__UINTPTR_TYPE__)(lds_cdouble*)lds_stage;
-    if (span == 1) {
+    const uint32_t stage_a = lds_addr(lds_stage);
+    auto one_tile = [&](double P, double R, uint32_t base) {
 #pragma unroll
         for (int k = 0; k < NK; ++k) {
 #pragma unroll
-            for (int c = 0; c < 2; ++c) { tloc[k][c] = __builtin_ceil((tau[k][c] - Pm) * R0); pb[k][c] = stage_a; }
+            for (int c = 0; c < 2; ++c) { tloc[k][c] = __builtin_ceil((tau[k][c] - P) * R); pb[k][c] = base; }
         }
-    } else if (span == 2) {
+    };
+    if (span == 1) one_tile(Pm, R0, stage_a);
+    else if (span == 2) {
+        bool any_up = false, all_up = true;
 #pragma unroll
         for (int k = 0; k < NK; ++k) {
 #pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                const bool up = T0 < tau[k][c];
-                tloc[k][c] = __builtin_ceil((tau[k][c] - (up ? T0 : Pm)) * (up ? R1 : R0));
-                pb[k][c] = up ? stage_a + (uint32_t)(TILE * 8) : stage_a;
+            for (int c = 0; c < 2; ++c) { const bool up = T0 < tau[k][c]; any_up = any_up || up; all_up = all_up && up; }
+        }
+        if (!__builtin_amdgcn_ballot_w64(any_up)) {            // the whole wave in the first staged tile
+            asm volatile("");                                  // (kept a branch, as the ragged tile's)
+            one_tile(Pm, R0, stage_a);
+        } else if (!__builtin_amdgcn_ballot_w64(!all_up)) {    // the whole wave in the second
+            asm volatile("");
+            one_tile(T0, R1, stage_a + (uint32_t)(TILE * 8));
+        } else {
+#pragma unroll
+            for (int k = 0; k < NK; ++k) {
+#pragma unroll
+                for (int c = 0; c < 2; ++c) {
+                    const bool up = T0 < tau[k][c];
+                    tloc[k][c] = __builtin_ceil((tau[k][c] - (up ? T0 : Pm)) * (up ? R1 : R0));
+                    pb[k][c] = up ? stage_a + (uint32_t)(TILE * 8) : stage_a;
+                }
             }
         }
     } else {
+        int sel[NK][2];
+        bool differs = false;
 #pragma unroll
         for (int k = 0; k < NK; ++k) {
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
-                const double target = tau[k][c];
-                int sel = (T0 < target ? 1 : 0) + (T1 < target ? 1 : 0);
-                sel = sel < span - 1 ? sel : span - 1;
-                const double Pb = sel == 0 ? Pm : (sel == 1 ? T0 : T1);
-                const double Rb = sel == 0 ? R0 : (sel == 1 ? R1 : R2);
-                tloc[k][c] = __builtin_ceil((target - Pb) * Rb);
-                pb[k][c] = stage_a + (uint32_t)sel * (uint32_t)(TILE * 8);
+                const int s = (T0 < tau[k][c] ? 1 : 0) + (T1 < tau[k][c] ? 1 : 0);
+                sel[k][c] = s < span - 1 ? s : span - 1;
+            }
+        }
+        const int sel_u = __builtin_amdgcn_readfirstlane(sel[0][0]);
+#pragma unroll
+        for (int k = 0; k < NK; ++k) differs = differs || sel[k][0] != sel_u || sel[k][1] != sel_u;
+        if (!__builtin_amdgcn_ballot_w64(differs)) {           // the whole wave in one staged tile
+            asm volatile("");
+            one_tile(sel_u == 0 ? Pm : (sel_u == 1 ? T0 : T1), sel_u == 0 ? R0 : (sel_u == 1 ? R1 : R2), stage_a + (uint32_t)sel_u * (uint32_t)(TILE * 8));
+        } else {
+#pragma unroll
+            for (int k = 0; k < NK; ++k) {
+#pragma unroll
+                for (int c = 0; c < 2; ++c) {
+                    const int s = sel[k][c];
+                    const double Pb = s == 0 ? Pm : (s == 1 ? T0 : T1);
+                    const double Rb = s == 0 ? R0 : (s == 1 ? R1 : R2);
+                    tloc[k][c] = __builtin_ceil((tau[k][c] - Pb) * Rb);
+                    pb[k][c] = stage_a + (uint32_t)s * (uint32_t)(TILE * 8);
+                }
             }
         }
     }
@@ -750,7 +793,7 @@ __device__ __forceinline__ void staged_search(const double (&tau)[NK][2], int sp
             lds_count_search<TILE / 2, NK>::run(pa1, t1);
         }
 #pragma unroll
-        for (int k = 0; k < NK; ++k) { off[k][0] = (int)((pa0[k] - stage_a) >> 3); off[k][1] = (int)((pa1[k] - stage_a) >> 3); }
+        for (int k = 0; k < NK; ++k) { pos[k][0] = pa0[k]; pos[k][1] = pa1[k]; }
     } else {
         uint32_t pa[2 * NK];
         double tq[2 * NK];
@@ -758,8 +801,17 @@ __device__ __forceinline__ void staged_search(const double (&tau)[NK][2], int sp
         for (int k = 0; k < NK; ++k) { pa[2 * k] = pb[k][0]; pa[2 * k + 1] = pb[k][1]; tq[2 * k] = tloc[k][0]; tq[2 * k + 1] = tloc[k][1]; }
         lds_count_search<TILE / 2, 2 * NK>::run(pa, tq);
 #pragma unroll
-        for (int k = 0; k < NK; ++k) { off[k][0] = (int)((pa[2 * k] - stage_a) >> 3); off[k][1] = (int)((pa[2 * k + 1] - stage_a) >> 3); }
+        for (int k = 0; k < NK; ++k) { pos[k][0] = pa[2 * k]; pos[k][1] = pa[2 * k + 1]; }
     }
+}
+template <int TILE, int NK>
+__device__ __forceinline__ void staged_search(const double (&tau)[NK][2], int span, double Pm, double T0, double T1, double R0, double R1,
+                                              double R2, const double* lds_stage, int (&off)[NK][2]) {
+    uint32_t pos[NK][2];
+    staged_search_pos<TILE, NK>(tau, span, Pm, T0, T1, R0, R1, R2, lds_stage, pos);
+    const uint32_t stage_a = lds_addr(lds_stage);
+#pragma unroll
+    for (int k = 0; k < NK; ++k) { off[k][0] = (int)((pos[k][0] - stage_a) >> 3); off[k][1] = (int)((pos[k][1] - stage_a) >> 3); }
 }
 
 // ---------------------------------------------------------------------------------------
@@ -935,10 +987,11 @@ __device__ __forceinline__ void store_pair(double* p, double v0, double v1, int 
         __builtin_nontemporal_store(v, reinterpret_cast<f64x2_t*>(p));
     } else *reinterpret_cast<double2*>(p) = make_double2(v0, v1);
 }
-template <int MODEL, int NT, bool BIG = false, int TILE = kTile, int RS = -1, bool WL2 = false>
+template <int MODEL, int NT, bool BIG = false, int TILE = kTile, int RS = -1, bool WL2 = false, bool RESIDENT = false>
 __global__ __launch_bounds__(NT) void k_filter_step(const StepArgs a) {
     constexpr int NK = TILE / 2 / NT;
     constexpr bool HOT = RS >= 0;
+    static_assert(!RESIDENT || HOT, "the compiled-in schedule exists for the RS >= 0 kernels only");
     static_assert(NK >= 1 && NK * NT * 2 == TILE, "tile = 2 NT NK particles");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int nT2 = (BIG || a.Bpow2 < 2) ? 2 : a.Bpow2;      // BIG: level-2 comes from k_level2_plan, no tables in LDS
@@ -1226,24 +1279,37 @@ __global__ __launch_bounds__(NT) void k_filter_step(const StepArgs a) {
             else { R0 = lds_R3[0]; R1 = lds_R3[1]; R2 = lds_R3[2]; }
             STAMP(a, 5);
             PRIO_AT(5);
-            // all 2 NK count-searches of the thread descend together (staged_search)
-            int soff[NK][2];
+            // all 2 NK count-searches of the thread descend together (staged_search_pos): positions as absolute LDS byte addresses
+            uint32_t spos[NK][2];
             if (ABL(a, 2)) {
 #pragma unroll
-                for (int k = 0; k < NK; ++k) { soff[k][0] = (int)(d2bits(tau[k][0]) >> 20) & 2047; soff[k][1] = (int)(d2bits(tau[k][1]) >> 20) & 2047; }
-            } else staged_search<TILE, NK>(tau, span, Pm, T0, T1, R0, R1, R2, lds_stage, soff);
-            // gather: the ancestor's state at a 32-bit byte offset from a uniform base (no 64-bit address arithmetic per lane)
+                for (int k = 0; k < NK; ++k)
+                    for (int c = 0; c < 2; ++c) spos[k][c] = lds_addr(lds_stage) + (((uint32_t)(d2bits(tau[k][c]) >> 20) & 2047u) << 3);
+            } else staged_search_pos<TILE, NK>(tau, span, Pm, T0, T1, R0, R1, R2, lds_stage, spos);
+            // gather: the ancestor's state at a 32-bit byte offset from a uniform base (no 64-bit address arithmetic per lane).
+            // ancestor = bb_min TILE + (position - stage) / 8, so its byte offset is the position plus a uniform: one add.  A count
+            // is at most TILE - 1, so an ancestor can pass N - 1 only in the filter's last tile when that tile is ragged: the
+            // clamp to N - 1 sits behind that uniform condition (kept a branch, as the ragged output tile's).
             const unsigned char* xbase = reinterpret_cast<const unsigned char*>(xin_r - win0);
+            const uint32_t pos2byte = (uint32_t)bb_min * (uint32_t)(TILE * 8) - lds_addr(lds_stage);
+            const bool last_src_ragged = bb_min + span >= a.B && a.B * TILE > a.N;
+            uint32_t goff[NK][2];
+#pragma unroll
+            for (int k = 0; k < NK; ++k) { goff[k][0] = spos[k][0] + pos2byte; goff[k][1] = spos[k][1] + pos2byte; }
+            if (last_src_ragged) {
+                asm volatile("");
+                const uint32_t top = (uint32_t)(a.N - 1) << 3;
+#pragma unroll
+                for (int k = 0; k < NK; ++k) { goff[k][0] = goff[k][0] < top ? goff[k][0] : top; goff[k][1] = goff[k][1] < top ? goff[k][1] : top; }
+            }
 #pragma unroll
             for (int k = 0; k < NK; ++k) {
 #pragma unroll
                 for (int c = 0; c < 2; ++c) {
-                    int anc = bb_min * TILE + soff[k][c];
-                    anc = anc < a.N - 1 ? anc : a.N - 1;
                     const int i = i_first + (k * NT + tid) * 2 + c;
-                    if (anc_p && i < a.N) anc_p[rowoff + i - out0] = (uint32_t)anc;
-                    xin[k][c] = *reinterpret_cast<const double*>(xbase + ((uint32_t)anc << 3));
-                    if constexpr (DX > 1) srcv[k][c] = anc;
+                    if (anc_p && i < a.N) anc_p[rowoff + i - out0] = goff[k][c] >> 3;
+                    xin[k][c] = *reinterpret_cast<const double*>(xbase + goff[k][c]);
+                    if constexpr (DX > 1) srcv[k][c] = (int)(goff[k][c] >> 3);
                     lw_old[k][c] = 0.0;
                 }
             }
@@ -1342,7 +1408,7 @@ __global__ __launch_bounds__(NT) void k_filter_step(const StepArgs a) {
         for (int c = 0; c < 2; ++c) { const double l = lg[k][c]; nan = nan || (l != l); mx = (l > mx) ? l : mx; }
         const size_t idx = rowoff + (size_t)(i0 - out0);
         store_pair(reinterpret_cast<double*>(reinterpret_cast<unsigned char*>(a.x_out + rowoff + (size_t)(i_first - out0)) + (uint32_t)(k * NT + tid) * 16u),
-                   xo[0], xo[1], a.stream_stores);
+                   xo[0], xo[1], RESIDENT ? 1 : a.stream_stores);
         if (logw_p) *reinterpret_cast<double2*>(logw_p + idx) = make_double2(lg[k][0], lg[k][1]);
         if constexpr (DX > 1) {
 #pragma unroll
@@ -1376,7 +1442,7 @@ __global__ __launch_bounds__(NT) void k_filter_step(const StepArgs a) {
 #pragma unroll
     for (int k = 0; k < NK; ++k) {
         store_pair(reinterpret_cast<double*>(reinterpret_cast<unsigned char*>(a.cdf_out + rowoff + (size_t)(i_first - out0)) + (uint32_t)(k * NT + tid) * 16u),
-                   inc[k][0], inc[k][1], a.stream_stores);
+                   inc[k][0], inc[k][1], RESIDENT ? 1 : a.stream_stores);
     }
     STAMP(a, 10);
     PRIO_AT(10);
