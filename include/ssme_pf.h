@@ -245,7 +245,7 @@ int ssme_pf_get_series_user_expectations(ssme_pf_handle h, double* out /* [T][n_
  * n = 1 .. 4 built-in functionals (SSME_H_*; component 0 of a vector state), by the summation trees of the filtered expectations:
  * row T - 1 is ssme_pf_get_expectations_multi after the series, to the bit.  One backward launch and one finishing launch.
  * Both: a filter without weight (all weights zero, -inf or NaN, e.g. `bad` parameters) gets NaN states / NaN rows and the call
- * returns SSME_OK; two calls from one history return the same bits; SSME_F32 handles round x_out / out to float.
+ * returns SSME_OK; its index_out still holds the in-range lineage indices (< N) of the terminals it was given or drew; two calls from one history return the same bits; SSME_F32 handles round x_out / out to float.
  * Validated before any HIP call -- SSME_ERR_INVALID_ARG: NULL handle or x_out / out / functionals, K < 1 or K > N, a terminal index
  * >= N, n < 1 or n > 4, a functional id out of range, T different from the recorded series' length; SSME_ERR_STATE: a sharded
  * handle (as ssme_pf_run_series answers), or no history in force -- recording off during the last ssme_pf_run_series, no

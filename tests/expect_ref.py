@@ -87,17 +87,38 @@ def _rows(h_vals, n):
     return h
 
 
+def exact_dot(v, q):
+    """sum_j v_j q_j of finite doubles v and integers q as a Fraction, exactly: v_j = m_j 2^(e_j) with an integer m_j of at most 53
+    bits (frexp), the products m_j q_j and their sums per exponent are Python integers, and the exponents are applied once per
+    distinct value.  The same number as sum(Fraction(v_j) * q_j), two orders of magnitude sooner."""
+    v = np.asarray(v, dtype=np.float64)
+    if v.size == 0:
+        return Fraction(0)
+    if not np.isfinite(v).all():
+        raise ValueError("exact_dot: a value that is not finite")
+    m, e = np.frexp(v)
+    mi = np.ldexp(m, 53).astype(np.int64)                       # |m| < 1: an integer below 2^53, exactly
+    e = e.astype(np.int64) - 53
+    prod = mi.astype(object) * np.asarray(q).astype(np.int64).astype(object)
+    lo = int(e.min())
+    tot = 0
+    for ue in np.unique(e):
+        tot += int(prod[e == ue].sum()) << (int(ue) - lo)
+    return Fraction(tot) * Fraction(2) ** lo
+
+
 def _ratio_fraction(h, st):
     tix, q, s = st["tix"], st["q"], st["s"]
     sf = [Fraction(float(v)) for v in s]
     den = sum((int(a) * f for a, f in zip(st["A"], sf)), Fraction(0))
+    starts = np.flatnonzero(np.diff(tix, prepend=-1))              # tix is sorted: tile b is a contiguous run
+    assert (np.diff(tix) >= 0).all() and len(starts) == len(sf)
+    ends = np.append(starts[1:], len(tix))
     out = []
     for row in h:
         num = Fraction(0)
         for b in range(len(sf)):
-            sel = np.nonzero(tix == b)[0]
-            part = sum((Fraction(float(row[j])) * int(q[j]) for j in sel), Fraction(0))
-            num += part * sf[b]
+            num += exact_dot(row[starts[b]:ends[b]], q[starts[b]:ends[b]]) * sf[b]
         out.append(num / den)
     return out
 
