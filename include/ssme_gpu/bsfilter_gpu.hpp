@@ -715,6 +715,12 @@ inline std::vector<double> sampled_trajectories(ssme_pf_handle h, std::size_t K,
     check(ssme_pf_sample_trajectories(h, (std::int32_t)K, nullptr, out.data(), nullptr, (std::int32_t)T), h);
     return out;
 }
+// ... and K trajectories per filter by backward simulation over the same history (ssme_pf_sample_trajectories_backward): the same layout
+inline std::vector<double> backward_trajectories(ssme_pf_handle h, std::size_t K, std::size_t T, std::size_t R, std::size_t dimx) {
+    std::vector<double> out(R * K * T * dimx);
+    check(ssme_pf_sample_trajectories_backward(h, (std::int32_t)K, nullptr, out.data(), nullptr, (std::int32_t)T), h);
+    return out;
+}
 inline std::vector<double> smoothed_rows(ssme_pf_handle h, const std::vector<std::int32_t>& ids, std::size_t T, std::size_t R) {
     std::vector<double> out(T * (ids.empty() ? 1 : ids.size()) * R);
     check(ssme_pf_get_smoothed_expectations(h, ids.data(), (std::int32_t)ids.size(), out.data(), (std::int32_t)T), h);
@@ -762,6 +768,9 @@ public:
     // proportional to exp(logliks()[r]) and takes trajectory 0 of it -- and smoothed_expectations(ids)[(t * ids + i) * num_pfilters + r].
     void record_history(bool on = true) { check(ssme_pf_set_series_history(h_.get(), on ? 1 : 0), h_.get()); }
     std::vector<double> sample_trajectories(std::size_t K) const { return detail::sampled_trajectories(h_.get(), K, y_.size(), ll_.size(), 1); }
+    // sample_backward(K): the same K paths per replicate drawn by backward simulation (ssme_pf.h) -- they end at the same particles but
+    // do not share ancestors, at O(K N T) density evaluations
+    std::vector<double> sample_backward(std::size_t K) const { return detail::backward_trajectories(h_.get(), K, y_.size(), ll_.size(), 1); }
     std::vector<double> smoothed_expectations(const std::vector<std::int32_t>& ids) const { return detail::smoothed_rows(h_.get(), ids, y_.size(), ll_.size()); }
     const std::vector<double>& logliks() const { return ll_; }          // the replicates' log-likelihoods of the last evaluation
 
@@ -819,6 +828,9 @@ public:
     // smoothed_expectations(ids) of built-in functionals (component 0 of the state); the header's own functionals are not smoothed.
     void record_history(bool on = true) { check(ssme_pf_set_series_history(h_.get(), on ? 1 : 0), h_.get()); }
     std::vector<double> sample_trajectories(std::size_t K) const { return detail::sampled_trajectories(h_.get(), K, T_, ll_.size(), dimx); }
+    // sample_backward(K): by backward simulation, for a header that declares its transition density (logf / logf_vec; else the call
+    // throws SSME_ERR_UNSUPPORTED)
+    std::vector<double> sample_backward(std::size_t K) const { return detail::backward_trajectories(h_.get(), K, T_, ll_.size(), dimx); }
     std::vector<double> smoothed_expectations(const std::vector<std::int32_t>& ids) const { return detail::smoothed_rows(h_.get(), ids, T_, ll_.size()); }
 
 private:

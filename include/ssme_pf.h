@@ -252,14 +252,44 @@ int ssme_pf_get_series_user_expectations(ssme_pf_handle h, double* out /* [T][n_
  * ssme_pf_run_series yet, a ssme_pf_run_series that failed, or any later ssme_pf_step, ssme_pf_run_series, ssme_pf_profile_series, ssme_pf_reset, ssme_pf_set_params
  * or ssme_pf_set_seed on the handle (they change or discard the state the smoothing weights live in).  Forecasts, expectation
  * getters and downloads do not invalidate the history.
- * ssme_pf_smoothing_elapsed_ms: HIP-event times of the last of the two calls: its kernels alone, and the call without the download.
- * Out of scope: the functionals of a user header, fixed-lag smoothing, Liu-West handles and sharded handles. */
+ * ssme_pf_smoothing_elapsed_ms: HIP-event times of the last of the smoothing calls (ssme_pf_sample_trajectories_backward included): its
+ * kernels alone, and the call without the download.
+ * Out of scope: the functionals of a user header, fixed-lag smoothing, Liu-West handles and sharded handles; the trajectories above are
+ * the filter's genealogy and share ancestors -- backward simulation (below) draws them without that defect. */
 int ssme_pf_set_series_history(ssme_pf_handle h, int32_t enable);
 int ssme_pf_series_history_bytes(ssme_pf_handle h, int32_t T, uint64_t* bytes);
 int ssme_pf_sample_trajectories(ssme_pf_handle h, int32_t K, const uint32_t* terminal /*[R][K] or NULL: drawn as above*/,
                                 double* x_out /*[((r*K + k)*T + t)*dim_x + d]*/, uint32_t* index_out /*[(r*K + k)*T + t] or NULL*/, int32_t T);
 int ssme_pf_get_smoothed_expectations(ssme_pf_handle h, const int32_t* functionals, int32_t n, double* out /*[(t*n + i)*R + r]*/, int32_t T);
 int ssme_pf_smoothing_elapsed_ms(ssme_pf_handle h, float* kernel_ms, float* call_ms);
+/* Backward-simulation smoothing (forward filtering, backward simulation: Godsill, Doucet and West 2004; ssme_amd/csrc/backward.h,
+ * DESIGN.md section 12.1): trajectories from the same recorded history whose earlier states are drawn AGAIN from all N particles of
+ * their step, P(B_t = i | x~_{t+1}) prop. W_t[i] f(x~_{t+1} | x_t[i], z_{t+1}), so that they do not coalesce as the genealogy does.
+ * ssme_pf_sample_trajectories_backward: arguments, layouts and validation of ssme_pf_sample_trajectories.  B_{T-1} is given or
+ * drawn exactly as there (both calls return the same index_out[.., T - 1]: the join with a forecast's start draw is kept; T = 1 returns
+ * that call's output).  For t = T-2 .. 0, with x~ = x_{t+1}[B_{t+1}] and the covariates of step t + 1:
+ *   a_i = lw_t[i] + logf(x~ | x_t[i], z_{t+1}) (NaN counts as -inf), m = max a_i, q_i = rint(exp(a_i - m) 2^sh) by the filter's
+ *   quantiser at sh = min(41, 52 - ceil(log2 N)), S = sum q_i and the inclusive sums C_i exact integers below 2^53;
+ *   u = the 40-bit midpoint uniform of words 0-1 of Philox(k, t, filter id, stream 165), target = ceil(u S), B_t = the first i with
+ *   C_i >= target.  m not finite or S not > 0 (a degenerate transition): B_t = the genealogical ancestor (anc_{t+1}[B_{t+1}], or
+ *   B_{t+1} where step t + 1 did not resample).  No index leaves [0, N).
+ * lw_t are the pre-resampling log-weights the filter had at step t, recomputed from the history, the series and the covariates
+ * (which the handle keeps on the device) with the filter's own device functions: 8 T R Npad bytes (ssme_pf_backward_bytes; no HIP
+ * call), filled by the first backward call after a recording run, reused while that history is in force and freed with its rows.
+ * ssme_pf_download_series_logweights hands out row t of one filter (N values): bit-equal to ssme_pf_download_state's logw after step
+ * t of a handle stepped under ssme_pf_set_debug(2).  The cost is O(K N T) density evaluations, sequential in t; N up to the handle's limit.
+ * A filter without final weight gets NaN states and in-range indices (SSME_OK); SSME_F32 handles round x_out; two calls from one
+ * history return the same bits; a call changes nothing a later call returns.  SSME_ERR_STATE: sharded handles, no history in force
+ * (as above); SSME_ERR_UNSUPPORTED: SSME_MODEL_USER0 whose header declares no transition density (logf / logf_vec of
+ * ssme_amd/csrc/model_api.h; ssme_pf_user_model_has_logf, which needs no device: 0 for the stock library).  Built-in models:
+ * log f = -((xn - mean) / sd)^2 / 2 with the mean of the proposal in its own operation order.
+ * Out of scope: Liu-West and sharded handles, rejection-sampling / MCMC backward steps, marginal O(N^2) smoothing weights and
+ * backward-simulated expectations of a user header's functionals. */
+int ssme_pf_user_model_has_logf(void);
+int ssme_pf_backward_bytes(ssme_pf_handle h, int32_t T, uint64_t* bytes);
+int ssme_pf_download_series_logweights(ssme_pf_handle h, int32_t filter, int32_t t, double* lw /*N*/);
+int ssme_pf_sample_trajectories_backward(ssme_pf_handle h, int32_t K, const uint32_t* terminal /*[R][K] or NULL*/,
+                                         double* x_out /*[((r*K + k)*T + t)*dim_x + d]*/, uint32_t* index_out /*[(r*K + k)*T + t] or NULL*/, int32_t T);
 /* Arbitrary host-side h (the reference's filt_func is a std::function, pswarm_filter.h:44,87-89): particles x (N,
  * nullable) and weights w (N) of one filter after the last step, w_j = exp(logw_j - max logw) in the 2^-41 fixed point
  * the resampler and ssme_pf_get_expectations use; the caller forms sum h(x_j) w_j / sum w_j.  Needs no debug mode. */

@@ -68,6 +68,16 @@
 // A header without the draw compiles and behaves as before (ssme_pf_user_model_has_gsamp reads 0, a forecast is
 // SSME_ERR_UNSUPPORTED).  tests/models/svol_leverage_user.h, svol_two_factor_g.h, lin_gauss_3d_g.h, lin_gauss_4d_g.h declare it.
 //
+// TRANSITION DENSITY (optional; what backward-simulation smoothing needs: ssme_pf_sample_trajectories_backward, backward.h, DESIGN.md
+// section 12.1).  A header that declares it can be smoothed by backward simulation:
+//     static __device__ double logf(const ssme::ModelConst& c, double xn, double x, double zcov, const ssme::ExpTabEntry* etab);   // scalar model
+//     static __device__ double logf_vec(const ssme::ModelConst& c, const double* xn /*dim_x*/, const double* x /*dim_x*/, double zcov,
+//                                       const ssme::ExpTabEntry* etab);                                                         // vector model
+// log f(xn | x, zcov), the density of the header's own prop / prop_vec, up to a constant that does not depend on x (it cancels in the
+// backward weights); zcov is the covariate of the step that made xn and is `const double*` in a dim_cov header, as in every callback.
+// The rules of the other callbacks hold.  A header without it compiles and behaves as before (ssme_pf_user_model_has_logf reads 0, the
+// backward call is SSME_ERR_UNSUPPORTED).  tests/models/svol_student_t_f.h, svol_two_factor_f.h and svol_reg_cov_f.h declare it.
+//
 // COVARIATES (optional; pf::filters::BSFilterWC<nparts, dimx, dimy, dimcov, ...> of the reference, pswarm_filter.h:309-352: z_t enters
 // fSamp, logGEv, q1Samp, logMuEv, logQ1Ev and the functionals).  A header that declares
 //     static constexpr int dim_cov = K;                            // 1 .. 4 covariates per step
@@ -153,6 +163,19 @@ template <class M> struct user_gsamp {
                   "a scalar user model declares its observation draw as gsamp, not gsamp_vec");
     static constexpr bool has = vec ? declares_gsamp_vec<M>::value : declares_gsamp<M>::value;
 };
+// does the header declare the transition log-density, in the form its dimensions ask for (logf / logf_vec above)?
+template <class M, class = void> struct declares_logf : std::false_type {};
+template <class M> struct declares_logf<M, std::void_t<decltype(&M::logf)>> : std::true_type {};
+template <class M, class = void> struct declares_logf_vec : std::false_type {};
+template <class M> struct declares_logf_vec<M, std::void_t<decltype(&M::logf_vec)>> : std::true_type {};
+template <class M> struct user_logf {
+    static constexpr bool vec = user_dims<M>::dx > 1 || user_dims<M>::dy > 1;
+    static_assert(!(vec && declares_logf<M>::value && !declares_logf_vec<M>::value),
+                  "a vector user model (dim_x or dim_y > 1) declares its transition density as logf_vec, not logf");
+    static_assert(!(!vec && declares_logf_vec<M>::value && !declares_logf<M>::value),
+                  "a scalar user model declares its transition density as logf, not logf_vec");
+    static constexpr bool has = vec ? declares_logf_vec<M>::value : declares_logf<M>::value;
+};
 // COVARIATES (dim_cov above): how many a user model declares, 0 for a header without them
 constexpr int kMaxCov = 4;
 template <class M, class = void> struct user_cov { static constexpr int k = 0; };
@@ -183,6 +206,8 @@ template <class M> struct user_calls<M, false, false> {
     static __device__ __forceinline__ void prop_vec(const ModelConst& c, const double* x, const double* zn, double zcov, double* xn, const ExpTabEntry* etab) { xn[0] = M::prop(c, x[0], zn[0], zcov, etab); }
     static __device__ __forceinline__ double logg_vec(const ModelConst& c, const double* y, const double* x, const ExpTabEntry* etab) { return M::logg(c, y[0], x[0], etab); }
     static __device__ __forceinline__ void gsamp_vec(const ModelConst& c, const double* x, const double* zo, double* y, const ExpTabEntry* etab) { y[0] = M::gsamp(c, x[0], zo[0], etab); }
+    static __device__ __forceinline__ double logf(const ModelConst& c, double xn, double x, double zcov, const ExpTabEntry* etab) { return M::logf(c, xn, x, zcov, etab); }
+    static __device__ __forceinline__ double logf_vec(const ModelConst& c, const double* xn, const double* x, double zcov, const ExpTabEntry* etab) { return M::logf(c, xn[0], x[0], zcov, etab); }
 };
 template <class M> struct user_calls<M, true, false> {
     static __device__ __forceinline__ double prop(const ModelConst&, double, double, double, const ExpTabEntry*) { return 0.0; }
@@ -191,6 +216,8 @@ template <class M> struct user_calls<M, true, false> {
     static __device__ __forceinline__ void prop_vec(const ModelConst& c, const double* x, const double* zn, double zcov, double* xn, const ExpTabEntry* etab) { M::prop_vec(c, x, zn, zcov, xn, etab); }
     static __device__ __forceinline__ double logg_vec(const ModelConst& c, const double* y, const double* x, const ExpTabEntry* etab) { return M::logg_vec(c, y, x, etab); }
     static __device__ __forceinline__ void gsamp_vec(const ModelConst& c, const double* x, const double* zo, double* y, const ExpTabEntry* etab) { M::gsamp_vec(c, x, zo, y, etab); }
+    static __device__ __forceinline__ double logf(const ModelConst&, double, double, double, const ExpTabEntry*) { return 0.0; }
+    static __device__ __forceinline__ double logf_vec(const ModelConst& c, const double* xn, const double* x, double zcov, const ExpTabEntry* etab) { return M::logf_vec(c, xn, x, zcov, etab); }
 };
 // dim_cov headers: the kernels reach them through the vector forms alone (cov_step / cov_sim below); the scalar-covariate
 // entry points of the other grammar are stubs that no launch of such a model reaches
@@ -201,6 +228,8 @@ template <class M> struct user_calls<M, false, true> {
     static __device__ __forceinline__ void prop_vec(const ModelConst& c, const double* x, const double* zn, const double* zcov, double* xn, const ExpTabEntry* etab) { xn[0] = M::prop(c, x[0], zn[0], zcov, etab); }
     static __device__ __forceinline__ double logg_vec(const ModelConst& c, const double* y, const double* x, const double* zcov, const ExpTabEntry* etab) { return M::logg(c, y[0], x[0], zcov, etab); }
     static __device__ __forceinline__ void gsamp_vec(const ModelConst& c, const double* x, const double* zo, const double* zcov, double* y, const ExpTabEntry* etab) { y[0] = M::gsamp(c, x[0], zo[0], zcov, etab); }
+    static __device__ __forceinline__ double logf(const ModelConst&, double, double, double, const ExpTabEntry*) { return 0.0; }
+    static __device__ __forceinline__ double logf_vec(const ModelConst& c, const double* xn, const double* x, const double* zcov, const ExpTabEntry* etab) { return M::logf(c, xn[0], x[0], zcov, etab); }
 };
 template <class M> struct user_calls<M, true, true> {
     static __device__ __forceinline__ double prop(const ModelConst&, double, double, double, const ExpTabEntry*) { return 0.0; }
@@ -209,6 +238,8 @@ template <class M> struct user_calls<M, true, true> {
     static __device__ __forceinline__ void prop_vec(const ModelConst& c, const double* x, const double* zn, const double* zcov, double* xn, const ExpTabEntry* etab) { M::prop_vec(c, x, zn, zcov, xn, etab); }
     static __device__ __forceinline__ double logg_vec(const ModelConst& c, const double* y, const double* x, const double* zcov, const ExpTabEntry* etab) { return M::logg_vec(c, y, x, zcov, etab); }
     static __device__ __forceinline__ void gsamp_vec(const ModelConst& c, const double* x, const double* zo, const double* zcov, double* y, const ExpTabEntry* etab) { M::gsamp_vec(c, x, zo, zcov, y, etab); }
+    static __device__ __forceinline__ double logf(const ModelConst&, double, double, double, const ExpTabEntry*) { return 0.0; }
+    static __device__ __forceinline__ double logf_vec(const ModelConst& c, const double* xn, const double* x, const double* zcov, const ExpTabEntry* etab) { return M::logf_vec(c, xn, x, zcov, etab); }
 };
 // One filter step of one particle of a dim_cov model: xn <- first (t = 0, when declared; init_vec / a2 * zn otherwise) or prop,
 // and the increment of its log-weight: [first_logw +] logg, -inf for a `bad` filter.  x, zn, xn: dim_x values; y: dim_y; zcov: dim_cov.
@@ -229,6 +260,19 @@ __device__ __forceinline__ double cov_step(const ModelConst& c, bool first_step,
         UC::prop_vec(c, x, zn, zcov, xn, etab);
         g = UC::logg_vec(c, y, xn, zcov, etab);
     }
+    return c.bad ? -dinf() : g;
+}
+// The weight part of cov_step alone, for a particle xn that exists already (backward.h recomputes the log-weights of a recorded
+// series from its populations): [first_logw +] logg in cov_step's own order, -inf for a `bad` filter.
+template <class M>
+__device__ __forceinline__ double cov_logw(const ModelConst& c, bool first_step, const double* y, const double* zcov, const double* xn,
+                                           const ExpTabEntry* etab) {
+    using UC = user_calls<M>;
+    double g;
+    if (first_step) {
+        if constexpr (user_first<M>::has) g = M::first_logw(c, y, xn, zcov, etab) + UC::logg_vec(c, y, xn, zcov, etab);
+        else g = UC::logg_vec(c, y, xn, zcov, etab);
+    } else g = UC::logg_vec(c, y, xn, zcov, etab);
     return c.bad ? -dinf() : g;
 }
 #if SSME_HAS_USER_MODEL

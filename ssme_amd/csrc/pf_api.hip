@@ -9,6 +9,7 @@
 #include "user_expect.h"
 #include "forecast.h"
 #include "smooth.h"
+#include "backward.h"
 #include "series_history.h"
 #include "handle_core.h"
 #include "shard_driver.h"
@@ -95,6 +96,9 @@ struct ssme_pf_s : HandleCore {
     double *sm_part, *sm_out;    // [T][R][Bs][4] per-tile numerators of the sweep, [T][4][R] its rows
     hipEvent_t sm_ev[3];         // call start, backward kernel start, kernels' end
     float sm_ms_kernel, sm_ms_call;
+    // backward simulation (backward.h): the pre-resampling log-weights of every step of the history, recomputed on first use
+    double* bs_lw;               // [hist.lw_cap][R][Npad]; freed with the history rows
+    int hist_has_z;              // the recorded series had covariates (zbuf holds them; 0: the kernels read zeros)
     std::vector<ModelConst> h_mc;
     // forecast (HandleCore::fc): fc.x0 is [dx][R][Npad], the samples fc.y / fc.x [R][H][dy][Ns] / [R][H][dx][Ns]
     std::vector<double> h_gscale;    // per filter: scale of the observation draw (set_params)
@@ -597,9 +601,11 @@ static int user_expectations_checked(ssme_pf_handle h) {
 #if SSME_HAS_USER_MODEL
 constexpr bool kUserHasGsamp = user_gsamp<ssme_user_model0>::has;
 constexpr int kUserNH = user_nh<ssme_user_model0>::n;      // functionals the compiled-in header declares
+constexpr bool kUserHasLogf = user_logf<ssme_user_model0>::has;     // ... and its transition density (logf / logf_vec)
 #else
 constexpr bool kUserHasGsamp = false;
 constexpr int kUserNH = 0;
+constexpr bool kUserHasLogf = false;
 #endif
 
 // Recorded series: the trajectory buffers for T time rows of the current recording configuration, and the per-tile numerators of the
@@ -630,13 +636,14 @@ static int ensure_trajectory(ssme_pf_handle h, int T) {
 static int ensure_history(ssme_pf_handle h, int T) {
     if (!h->hist.on) {
         if (h->hist_x || h->hist_anc) { drop_graph(h); own_free(h, h->hist_x); own_free(h, h->hist_anc); }
+        own_free(h, h->bs_lw);
         h->hist.rows_dropped();
         return SSME_OK;
     }
     if (T <= h->hist.cap) return SSME_OK;
     // the rows are replaced: whatever history they held is no longer in force, whether or not the new allocation succeeds
     drop_graph(h);
-    own_free(h, h->hist_x); own_free(h, h->hist_anc);
+    own_free(h, h->hist_x); own_free(h, h->hist_anc); own_free(h, h->bs_lw);
     h->hist.rows_dropped();
     const size_t np = (size_t)h->R * h->Npad;
     hipError_t e = own_alloc(h, h->hist_x, sizeof(double) * (size_t)T * h->dx * np);
@@ -812,6 +819,7 @@ int ssme_pf_user_model_n_h(void) {
 #endif
 }
 int ssme_pf_user_model_has_gsamp(void) { return kUserHasGsamp ? 1 : 0; }
+int ssme_pf_user_model_has_logf(void) { return kUserHasLogf ? 1 : 0; }
 int ssme_pf_user_model_dim_cov(void) { return kcov_of(SSME_MODEL_USER0); }
 int ssme_pf_user_model_has_first(void) {
 #if SSME_HAS_USER_MODEL
@@ -1296,6 +1304,7 @@ int ssme_pf_run_series(ssme_pf_handle h, const double* y, const double* z, int32
     HIPCHK(hipMemcpyAsync(h->ybuf, y, sizeof(double) * T * h->dy, hipMemcpyHostToDevice, h->stream));
     if (z) HIPCHK(hipMemcpyAsync(h->zbuf, z, sizeof(double) * T * h->kz, hipMemcpyHostToDevice, h->stream));
     set_last_z(h, z, T);
+    h->hist_has_z = z != nullptr;
     if (h->cfg.dtype == SSME_F32) HIPCHK(hipStreamSynchronize(h->stream));      // the staging vectors go out of scope
     rc = do_reset(h);
     if (rc != SSME_OK) return rc;
@@ -1519,6 +1528,102 @@ int ssme_pf_get_smoothed_expectations(ssme_pf_handle h, const int32_t* functiona
     rc = smoothing_end(h);
     if (rc != SSME_OK) return rc;
     round_out(h, out, nout);
+    return SSME_OK;
+}
+
+// ---- backward simulation (kernels: backward.h) ----
+int ssme_pf_backward_bytes(ssme_pf_handle h, int32_t T, uint64_t* bytes) {
+    if (!h || !bytes || T < 1) return SSME_ERR_INVALID_ARG;
+    if (h->shard_world > 0) return SSME_ERR_STATE;
+    *bytes = (uint64_t)8 * (uint64_t)T * (uint64_t)h->R * (uint64_t)h->Npad;
+    return SSME_OK;
+}
+
+extern "C++" {
+template <int MODEL>
+static void launch_bsim_logw(ssme_pf_handle h, const BsimArgs& a) {
+    if constexpr (MODEL != MODEL_USER0 || kUserHasLogf)
+        hipLaunchKernelGGL((k_bsim_logw<MODEL>), dim3(h->Npad / kThreads, h->R), dim3(kThreads), 0, h->stream, a);
+}
+template <int MODEL>
+static void launch_bsim(ssme_pf_handle h, const BsimArgs& a, int K, const uint32_t* term, uint32_t* idx) {
+    if constexpr (MODEL != MODEL_USER0 || kUserHasLogf) {
+        const dim3 grid((K + kBsimG - 1) / kBsimG, h->R);
+        if (h->N <= 2 * kThreads) hipLaunchKernelGGL((k_bsim<MODEL, 2>), grid, dim3(kThreads), 0, h->stream, a, K, term, h->sm_x, idx);
+        else hipLaunchKernelGGL((k_bsim<MODEL, 8>), grid, dim3(kThreads), 0, h->stream, a, K, term, h->sm_x, idx);
+    }
+}
+}  // extern "C++"
+
+// The log-weight rows of the history in force (T steps), filled on the first call after the recording run and reused while that
+// history stays in force (series_history.h).  `a`: what both backward kernels read of the handle, a->s of the caller left alone.
+static int backward_weights(ssme_pf_handle h, int T, BsimArgs* a) {
+    if (h->hist.weights_query(h->bs_lw != nullptr) == SeriesHistoryState::allocate) {
+        h->hist.weights_dropped();
+        const hipError_t e = own_alloc(h, h->bs_lw, sizeof(double) * (size_t)T * h->R * h->Npad);
+        if (e != hipSuccess) { (void)hipGetLastError(); return fail(h, "backward-simulation weights (ssme_pf_backward_bytes)", e); }
+        h->hist.weights_ready(T);
+    }
+    a->y = h->ybuf; a->z = h->hist_has_z ? h->zbuf : nullptr; a->mc = h->mc; a->lw = h->bs_lw;
+    int lg = 0;
+    while ((1L << lg) < (long)h->N) ++lg;                        // ceil(log2 N)
+    a->shift = 52 - lg < kTileShift ? 52 - lg : kTileShift;
+    if (h->hist.weights_query(true) == SeriesHistoryState::fill) {
+        BsimArgs w = *a;
+        w.s = SmArgs{};
+        w.s.hx = h->hist_x; w.s.N = h->N; w.s.Npad = h->Npad; w.s.R = h->R; w.s.T = T; w.s.resamp_sched = h->cfg.resamp_sched; w.s.dx = h->dx;
+        with_model(h->cfg.model, [&](auto m) { launch_bsim_logw<decltype(m)::value>(h, w); });
+        HIPCHK(hipGetLastError());
+        h->hist.weights_filled();
+    }
+    return SSME_OK;
+}
+
+int ssme_pf_download_series_logweights(ssme_pf_handle h, int32_t filter, int32_t t, double* lw) {
+    if (!h || !lw || filter < 0 || filter >= h->R || t < 0) return SSME_ERR_INVALID_ARG;
+    if (h->shard_world > 0) return SSME_ERR_STATE;
+    if (h->cfg.model == SSME_MODEL_USER0 && !kUserHasLogf) return SSME_ERR_UNSUPPORTED;
+    if (h->hist.query(h->hist_x && h->hist_anc, h->hist.T) != SeriesHistoryState::in_force) {
+        h->err = "no series history in force: ssme_pf_set_series_history, then ssme_pf_run_series";
+        return SSME_ERR_STATE;
+    }
+    if (t >= h->hist.T) return SSME_ERR_INVALID_ARG;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    BsimArgs a{};
+    const int rc = backward_weights(h, h->hist.T, &a);
+    if (rc != SSME_OK) return rc;
+    HIPCHK(hipMemcpyAsync(lw, h->bs_lw + ((size_t)t * h->R + filter) * h->Npad, sizeof(double) * h->N, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    round_out(h, lw, h->N);
+    return SSME_OK;
+}
+
+int ssme_pf_sample_trajectories_backward(ssme_pf_handle h, int32_t K, const uint32_t* terminal, double* x_out, uint32_t* index_out, int32_t T) {
+    if (!h || !x_out || K < 1 || K > h->N || T < 1) return SSME_ERR_INVALID_ARG;
+    if (terminal)
+        for (size_t i = 0; i < (size_t)h->R * K; ++i)
+            if (terminal[i] >= (uint32_t)h->N) return SSME_ERR_INVALID_ARG;
+    if (h->cfg.model == SSME_MODEL_USER0 && !kUserHasLogf && h->shard_world == 0) return SSME_ERR_UNSUPPORTED;
+    BsimArgs a{};
+    int rc = smoothing_begin(h, T, &a.s);
+    if (rc == SSME_OK) rc = backward_weights(h, T, &a);
+    if (rc != SSME_OK) return rc;
+    const size_t nk = (size_t)h->R * K, ni = nk * T, nx = ni * h->dx;
+    rc = sm_grow(h, h->sm_x, h->sm_cap_x, nx);
+    if (rc == SSME_OK && index_out) rc = sm_grow(h, h->sm_idx, h->sm_cap_idx, ni);
+    if (rc == SSME_OK && terminal) rc = sm_grow(h, h->sm_term, h->sm_cap_term, nk);
+    if (rc != SSME_OK) return rc;
+    if (terminal) HIPCHK(hipMemcpyAsync(h->sm_term, terminal, sizeof(uint32_t) * nk, hipMemcpyHostToDevice, h->stream));
+    const uint32_t* term = terminal ? h->sm_term : nullptr;
+    uint32_t* idx = index_out ? h->sm_idx : nullptr;
+    with_model(h->cfg.model, [&](auto m) { launch_bsim<decltype(m)::value>(h, a, K, term, idx); });
+    HIPCHK(hipEventRecord(h->sm_ev[2], h->stream));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(x_out, h->sm_x, sizeof(double) * nx, hipMemcpyDeviceToHost, h->stream));
+    if (index_out) HIPCHK(hipMemcpyAsync(index_out, h->sm_idx, sizeof(uint32_t) * ni, hipMemcpyDeviceToHost, h->stream));
+    rc = smoothing_end(h);
+    if (rc != SSME_OK) return rc;
+    round_out(h, x_out, nx);
     return SSME_OK;
 }
 

@@ -307,6 +307,26 @@ __device__ __forceinline__ double model_prop(const ModelConst& c, double x, doub
     return c.a0 * x + zn * c.a1;          // univ_svol_bootstrap_filter.h:74-79
 }
 
+// log f(xn | x, zcov) up to a constant that does not depend on x: the density of model_prop's draw, with the mean formed in
+// model_prop's own operation order (backward simulation, backward.h; a user model: its logf, model_api.h).
+template <int MODEL>
+__device__ __forceinline__ double model_logf(const ModelConst& c, double xn, double x, double zcov, const ExpTabEntry* etab) {
+#if SSME_HAS_USER_MODEL
+    if constexpr (MODEL == MODEL_USER0) return user_calls<ssme_user_model0>::logf(c, xn, x, zcov, etab);      // model_api.h
+#endif
+    double mean, sd;
+    if (MODEL == MODEL_SVOL_LEVERAGE) {
+        const double e = dexp_scaled_t(-0.5 * x, 0, etab);
+        mean = (c.a1 + c.a0 * (x - c.a1)) + (c.a4 * zcov) * e;
+        sd = c.a3;
+    } else {
+        mean = c.a0 * x;
+        sd = c.a1;
+    }
+    const double d = (xn - mean) / sd;
+    return -0.5 * (d * d);
+}
+
 template <int MODEL>
 __device__ __forceinline__ double model_logg(const ModelConst& c, double y, double x, const ExpTabEntry* etab) {
 #if SSME_HAS_USER_MODEL

@@ -16,7 +16,7 @@ from . import _capi as capi
 from ._capi import (MODEL_LIN_GAUSS, MODEL_SVOL, MODEL_SVOL_LEVERAGE, MODEL_USER0, RESAMP_MULTINOMIAL, RESAMP_MULTINOMIAL_IID,
                     RESAMP_STRATIFIED, RESAMP_SYSTEMATIC, SsmeError)
 
-__all__ = ["default_tile", "user_model_has_gsamp", "user_model_dim_cov", "ParticleFilterBank", "svol_bs", "svol_leverage", "lin_gauss_bs", "log_like_eval", "svol_lw_1_par", "svol_lw_2_par", "SwarmWithCovs", "Swarm", "svol_swarm_1",
+__all__ = ["default_tile", "user_model_has_gsamp", "user_model_has_logf", "user_model_dim_cov", "ParticleFilterBank", "svol_bs", "svol_leverage", "lin_gauss_bs", "log_like_eval", "svol_lw_1_par", "svol_lw_2_par", "SwarmWithCovs", "Swarm", "svol_swarm_1",
            "TR_NULL", "TR_TWICE_FISHER", "TR_LOGIT", "TR_LOG",
            "MODEL_SVOL", "MODEL_SVOL_LEVERAGE", "MODEL_LIN_GAUSS", "MODEL_USER0", "RESAMP_MULTINOMIAL", "RESAMP_SYSTEMATIC",
            "RESAMP_STRATIFIED", "RESAMP_MULTINOMIAL_IID", "SsmeError"]
@@ -31,6 +31,13 @@ def user_model_has_gsamp():
     """Does the loaded library's user model declare its observation draw (csrc/model_api.h: gsamp / gsamp_vec), so that
     MODEL_USER0 filters can be forecast (sim_future_obs)?  False for the stock library.  Needs no device."""
     return bool(capi.lib().ssme_pf_user_model_has_gsamp())
+
+
+def user_model_has_logf():
+    """Does the loaded library's user model declare its transition log-density (csrc/model_api.h: logf / logf_vec), so that
+    MODEL_USER0 filters can be smoothed by backward simulation (sample_trajectories_backward)?  False for the stock library.
+    Needs no device."""
+    return bool(capi.lib().ssme_pf_user_model_has_logf())
 
 
 def user_model_dim_cov():
@@ -287,6 +294,50 @@ class ParticleFilterBank:
         out = np.empty((self._last_T, max(fs.size, 1), self.r))
         self._chk(capi.lib().ssme_pf_get_smoothed_expectations(self._h, fs.ctypes.data_as(C.POINTER(C.c_int32)), fs.size, capi.dptr(out),
                                                                self._last_T))
+        return out
+
+    user_model_has_logf = staticmethod(user_model_has_logf)
+
+    def backward_bytes(self, T):
+        """Device bytes of the log-weight rows backward simulation keeps for a T-step history: 8 T R Npad (no device call)."""
+        b = C.c_uint64()
+        self._chk(capi.lib().ssme_pf_backward_bytes(self._h, int(T), C.byref(b)))
+        return int(b.value)
+
+    def series_logweights(self, f, t):
+        """The N pre-resampling log-weights filter f had at step t of the last recorded run_series, recomputed from the history
+        (ssme_pf_download_series_logweights): what state(f)["logw"] holds after step t of a handle stepped with keep_logw, to the bit."""
+        out = np.empty(self.n)
+        self._chk(capi.lib().ssme_pf_download_series_logweights(self._h, int(f), int(t), capi.dptr(out)))
+        return out
+
+    def sample_trajectories_backward(self, K, terminal=None, return_indices=False):
+        """K state trajectories per filter from p(x_{0:T-1} | y_{0:T-1}) by BACKWARD SIMULATION over the history of the last run_series
+        (recorded with record_series_history): x[R, K, T, dim_x].  The terminal particle is given or drawn as in sample_trajectories
+        (the same index); every earlier state is drawn again from all N particles of its step, reweighted by the transition density to
+        the state already chosen, so the K paths do not share ancestors as the genealogy's do.  O(K N T).
+        return_indices=True: (x, index[R, K, T])."""
+        K, T, dx = int(K), self._last_T, self._dims()[0]
+        term = None
+        if terminal is not None:
+            term = np.ascontiguousarray(terminal, dtype=np.uint32)
+            assert term.size == self.r * K, "terminal: [R, K]"
+        x = np.empty((self.r, K, T, dx))
+        idx = np.empty((self.r, K, T), dtype=np.uint32) if return_indices else None
+        self._chk(capi.lib().ssme_pf_sample_trajectories_backward(self._h, K, capi.u32ptr(term), capi.dptr(x), capi.u32ptr(idx), T))
+        return (x, idx) if return_indices else x
+
+    def backward_smoothed_means(self, K, functionals):
+        """Smoothed means of built-in functionals (H_X, H_X2, H_VOL, H_CONST42; component 0 of a vector state) from K
+        backward-simulated paths per filter: [T, n, R].  The plain mean of K equally weighted draws, formed on the host -- its
+        Monte-Carlo error is that of K draws (standard deviation of h / sqrt(K)) on top of the filter's own."""
+        x = self.sample_trajectories_backward(K)[..., 0]                    # [R, K, T]
+        hs = {capi.H_X: lambda v: v, capi.H_X2: lambda v: v * v, capi.H_VOL: lambda v: np.exp(0.5 * v),
+              capi.H_CONST42: lambda v: np.full_like(v, 42.0)}
+        fs = [int(f) for f in np.ravel(functionals)]
+        out = np.empty((x.shape[2], max(len(fs), 1), self.r))
+        for i, f in enumerate(fs):
+            out[:, i, :] = hs[f](x).mean(axis=1).T
         return out
 
     def smoothing_elapsed_ms(self):
