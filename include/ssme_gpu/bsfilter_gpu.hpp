@@ -726,6 +726,17 @@ inline std::vector<double> smoothed_rows(ssme_pf_handle h, const std::vector<std
     check(ssme_pf_get_smoothed_expectations(h, ids.data(), (std::int32_t)ids.size(), out.data(), (std::int32_t)T), h);
     return out;
 }
+// Marginal smoothing (ssme_pf.h): om_t of replicate r, N weights (not normalised), and the smoothed means under them, [(t * ids + i) * R + r]
+inline std::vector<double> smoothing_weight_row(ssme_pf_handle h, std::size_t N, std::size_t r, std::size_t t) {
+    std::vector<double> w(N);
+    check(ssme_pf_download_smoothing_weights(h, (std::int32_t)r, (std::int32_t)t, nullptr, w.data()), h);
+    return w;
+}
+inline std::vector<double> marginal_rows(ssme_pf_handle h, const std::vector<std::int32_t>& ids, std::size_t T, std::size_t R) {
+    std::vector<double> out(T * (ids.empty() ? 1 : ids.size()) * R);
+    check(ssme_pf_get_marginal_smoothed_expectations(h, ids.data(), (std::int32_t)ids.size(), out.data(), (std::int32_t)T), h);
+    return out;
+}
 }  // namespace detail
 
 // ---- persistent evaluator: one handle, one captured graph, a fresh random stream per call --------------------------
@@ -736,7 +747,8 @@ class svol_log_like_evaluator {
 public:
     template <typename Data>
     svol_log_like_evaluator(const Data& data, int nparts, int num_pfilters, gpu_options o = gpu_options())
-        : h_(SSME_MODEL_SVOL, nparts, num_pfilters, o.seed, o.resampler, o.resamp_sched, o.device, 0), ll_((std::size_t)num_pfilters) {
+        : h_(SSME_MODEL_SVOL, nparts, num_pfilters, o.seed, o.resampler, o.resamp_sched, o.device, 0), ll_((std::size_t)num_pfilters),
+          nparts_((std::size_t)(nparts > 0 ? nparts : 0)) {
         if (data.empty()) throw std::length_error("can't read in data\n");
         y_ = detail::column0(data);
     }
@@ -772,11 +784,17 @@ public:
     // do not share ancestors, at O(K N T) density evaluations
     std::vector<double> sample_backward(std::size_t K) const { return detail::backward_trajectories(h_.get(), K, y_.size(), ll_.size(), 1); }
     std::vector<double> smoothed_expectations(const std::vector<std::int32_t>& ids) const { return detail::smoothed_rows(h_.get(), ids, y_.size(), ll_.size()); }
+    // Marginal smoothing (ssme_pf.h): smoothing_weights(r, t), the N weights om_t of replicate r -- the exact law of the backward draw
+    // B_t, not normalised -- and marginal_smoothed_expectations(ids)[(t * ids + i) * num_pfilters + r], the smoothed means under them:
+    // no draw noise, no shared ancestors, at 3 N^2 (T - 1) density evaluations on the first call after operator()
+    std::vector<double> smoothing_weights(std::size_t r, std::size_t t) const { return detail::smoothing_weight_row(h_.get(), nparts_, r, t); }
+    std::vector<double> marginal_smoothed_expectations(const std::vector<std::int32_t>& ids) const { return detail::marginal_rows(h_.get(), ids, y_.size(), ll_.size()); }
     const std::vector<double>& logliks() const { return ll_; }          // the replicates' log-likelihoods of the last evaluation
 
 private:
     handle h_;
     std::vector<double> y_, ll_;
+    std::size_t nparts_ = 0;
     std::size_t n_rec_ = 0, n_run_ = 0;                    // built-in functionals set for the next evaluation / recorded by the last one
 };
 
@@ -790,7 +808,7 @@ class user_log_like_evaluator {
 public:
     user_log_like_evaluator(const std::vector<double>& y, const std::vector<double>& z, int nparts, int num_pfilters,
                             gpu_options o = gpu_options())
-        : y_(y), z_(z), ll_((std::size_t)(num_pfilters > 0 ? num_pfilters : 0)) {
+        : y_(y), z_(z), ll_((std::size_t)(num_pfilters > 0 ? num_pfilters : 0)), nparts_((std::size_t)(nparts > 0 ? nparts : 0)) {
         std::int32_t dx = 0, dy = 0;
         check(ssme_pf_user_model_dims(&dx, &dy));                      // SSME_ERR_UNSUPPORTED: the stock library was linked
         if (dx != (std::int32_t)dimx || dy != (std::int32_t)dimy) throw std::invalid_argument("user_log_like_evaluator: dimx / dimy are not the compiled-in model's");
@@ -832,6 +850,10 @@ public:
     // throws SSME_ERR_UNSUPPORTED)
     std::vector<double> sample_backward(std::size_t K) const { return detail::backward_trajectories(h_.get(), K, T_, ll_.size(), dimx); }
     std::vector<double> smoothed_expectations(const std::vector<std::int32_t>& ids) const { return detail::smoothed_rows(h_.get(), ids, T_, ll_.size()); }
+    // smoothing_weights(r, t) / marginal_smoothed_expectations(ids): marginal smoothing as svol_log_like_evaluator offers it, for a
+    // header that declares its transition density (else SSME_ERR_UNSUPPORTED is thrown); the functionals see component 0 of the state
+    std::vector<double> smoothing_weights(std::size_t r, std::size_t t) const { return detail::smoothing_weight_row(h_.get(), nparts_, r, t); }
+    std::vector<double> marginal_smoothed_expectations(const std::vector<std::int32_t>& ids) const { return detail::marginal_rows(h_.get(), ids, T_, ll_.size()); }
 
 private:
     void apply_recording(const std::vector<std::int32_t>& ids, bool user) {
@@ -843,6 +865,7 @@ private:
     std::vector<double> y_, z_, ll_;
     std::vector<std::int32_t> ids_;                        // set for the next evaluation
     bool user_ = false;
+    std::size_t nparts_ = 0;
     std::size_t T_ = 0, n_run_ = 0;                        // n_run_: built-in functionals the last evaluation recorded
 };
 

@@ -283,13 +283,46 @@ int ssme_pf_smoothing_elapsed_ms(ssme_pf_handle h, float* kernel_ms, float* call
  * (as above); SSME_ERR_UNSUPPORTED: SSME_MODEL_USER0 whose header declares no transition density (logf / logf_vec of
  * ssme_amd/csrc/model_api.h; ssme_pf_user_model_has_logf, which needs no device: 0 for the stock library).  Built-in models:
  * log f = -((xn - mean) / sd)^2 / 2 with the mean of the proposal in its own operation order.
- * Out of scope: Liu-West and sharded handles, rejection-sampling / MCMC backward steps, marginal O(N^2) smoothing weights and
- * backward-simulated expectations of a user header's functionals. */
+ * Out of scope: Liu-West and sharded handles, rejection-sampling / MCMC backward steps and backward-simulated expectations of a user
+ * header's functionals; the marginal O(N^2) smoothing weights follow below. */
 int ssme_pf_user_model_has_logf(void);
 int ssme_pf_backward_bytes(ssme_pf_handle h, int32_t T, uint64_t* bytes);
 int ssme_pf_download_series_logweights(ssme_pf_handle h, int32_t filter, int32_t t, double* lw /*N*/);
 int ssme_pf_sample_trajectories_backward(ssme_pf_handle h, int32_t K, const uint32_t* terminal /*[R][K] or NULL*/,
                                          double* x_out /*[((r*K + k)*T + t)*dim_x + d]*/, uint32_t* index_out /*[(r*K + k)*T + t] or NULL*/, int32_t T);
+/* Marginal smoothing weights (forward filtering, backward smoothing: Doucet, Godsill and Andrieu 2000; ssme_amd/csrc/marginal.h,
+ * DESIGN.md section 12.2): the EXPECTATION of the backward draws above, a weight per particle of every step of the recorded history,
+ *   om_{T-1}[j] = w_j, the unnormalised final weights of ssme_pf_download_weights, bit for bit;  for t = T-2 .. 0, with the covariates
+ *   of step t + 1:  a_ij = lw_t[i] + logf(x_{t+1}[j] | x_t[i], z_{t+1}) (NaN counts as -inf), m_j = max_i a_ij,
+ *   q_ij = rint(exp(a_ij - m_j) 2^sh) (the quantiser and sh of backward simulation), D_j = sum_i q_ij (an exact integer below 2^53);
+ *   column j is live when m_j is finite and D_j > 0, then c_j = om_{t+1}[j] / D_j; otherwise it is degenerate and its mass goes to its
+ *   genealogical parent g(j) = min(anc_{t+1}[j], N - 1) where step t + 1 resampled, j otherwise:
+ *   om_t[i] = sum_{j live} c_j q_ij + sum_{j degenerate, g(j) = i} om_{t+1}[j].
+ * q_ij / D_j and the fallback are, to the bit, what ssme_pf_sample_trajectories_backward draws B_t from given B_{t+1} = j, so om_t is
+ * the exact law of B_t when B_{T-1} is drawn from the final weights: smoothed means without the noise of K draws and without the path
+ * degeneracy of the genealogy, at 3 N^2 (T - 1) density evaluations.  The sum over j is a floating-point sum of non-negative terms in a
+ * FIXED order that depends on N alone (no atomics; chunks of 64 columns dealt round-robin to 8 partial sums, each in ascending j, the
+ * 8 then added in order): two calls from one history return the same bits, whatever the bank shape or the route.  Rows are not normalised: sum_i
+ * om_t[i] equals sum_j w_j up to rounding.
+ * ssme_pf_marginal_smoothing_bytes: the device bytes a T-step history needs for this, 32 T R Npad -- 8 T R Npad of them the
+ * log-weight rows it shares with backward simulation (ssme_pf_backward_bytes), 8 T R Npad the weight rows, 16 T R Npad the column
+ * tables m and D.  Makes no HIP call.  All of it is filled by the first marginal call after a recording run (the log-weight rows
+ * first, unless backward simulation already did), reused while that history is in force, stale the moment the handle moves on and
+ * freed with the history rows; a refused allocation is SSME_ERR_HIP, the handle stays usable and the history in force.
+ * ssme_pf_download_smoothing_weights: x_t (x[d * N + i], dim_x planes, or NULL) and om_t (w, N values) of one filter, for host-side
+ * functionals: the caller forms sum h(x_t[i]) om_t[i] / sum om_t[i].
+ * ssme_pf_get_marginal_smoothed_expectations: out[(t n + i) R + r] = sum_j h_i(x_t[j]) om_t[j] / sum_j om_t[j] for n = 1 .. 4 built-in
+ * functionals (SSME_H_*; component 0 of a vector state) in a fixed summation tree; NaN where sum_j om_t[j] is not > 0.
+ * A filter without final weight gets all-zero weight rows and NaN expectation rows (SSME_OK).  SSME_F32 handles round x, w and out to
+ * float.  A call changes nothing the other smoothing calls return.  ssme_pf_smoothing_elapsed_ms reports these calls too.
+ * Validated before any HIP call, as ssme_pf_sample_trajectories_backward validates -- SSME_ERR_INVALID_ARG: NULL handle, bytes, w,
+ * out or functionals, filter or t out of range, n < 1 or n > 4, a functional id out of range, T < 1 or different from the recorded
+ * length; SSME_ERR_STATE: sharded handles, no history in force; SSME_ERR_UNSUPPORTED: SSME_MODEL_USER0 without logf / logf_vec.
+ * Out of scope: Liu-West and sharded handles, device-side expectations of a user header's own functionals (the weight rows serve
+ * those on the host), two-filter smoothing and sub-quadratic approximations. */
+int ssme_pf_marginal_smoothing_bytes(ssme_pf_handle h, int32_t T, uint64_t* bytes);
+int ssme_pf_download_smoothing_weights(ssme_pf_handle h, int32_t filter, int32_t t, double* x /*[dim_x][N] or NULL*/, double* w /*N*/);
+int ssme_pf_get_marginal_smoothed_expectations(ssme_pf_handle h, const int32_t* functionals, int32_t n, double* out /*[(t*n + i)*R + r]*/, int32_t T);
 /* Arbitrary host-side h (the reference's filt_func is a std::function, pswarm_filter.h:44,87-89): particles x (N,
  * nullable) and weights w (N) of one filter after the last step, w_j = exp(logw_j - max logw) in the 2^-41 fixed point
  * the resampler and ssme_pf_get_expectations use; the caller forms sum h(x_j) w_j / sum w_j.  Needs no debug mode. */

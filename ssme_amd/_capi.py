@@ -29,6 +29,7 @@ EXPORTS = [
     "ssme_pf_test_philox", "ssme_pf_test_quantize", "ssme_pf_test_rescale", "ssme_pf_test_block_scan",
     "ssme_pf_test_copy", "ssme_pf_test_gamma",
     "ssme_pf_user_model_has_logf", "ssme_pf_backward_bytes", "ssme_pf_download_series_logweights", "ssme_pf_sample_trajectories_backward",
+    "ssme_pf_marginal_smoothing_bytes", "ssme_pf_download_smoothing_weights", "ssme_pf_get_marginal_smoothed_expectations",
     "ssme_pf_strerror", "ssme_pf_last_error",
     "ssme_pf_version",
     "ssme_lw_create", "ssme_lw_destroy", "ssme_lw_reset", "ssme_lw_step", "ssme_lw_run_series", "ssme_lw_get_per_step",
@@ -123,6 +124,9 @@ def lib():
         L.ssme_pf_backward_bytes.argtypes = [H, C.c_int32, u64p]
         L.ssme_pf_download_series_logweights.argtypes = [H, C.c_int32, C.c_int32, dp]
         L.ssme_pf_sample_trajectories_backward.argtypes = [H, C.c_int32, u32p, dp, u32p, C.c_int32]
+        L.ssme_pf_marginal_smoothing_bytes.argtypes = [H, C.c_int32, u64p]
+        L.ssme_pf_download_smoothing_weights.argtypes = [H, C.c_int32, C.c_int32, dp, dp]
+        L.ssme_pf_get_marginal_smoothed_expectations.argtypes = [H, i32p, C.c_int32, dp, C.c_int32]
         L.ssme_pf_download_state.argtypes = [H, C.c_int32, dp, dp, u64p, u32p]
         L.ssme_pf_download_scalars.argtypes = [H, C.c_int32, dp, u64p, u64p, dp, i32p]
         L.ssme_pf_set_debug.argtypes = [H, C.c_int32]

@@ -10,7 +10,9 @@
 #include "forecast.h"
 #include "smooth.h"
 #include "backward.h"
+#include "marginal.h"
 #include "series_history.h"
+#include "marginal_state.h"
 #include "handle_core.h"
 #include "shard_driver.h"
 
@@ -99,6 +101,11 @@ struct ssme_pf_s : HandleCore {
     // backward simulation (backward.h): the pre-resampling log-weights of every step of the history, recomputed on first use
     double* bs_lw;               // [hist.lw_cap][R][Npad]; freed with the history rows
     int hist_has_z;              // the recorded series had covariates (zbuf holds them; 0: the kernels read zeros)
+    // marginal smoothing (marginal.h): the weight rows om, then the column tables m and D, each [msm.cap][R][Npad]; freed with the history rows
+    MarginalRowsState msm;       // do they hold the history in force?  Told of every event of `hist` (marginal_state.h)
+    double* ms_rows;
+    double* ms_out;              // [T][4][R] the smoothed means, ms_cap_out doubles
+    size_t ms_cap_out;
     std::vector<ModelConst> h_mc;
     // forecast (HandleCore::fc): fc.x0 is [dx][R][Npad], the samples fc.y / fc.x [R][H][dy][Ns] / [R][H][dx][Ns]
     std::vector<double> h_gscale;    // per filter: scale of the observation draw (set_params)
@@ -540,7 +547,7 @@ static int do_reset(ssme_pf_handle h) {
     if (h->l2_ticket) HIPCHK(hipMemsetAsync(h->l2_ticket, 0, sizeof(int32_t) * h->R, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));   // sc is a temporary
     h->t = 0; h->cur = 0;
-    h->hist.moved_on();                         // the smoothing weights live in the state that is discarded here
+    h->hist.moved_on(); h->msm.moved_on();                         // the smoothing weights live in the state that is discarded here
     h->gamma_rows = 0;                          // tables are redrawn for the new stream / the new series
     return SSME_OK;
 }
@@ -636,15 +643,15 @@ static int ensure_trajectory(ssme_pf_handle h, int T) {
 static int ensure_history(ssme_pf_handle h, int T) {
     if (!h->hist.on) {
         if (h->hist_x || h->hist_anc) { drop_graph(h); own_free(h, h->hist_x); own_free(h, h->hist_anc); }
-        own_free(h, h->bs_lw);
-        h->hist.rows_dropped();
+        own_free(h, h->bs_lw); own_free(h, h->ms_rows);
+        h->hist.rows_dropped(); h->msm.dropped();
         return SSME_OK;
     }
     if (T <= h->hist.cap) return SSME_OK;
     // the rows are replaced: whatever history they held is no longer in force, whether or not the new allocation succeeds
     drop_graph(h);
-    own_free(h, h->hist_x); own_free(h, h->hist_anc); own_free(h, h->bs_lw);
-    h->hist.rows_dropped();
+    own_free(h, h->hist_x); own_free(h, h->hist_anc); own_free(h, h->bs_lw); own_free(h, h->ms_rows);
+    h->hist.rows_dropped(); h->msm.dropped();
     const size_t np = (size_t)h->R * h->Npad;
     hipError_t e = own_alloc(h, h->hist_x, sizeof(double) * (size_t)T * h->dx * np);
     if (e == hipSuccess) e = own_alloc(h, h->hist_anc, sizeof(uint32_t) * (size_t)T * np);
@@ -688,7 +695,7 @@ static hipError_t launch_fc_user(ssme_pf_handle h, const FcArgs& a) {
 
 extern "C" {
 
-int ssme_pf_version(void) { return 333; }
+int ssme_pf_version(void) { return 334; }
 
 const char* ssme_pf_strerror(int s) {
     switch (s) {
@@ -1230,7 +1237,7 @@ int ssme_pf_step(ssme_pf_handle h, const double* y, const double* z, double* out
     if (h->split_l2) launch_kf(h, h->t, false, want ? h->pin_dev + PinLayout::results : nullptr);
     HIPCHK(hipGetLastError());
     h->t += 1;
-    h->hist.moved_on();                                // the final weights of the recorded series are gone
+    h->hist.moved_on(); h->msm.moved_on();                                // the final weights of the recorded series are gone
     if (want) HIPCHK(wait_results(h->stream, res, h->R));
     if (out) for (int r = 0; r < h->R; ++r) out[r] = res[r];
     round_out(h, out, h->R);
@@ -1289,7 +1296,7 @@ int ssme_pf_run_series(ssme_pf_handle h, const double* y, const double* z, int32
     if (!h->params_set) return SSME_ERR_STATE;
     HIPCHK(hipSetDevice(h->cfg.device));
     h->rec_T = 0;                                      // rows are valid once the series is queued; a failure below leaves none
-    h->hist.moved_on();                                // ... and no history in force: the one of an earlier series ends here
+    h->hist.moved_on(); h->msm.moved_on();                                // ... and no history in force: the one of an earlier series ends here
     int rc = ensure_series_capacity(h, T);
     if (rc == SSME_OK) rc = ensure_trajectory(h, T);
     if (rc == SSME_OK) rc = ensure_history(h, T);
@@ -1345,7 +1352,7 @@ int ssme_pf_run_series(ssme_pf_handle h, const double* y, const double* z, int32
     rc = read_loglik(h, loglik_out);
     if (rc != SSME_OK) return rc;
     HIPCHK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
-    h->hist.recorded(T);                               // in force until the handle moves on (run_series, do_reset, ssme_pf_step)
+    h->hist.recorded(T); h->msm.moved_on();                               // in force until the handle moves on (run_series, do_reset, ssme_pf_step)
     round_out(h, loglik_out, h->R);
     return SSME_OK;
 }
@@ -1624,6 +1631,106 @@ int ssme_pf_sample_trajectories_backward(ssme_pf_handle h, int32_t K, const uint
     rc = smoothing_end(h);
     if (rc != SSME_OK) return rc;
     round_out(h, x_out, nx);
+    return SSME_OK;
+}
+
+// ---- marginal smoothing weights (kernels: marginal.h; the state of the rows: marginal_state.h) ----
+int ssme_pf_marginal_smoothing_bytes(ssme_pf_handle h, int32_t T, uint64_t* bytes) {
+    if (!h || !bytes || T < 1) return SSME_ERR_INVALID_ARG;
+    if (h->shard_world > 0) return SSME_ERR_STATE;
+    // 8 (the log-weight rows, shared with backward simulation: ssme_pf_backward_bytes) + 8 (om) + 16 (m and D) bytes per particle and step
+    *bytes = (uint64_t)32 * (uint64_t)T * (uint64_t)h->R * (uint64_t)h->Npad;
+    return SSME_OK;
+}
+
+extern "C++" {
+constexpr int kMsmNJ = 2;          // columns per thread of k_msm_columns
+template <int MODEL>
+static void launch_msm_fill(ssme_pf_handle h, const MsmArgs& a, int T) {
+    if constexpr (MODEL != MODEL_USER0 || kUserHasLogf) {
+        hipLaunchKernelGGL(k_msm_start, dim3(h->B, h->R), dim3(kThreads), 0, h->stream, a, (const double*)h->tmax[h->cur]);
+        if (T < 2) return;
+        const unsigned gx = (unsigned)((h->N + kThreads * kMsmNJ - 1) / (kThreads * kMsmNJ));
+        for (int t0 = 0; t0 < T - 1; t0 += 65535) {
+            const int steps = T - 1 - t0 < 65535 ? T - 1 - t0 : 65535;
+            hipLaunchKernelGGL((k_msm_columns<MODEL, kMsmNJ>), dim3(gx, steps, h->R), dim3(kThreads), 0, h->stream, a, t0);
+        }
+        const dim3 grid((h->N + 63) / 64, h->R);
+        for (int t = T - 2; t >= 0; --t) hipLaunchKernelGGL((k_msm_rows<MODEL>), grid, dim3(64 * kMsmSeg), 0, h->stream, a, t);
+    }
+}
+}  // extern "C++"
+
+// The weight rows of the history in force (T steps): the log-weight rows first (backward_weights), then om, m and D, filled on the first
+// marginal call after the recording run and reused while that history stays in force (marginal_state.h).  a->b.s: smoothing_begin's.
+static int marginal_rows(ssme_pf_handle h, int T, MsmArgs* a) {
+    int rc = backward_weights(h, T, &a->b);
+    if (rc != SSME_OK) return rc;
+    const size_t n = (size_t)T * h->R * h->Npad;
+    if (h->msm.query(h->ms_rows != nullptr, T) == MarginalRowsState::rows_allocate) {
+        h->msm.dropped();
+        const hipError_t e = own_alloc(h, h->ms_rows, sizeof(double) * 3 * n);
+        if (e != hipSuccess) { (void)hipGetLastError(); return fail(h, "marginal smoothing rows (ssme_pf_marginal_smoothing_bytes)", e); }
+        h->msm.ready(T);
+    }
+    const size_t cap = (size_t)h->msm.cap * h->R * h->Npad;
+    a->om = h->ms_rows; a->cm = h->ms_rows + cap; a->cD = h->ms_rows + 2 * cap;
+    if (h->msm.query(true, T) == MarginalRowsState::rows_fill) {
+        with_model(h->cfg.model, [&](auto m) { launch_msm_fill<decltype(m)::value>(h, *a, T); });
+        HIPCHK(hipGetLastError());
+        h->msm.filled(T);
+    }
+    return SSME_OK;
+}
+
+int ssme_pf_download_smoothing_weights(ssme_pf_handle h, int32_t filter, int32_t t, double* x, double* w) {
+    if (!h || !w || filter < 0 || filter >= h->R || t < 0) return SSME_ERR_INVALID_ARG;
+    // as ssme_pf_download_series_logweights: the handle's state, then the range of t, before any HIP call
+    if (h->shard_world > 0) return SSME_ERR_STATE;
+    if (h->cfg.model == SSME_MODEL_USER0 && !kUserHasLogf) return SSME_ERR_UNSUPPORTED;
+    if (h->hist.query(h->hist_x && h->hist_anc, h->hist.T) != SeriesHistoryState::in_force) {
+        h->err = "no series history in force: ssme_pf_set_series_history, then ssme_pf_run_series";
+        return SSME_ERR_STATE;
+    }
+    if (t >= h->hist.T) return SSME_ERR_INVALID_ARG;
+    MsmArgs a{};
+    int rc = smoothing_begin(h, h->hist.T, &a.b.s);
+    if (rc == SSME_OK) rc = marginal_rows(h, h->hist.T, &a);
+    if (rc != SSME_OK) return rc;
+    HIPCHK(hipEventRecord(h->sm_ev[2], h->stream));
+    const size_t plane = (size_t)h->R * h->Npad, off = (size_t)filter * h->Npad;
+    HIPCHK(hipMemcpyAsync(w, a.om + (size_t)t * plane + off, sizeof(double) * h->N, hipMemcpyDeviceToHost, h->stream));
+    if (x) for (int d = 0; d < h->dx; ++d)                 // vector models: dim_x planes, x[d * N + i]
+        HIPCHK(hipMemcpyAsync(x + (size_t)d * h->N, h->hist_x + ((size_t)t * h->dx + d) * plane + off, sizeof(double) * h->N, hipMemcpyDeviceToHost, h->stream));
+    rc = smoothing_end(h);
+    if (rc != SSME_OK) return rc;
+    round_out(h, x, (size_t)h->dx * h->N);
+    round_out(h, w, h->N);
+    return SSME_OK;
+}
+
+int ssme_pf_get_marginal_smoothed_expectations(ssme_pf_handle h, const int32_t* functionals, int32_t n, double* out, int32_t T) {
+    if (!h || !out || !functionals || n < 1 || n > kMaxFunctionals || T < 1) return SSME_ERR_INVALID_ARG;
+    FunctionalIds fs{};
+    fs.n = n;
+    for (int i = 0; i < n; ++i) {
+        if (functionals[i] < SSME_H_X || functionals[i] > SSME_H_CONST42) return SSME_ERR_INVALID_ARG;
+        fs.id[i] = functionals[i];
+    }
+    if (h->cfg.model == SSME_MODEL_USER0 && !kUserHasLogf && h->shard_world == 0) return SSME_ERR_UNSUPPORTED;
+    MsmArgs a{};
+    int rc = smoothing_begin(h, T, &a.b.s);
+    if (rc == SSME_OK) rc = marginal_rows(h, T, &a);
+    const size_t nout = (size_t)T * n * h->R;
+    if (rc == SSME_OK) rc = sm_grow(h, h->ms_out, h->ms_cap_out, (size_t)T * kMaxFunctionals * h->R);
+    if (rc != SSME_OK) return rc;
+    hipLaunchKernelGGL(k_msm_expect, dim3((unsigned)((size_t)T * h->R)), dim3(kThreads), 0, h->stream, a, fs, h->ms_out);
+    HIPCHK(hipEventRecord(h->sm_ev[2], h->stream));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, h->ms_out, sizeof(double) * nout, hipMemcpyDeviceToHost, h->stream));
+    rc = smoothing_end(h);
+    if (rc != SSME_OK) return rc;
+    round_out(h, out, nout);
     return SSME_OK;
 }
 

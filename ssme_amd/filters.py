@@ -340,6 +340,32 @@ class ParticleFilterBank:
             out[:, i, :] = hs[f](x).mean(axis=1).T
         return out
 
+    def marginal_smoothing_bytes(self, T):
+        """Device bytes marginal smoothing keeps for a T-step history: 32 T R Npad, 8 T R Npad of them the log-weight rows it shares
+        with backward simulation (backward_bytes).  No device call."""
+        b = C.c_uint64()
+        self._chk(capi.lib().ssme_pf_marginal_smoothing_bytes(self._h, int(T), C.byref(b)))
+        return int(b.value)
+
+    def smoothing_weights(self, f, t):
+        """(x, w): the population x_t of filter f ([N], or [dim_x, N] for a vector model) and its marginal smoothing weights om_t[N]
+        over the history of the last run_series (ssme_pf_download_smoothing_weights): the exact law of the backward-simulated B_t, not
+        normalised.  A host-side functional h has the smoothed mean sum(h(x) * w) / sum(w)."""
+        dx = self._dims()[0]
+        x, w = (np.empty(self.n) if dx == 1 else np.empty((dx, self.n))), np.empty(self.n)
+        self._chk(capi.lib().ssme_pf_download_smoothing_weights(self._h, int(f), int(t), capi.dptr(x), capi.dptr(w)))
+        return x, w
+
+    def marginal_smoothed_expectations(self, functionals):
+        """E[h_i(x_t) | y_{0:T-1}] for every step t of the last run_series (recorded with record_series_history) under the marginal
+        smoothing weights, up to 4 built-in functionals (component 0 of a vector state): [T, n, R].  No draw noise and no path
+        degeneracy, at 3 N^2 (T - 1) density evaluations on the first call after the run."""
+        fs = np.ascontiguousarray(functionals, dtype=np.int32)
+        out = np.empty((self._last_T, max(fs.size, 1), self.r))
+        self._chk(capi.lib().ssme_pf_get_marginal_smoothed_expectations(self._h, fs.ctypes.data_as(C.POINTER(C.c_int32)), fs.size,
+                                                                        capi.dptr(out), self._last_T))
+        return out
+
     def smoothing_elapsed_ms(self):
         """HIP-event times (ms) of the last sample_trajectories / smoothed_expectations: (kernels alone, call without the download)."""
         k, c = C.c_float(), C.c_float()
